@@ -3,11 +3,18 @@
 one light, 3x3 supersampling) on N MI355X.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload rt|rast|c4|c5]
-                  [--no-cpu-baseline]
+                  [--dump-outputs DIR] [--full [--no-cpu-baseline] ...]
 
 --workload rt (default) is the metric's config C2; rast is C3; c4 (3840x2160,
 8x8 area light = 64 lights) and c5 (1080p over 1M random triangles) are the
 build-defined SURVEY.md 8d workloads, measured the same way.
+
+A plain run sets up, renders the W warm-up frames, times the K steps, writes
+the last step's outputs if --dump-outputs is given and prints the result line.
+--full adds everything else to that line: the roofline, the CPU baseline, the
+golden and in-call parity flags, the settled-clock figure, the host-buffer
+`draw` record, the single-Draw latency of the rasteriser, and (rt) the C3/C4/C5
+sub-records; its --no-* options drop single parts again.
 
 A step is one whole frame, inputs resident in HBM.  N = 1: frames rendered 32
 per cg_rt_render_frames_device call.  N > 1 (default layout `bands`): every
@@ -589,6 +596,26 @@ def cpu_baseline_rast(gpu_frame, budget_s=10.0):
             "frame_matches_gpu": bool(np.array_equal(ref, gpu_frame))}
 
 
+DUMP_BUDGET = 64 * 10**6     # bytes, over all files of one --dump-outputs
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: array} as path/<name>.npy.  Integer outputs go out as float64 (a
+    uint32 ARGB pixel is exact there), float ones as float32.  When they exceed the byte budget
+    together, each is cut to a sample of its elements in index order: the same seeded indices in
+    every run, so two builds' files still compare element for element."""
+    os.makedirs(path, exist_ok=True)
+    conv = {k: np.asarray(v).astype(np.float32 if np.asarray(v).dtype.kind == "f" else np.float64)
+            for k, v in arrays.items()}
+    total = sum(a.nbytes for a in conv.values())
+    for k, a in conv.items():
+        if total > DUMP_BUDGET:
+            keep = int(a.size * 0.98 * DUMP_BUDGET / total)
+            idx = np.sort(np.random.default_rng(0x5EED).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -596,9 +623,15 @@ def main():
                     help="timed frames (default: rt/rast/f256 800 = 25 RT calls of 32, c4 64, c5 20, yaw 320)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed frames (default: rt/rast 32, c4/c5 3)")
     ap.add_argument("--workload", choices=["rt", "rast", "c4", "c5", "c5yaw", "yaw", "f256"], default="rt")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: roofline, CPU baseline, parity flags, settled-clock figure, `draw` "
+                         "record, single-Draw latency and (rt) the C3/C4/C5 sub-records; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (the frame a caller receives) as "
+                         "DIR/<name>.npy, float32 or float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: omit the CPU baseline")
     ap.add_argument("--no-steady", dest="steady", action="store_false",
-                    help="rt, N = 1: omit the informational settled-clock figure measured after the timed region")
+                    help="--full, rt, N = 1: omit the informational settled-clock figure measured after the timed region")
     ap.add_argument("--no-rast", action="store_true", help="rt: omit the C3 `rast` sub-record")
     ap.add_argument("--camera-path", choices=["fixed", "dolly"], default="fixed",
                     help="fixed: the workload's camera every frame (the metric); dolly: cameraPos.z steps 0.005 "
@@ -634,6 +667,9 @@ def main():
     ap.add_argument("--rank-timeout", type=float, default=0.0,
                     help="N > 1 started by bench.py itself: fail the job (exit 124) if a rank runs longer (s; 0 = none)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: the timed steps only (rt_report / measure_rast leave out the rest on args.full)
+        args.no_cpu_baseline, args.steady, args.draw, args.no_sub = True, False, False, True
     if args.layout is None:
         args.layout = "bands" if args.backend == "nccl" else "stripes"
     if args.steps is None:
@@ -672,7 +708,7 @@ def main():
     if args.workload == "rast":
         ctx = cgamd.Context(local)
         rec = measure_rast(args, ctx, dev, stream, sp, world, rank, args.steps, args.warmup,
-                           cpu=world == 1 and not args.no_cpu_baseline)
+                           cpu=world == 1 and not args.no_cpu_baseline, dump=args.dump_outputs)
         if rank == 0:
             print(json.dumps(rec), flush=True)
         if world > 1:
@@ -883,8 +919,11 @@ def measure_rt(args, local, dev, stream, world, rank, distributed):
         b_last, nf_last = state["last"]
         src = frames if distributed else bufs[b_last]
         step_px = RT_H * RT_W if distributed else shard_px
+        # every frame of the last call (--full checks them all); a plain run keeps the last step's only
         outs = [src[k * step_px:k * step_px + RT_H * RT_W].cpu().numpy().view(np.uint32).copy()
-                for k in range(nf_last)]
+                for k in range(0 if args.full else nf_last - 1, nf_last)]
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"argb": outs[-1].reshape(RT_H, RT_W)})
     # informational, after the timed region and its outputs: the same calls back to back once
     # the GPU's clocks have settled (the timed call follows W frames after host-side setup, when
     # the GPU is still at post-idle clocks); never the metric
@@ -935,6 +974,7 @@ def finish_rt(args, local, dev, stream, world, rank, distributed, rec):
             name, steps, warm = item.split(":")
             sub = argparse.Namespace(**vars(args))
             sub.workload, sub.steps, sub.warmup, sub.stripe = name, int(steps), int(warm), None
+            sub.dump_outputs = None                  # the dump is the headline workload's
             r = measure_rt(sub, local, dev, stream, world, rank, distributed)
             if rank == 0:
                 rec[name] = r
@@ -999,7 +1039,10 @@ def rt_bands_loop(args, ctx, dev, stream, world, rank, wl, cam, lights):
     bands = d.bands()
     outs = None
     if rank == 0:
-        outs = [frames[k * H * W:(k + 1) * H * W].cpu().numpy().view(np.uint32).copy() for k in range(st["last"])]
+        outs = [frames[k * H * W:(k + 1) * H * W].cpu().numpy().view(np.uint32).copy()
+                for k in range(0 if args.full else st["last"] - 1, st["last"])]
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"argb": outs[-1].reshape(H, W)})
     r0, nr = bands[rank]
     d.close()
     return dict(elapsed=elapsed, launch_ms=float(allt[rank, 1]) * min(K, 32), kernel_ms=float(allt[rank, 1]), K=K,
@@ -1043,6 +1086,7 @@ def rt_report(args, wl, world, rank, n, n_sph, n_lights, res):
         total = {k: int(v.sum()) for k, v in rc.items()}
         rec["mrays_per_s"] = total["n_ray"] * fps / 1e6
         rec["mrays_counted"] = "every ClosestIntersection call (primary + shadow, SURVEY.md 8d N_ray)"
+    if rc is not None and args.full:
         my_rows = res["my_rows"]
         launch = {k: int(v[my_rows].sum()) for k, v in rc.items()}
         # one lattice launch renders fpl <= 32 frames (a call of K frames is K/32
@@ -1081,7 +1125,9 @@ def rt_report(args, wl, world, rank, n, n_sph, n_lights, res):
                        "lattice_primary_mrays_per_s": (RT_W // 16) * -(-RT_H // 15) * 33 * 31 * fps / 1e6,
                        "lattice_note": "distinct sub-rays the lattice kernel traces (33 x 31 per 16 x 15 tile, "
                                        "tiles with no candidate triangle exit without tracing)"}
-    if args.workload != "rt":
+    if not args.full:
+        pass                            # a plain run: the timed steps' own figures only
+    elif args.workload != "rt":
         bytes_alg = 4.0 * RT_W * RT_H   # per frame
         kern = res.get("dominant_kernel", {"c4": "rt_lattice_lights_kernel", "c5": "rt_big_primary_kernel", "c5yaw": "rt_big_primary_kernel",
                                            "yaw": "rt_lattice_kernel", "f256": "rt_lattice_kernel"}[args.workload])
@@ -1116,11 +1162,14 @@ def rt_report(args, wl, world, rank, n, n_sph, n_lights, res):
         check = outs if args.camera_path == "fixed" else outs[:1]     # dolly: frame 0 has the golden camera
         rec["frame_sha256_matches_golden"] = all(hashlib.sha256(o.tobytes()).hexdigest() == want for o in check)
         rec["frames_checked"] = len(check)
-    if args.camera_path == "fixed":
+    if args.camera_path != "fixed":
+        rec["config"]["camera_path"] = "dolly: cameraPos.z = -3 + 0.005 k for frame k of each call"
+    if not args.full:
+        pass
+    elif args.camera_path == "fixed":
         # every frame of a call has the same camera: the call's frames must be identical
         rec["frames_identical_in_call"] = bool(all(np.array_equal(o, out) for o in outs))
     else:
-        rec["config"]["camera_path"] = "dolly: cameraPos.z = -3 + 0.005 k for frame k of each call"
         rec["frames_distinct_in_call"] = bool(all(not np.array_equal(outs[k], outs[k + 1]) for k in range(len(outs) - 1)))
     if res.get("scratch"):
         sc = res["scratch"]
@@ -1135,7 +1184,7 @@ def rt_report(args, wl, world, rank, n, n_sph, n_lights, res):
     return rec
 
 
-def measure_rast(args, ctx, dev, stream, sp, world, rank, steps, warmup, cpu, cpu_budget_s=10.0):
+def measure_rast(args, ctx, dev, stream, sp, world, rank, steps, warmup, cpu, cpu_budget_s=10.0, dump=None):
     """C3: rasteriser 1920x1080, focal 768 (replicas only across ranks).  A step
     is one frame: the whole Draw on the device -- geometry (shadow volumes +
     clip), span setup, ordered fill, post-pass.  Throughput: frames issued
@@ -1186,6 +1235,52 @@ def measure_rast(args, ctx, dev, stream, sp, world, rank, steps, warmup, cpu, cp
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     kernel_ms = float(sum(a.elapsed_time(b) for a, b in ev) / steps)   # device ms per frame
+    if dump and rank == 0:
+        k = calls[-1] - 1           # the last timed step's frame of the last call
+        dump_outputs(dump, {"argb": argb[k * npx:(k + 1) * npx].cpu().numpy().view(np.uint32).reshape(RAST_H, RAST_W),
+                            "depth": depth[k * npx:(k + 1) * npx].cpu().numpy().reshape(RAST_H, RAST_W)})
+    lat_ms, kt_single = rast_single_draw(ctx, p, argb, depth, dev, stream, sp) if args.full else (None, None)
+    if rank != 0:
+        return None
+    fps = world * steps / elapsed
+    rec = {"metric": "frames/sec, 1080p Cornell-box rasteriser", "value": fps, "unit": "frames/s",
+           "n_gpus": world, "steps": steps, "warmup": warmup,
+           "ms_per_step": 1e3 * elapsed / steps, "higher_is_better": True,
+           "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+           "config": {"workload": "rast_cornell_1920x1080_f768", "width": RAST_W, "height": RAST_H,
+                      "focal": RAST_F, "triangles_after_clip": n,
+                      "parallelism": (f"replicas{world}" if world > 1 else "single") +
+                      (f", {B} frames per call overlapped on streams" if B > 1 else "")}}
+    if not args.full:
+        return rec
+    frames = argb.cpu().numpy().view(np.uint32).reshape(B, npx)
+    out = frames[0].copy()
+    same = bool((frames[:calls[-1]] == out).all())
+    bytes_alg = 8.0 * npx          # colour + depth out (SURVEY.md 8d)
+    traffic = load_traffic("rast")
+    rec.update({
+           "single_frame_ms": lat_ms,
+           "single_frame_note": "device time of one cg_rast_draw_device (the whole Draw), frames issued one at "
+                                "a time; median of 45",
+           "single_frame_kernel_ms": kt_single,
+           "single_frame_kernel_note": "mean live HIP-event time per launch of the fill and post kernels over 20 "
+                                       "single Draws of a separate loop (cg_kernel_timing)",
+           "roofline": {"bound": "hbm", "achieved": bytes_alg / (kernel_ms * 1e-3) / 1e9,
+                        "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                        "frac": bytes_alg / (kernel_ms * 1e-3) / 1e9 / PEAK_HBM_GBS,
+                        "traffic": traffic, "traffic_per_algorithmic": (traffic / bytes_alg) if traffic else None,
+                        "algorithmic_bytes_per_frame": bytes_alg, "kernel_ms": kernel_ms,
+                        "kernel": "rast_* (geometry .. fill/post), one frame",
+                        "kernel_note": "device time per frame: each call's HIP-event span / its frames"},
+           "frames_identical_in_batch": same})
+    if cpu:
+        rec["cpu_baseline"] = cpu_baseline_rast(out, cpu_budget_s)
+    return rec
+
+
+def rast_single_draw(ctx, p, argb, depth, dev, stream, sp):
+    """--full: (median device ms of one cg_rast_draw_device, the fill and post kernels' own ms in
+    it), measured after the timed steps."""
     # single-frame latency: one Draw at a time (the reference's own use)
     lat = []
     for _ in range(50):
@@ -1205,39 +1300,7 @@ def measure_rast(args, ctx, dev, stream, sp, world, rank, steps, warmup, cpu, cp
     kt = read_kernel_times()
     cgamd.kernel_timing(False)
     kt_single = {k: live_kernel_ms(kt, k)[0] for k in ("rast_fill_kernel", "rast_post_kernel")}
-    if rank != 0:
-        return None
-    frames = argb.cpu().numpy().view(np.uint32).reshape(B, npx)
-    out = frames[0].copy()
-    same = bool((frames[:calls[-1]] == out).all())
-    fps = world * steps / elapsed
-    bytes_alg = 8.0 * npx          # colour + depth out (SURVEY.md 8d)
-    traffic = load_traffic("rast")
-    rec = {"metric": "frames/sec, 1080p Cornell-box rasteriser", "value": fps, "unit": "frames/s",
-           "n_gpus": world, "steps": steps, "warmup": warmup,
-           "ms_per_step": 1e3 * elapsed / steps, "higher_is_better": True,
-           "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-           "config": {"workload": "rast_cornell_1920x1080_f768", "width": RAST_W, "height": RAST_H,
-                      "focal": RAST_F, "triangles_after_clip": n,
-                      "parallelism": (f"replicas{world}" if world > 1 else "single") +
-                      (f", {B} frames per call overlapped on streams" if B > 1 else "")},
-           "single_frame_ms": lat_ms,
-           "single_frame_note": "device time of one cg_rast_draw_device (the whole Draw), frames issued one at "
-                                "a time; median of 45",
-           "single_frame_kernel_ms": kt_single,
-           "single_frame_kernel_note": "mean live HIP-event time per launch of the fill and post kernels over 20 "
-                                       "single Draws of a separate loop (cg_kernel_timing)",
-           "roofline": {"bound": "hbm", "achieved": bytes_alg / (kernel_ms * 1e-3) / 1e9,
-                        "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                        "frac": bytes_alg / (kernel_ms * 1e-3) / 1e9 / PEAK_HBM_GBS,
-                        "traffic": traffic, "traffic_per_algorithmic": (traffic / bytes_alg) if traffic else None,
-                        "algorithmic_bytes_per_frame": bytes_alg, "kernel_ms": kernel_ms,
-                        "kernel": "rast_* (geometry .. fill/post), one frame",
-                        "kernel_note": "device time per frame: each call's HIP-event span / its frames"},
-           "frames_identical_in_batch": same}
-    if cpu:
-        rec["cpu_baseline"] = cpu_baseline_rast(out, cpu_budget_s)
-    return rec
+    return lat_ms, kt_single
 
 
 if __name__ == "__main__":

@@ -19,10 +19,10 @@ step() {  # name timeout cmd...
 step tests 300 python -u -m pytest tests/test_rt_big_gpu.py tests/test_dist_gpu.py -m gpu -x -q --timeout 120 --timeout-method thread
 for i in 1 2; do
   for n in 1 2 3 4; do
-    step c5_slots${n}_$i 150 env CG_BIG_SLOTS=$n python bench.py --workload c5 --steps 20 --warmup 3 --no-cpu-baseline
+    step c5_slots${n}_$i 150 env CG_BIG_SLOTS=$n python bench.py --full --workload c5 --steps 20 --warmup 3 --no-cpu-baseline
   done
 done
-step c5yaw_slots1 150 env CG_BIG_SLOTS=1 python bench.py --workload c5yaw --steps 20 --warmup 3 --no-cpu-baseline
-step c5yaw_slots2 150 env CG_BIG_SLOTS=2 python bench.py --workload c5yaw --steps 20 --warmup 3 --no-cpu-baseline
-step c5yaw_slots3 150 env CG_BIG_SLOTS=3 python bench.py --workload c5yaw --steps 20 --warmup 3 --no-cpu-baseline
+step c5yaw_slots1 150 env CG_BIG_SLOTS=1 python bench.py --full --workload c5yaw --steps 20 --warmup 3 --no-cpu-baseline
+step c5yaw_slots2 150 env CG_BIG_SLOTS=2 python bench.py --full --workload c5yaw --steps 20 --warmup 3 --no-cpu-baseline
+step c5yaw_slots3 150 env CG_BIG_SLOTS=3 python bench.py --full --workload c5yaw --steps 20 --warmup 3 --no-cpu-baseline
 echo ab done

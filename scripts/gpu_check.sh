@@ -26,24 +26,24 @@ if [ "$MODE" = all ] || [ "$MODE" = test ]; then
   step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 fi
 if [ "$MODE" = all ] || [ "$MODE" = bench ]; then
-  step bench_rt 600 python bench.py
-  step bench_rast 300 python bench.py --workload rast
-  step bench_c4 300 python bench.py --workload c4 --steps 30 --warmup 3
-  step bench_c5 300 python bench.py --workload c5 --steps 20 --warmup 2
-  step bench_yaw 300 python bench.py --workload yaw
-  step bench_f256 300 python bench.py --workload f256
-  step bench_c5yaw 300 python bench.py --workload c5yaw --steps 20 --warmup 2
+  step bench_rt 600 python bench.py --full
+  step bench_rast 300 python bench.py --full --workload rast
+  step bench_c4 300 python bench.py --full --workload c4 --steps 30 --warmup 3
+  step bench_c5 300 python bench.py --full --workload c5 --steps 20 --warmup 2
+  step bench_yaw 300 python bench.py --full --workload yaw
+  step bench_f256 300 python bench.py --full --workload f256
+  step bench_c5yaw 300 python bench.py --full --workload c5yaw --steps 20 --warmup 2
 fi
 if [ "$MODE" = all ] || [ "$MODE" = prof ]; then
   cd /tmp
   step rocprof_rt 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_rt" -o rt -- \
-      python3 "$ROOT/bench.py" --no-cpu-baseline
+      python3 "$ROOT/bench.py" --full --no-cpu-baseline
   step rocprof_rast 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_rast" -o rast -- \
-      python3 "$ROOT/bench.py" --workload rast --no-cpu-baseline
+      python3 "$ROOT/bench.py" --full --workload rast --no-cpu-baseline
   step rocprof_c4 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_c4" -o c4 -- \
-      python3 "$ROOT/bench.py" --workload c4 --steps 10 --warmup 2 --no-cpu-baseline
+      python3 "$ROOT/bench.py" --full --workload c4 --steps 10 --warmup 2 --no-cpu-baseline
   step rocprof_c5 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_c5" -o c5 -- \
-      python3 "$ROOT/bench.py" --workload c5 --steps 10 --warmup 2 --no-cpu-baseline
+      python3 "$ROOT/bench.py" --full --workload c5 --steps 10 --warmup 2 --no-cpu-baseline
   cd "$ROOT"
 fi
 echo done

@@ -224,3 +224,56 @@ def test_default_line_useful_fraction_matches_counts():
         assert ro["useful_counts_file"] == "profiles/" + os.path.basename(paths[-1])
         assert 0 < ro["useful_frac"] <= 1
         assert ro["useful_frac"] == pytest.approx(ro["useful_achieved"] / ro["peak"])
+
+
+def test_dump_outputs_formats_and_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: integer outputs as float64 (exact for a uint32 pixel), float ones as float32,
+    whole and in shape under the byte budget; over it, the same seeded sample of every output's
+    elements (in index order) from run to run, within the budget in all."""
+    b = _bench()
+    argb = np.arange(0xFFFFFF00, 0xFFFFFF00 + 96, dtype=np.uint64).astype(np.uint32).reshape(8, 12)
+    depth = np.linspace(0.0, 1.0, 96, dtype=np.float32).reshape(8, 12)
+    b.dump_outputs(str(tmp_path / "a"), {"argb": argb, "depth": depth})
+    a, d = np.load(tmp_path / "a" / "argb.npy"), np.load(tmp_path / "a" / "depth.npy")
+    assert a.dtype == np.float64 and a.shape == (8, 12) and np.array_equal(a.astype(np.uint32), argb)
+    assert d.dtype == np.float32 and np.array_equal(d, depth)
+    monkeypatch.setattr(b, "DUMP_BUDGET", 600)           # 96 x 8 + 96 x 4 = 1152 bytes: over
+    b.dump_outputs(str(tmp_path / "b"), {"argb": argb, "depth": depth})
+    b.dump_outputs(str(tmp_path / "c"), {"argb": argb + 0, "depth": depth})
+    sb, sc = np.load(tmp_path / "b" / "argb.npy"), np.load(tmp_path / "c" / "argb.npy")
+    assert np.array_equal(sb, sc) and 0 < sb.size < 96 and set(sb) <= set(a.reshape(-1))
+    assert np.all(np.diff(sb) > 0)                       # index order of an increasing array
+    assert sb.nbytes + np.load(tmp_path / "b" / "depth.npy").nbytes <= 600
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_frame(tmp_path, monkeypatch, capsys, golden):
+    """A plain `bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: one JSON line whose
+    value and ms_per_step are of exactly K timed steps, without the records of --full, and the last
+    step's frame in DIR/argb.npy as float64 -- the C2 golden frame, identical run to run."""
+    import hashlib
+    import sys
+    import torch
+    b = _bench()
+    for run in ("a", "b"):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2",
+                                          "--dump-outputs", str(tmp_path / run)])
+        try:
+            b.main()
+        finally:
+            torch.cuda.set_stream(torch.cuda.default_stream())
+    lines = [x for x in capsys.readouterr().out.splitlines() if x.startswith("{")]
+    assert len(lines) == 2
+    d = json.loads(lines[-1])
+    for k in REQUIRED:
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["n_gpus"] == 1 and d["dtype"] == "f32"
+    assert d["metric"].startswith("frames/sec") and d["unit"] == "frames/s" and d["higher_is_better"] is True
+    assert d["ms_per_step"] > 0 and abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 1e-6
+    assert d["kernel_ms_live"]["rt_lattice_kernel"]["launches"] >= 1      # the live kernel timing stays on
+    for k in ("roofline", "cpu_baseline", "draw", "steady_fps_info", "rast", "c4", "c5", "frame_sha256_matches_golden"):
+        assert k not in d, k
+    fa, fb = np.load(tmp_path / "a" / "argb.npy"), np.load(tmp_path / "b" / "argb.npy")
+    assert fa.dtype == np.float64 and fa.shape == (1080, 1920) and np.array_equal(fa, fb)
+    want = golden["rt"]["rt_1920x1080_f1080"]["argb_sha256"]
+    assert hashlib.sha256(fa.astype(np.uint32).tobytes()).hexdigest() == want
