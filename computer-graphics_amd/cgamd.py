@@ -105,6 +105,7 @@ _SIGS = {
     "cg_rt_set_pending_cap": (C.c_int, [P, C.c_int]),
     "cg_rt_scratch_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
     "cg_rt_pool_demand": (C.c_int, [P, C.POINTER(C.c_uint64)]),
+    "cg_rt_tile_masks": (C.c_int, [P, C.c_int, P, P, C.POINTER(C.c_int)]),
     "cg_rt_route": (C.c_int, [C.POINTER(RtCamera), C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "cg_rt_set_pool_caps": (C.c_int, [P, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong]),
     "cg_rt_render_brute_device": (C.c_int, [P, C.POINTER(Light), C.c_int, C.POINTER(RtCamera), C.c_int, C.c_int, P, P]),
@@ -573,6 +574,18 @@ class Context:
         out = (C.c_uint64 * 4)()
         self._check(self.lib.cg_rt_pool_demand(self.h, out), "cg_rt_pool_demand")
         return dict(sup=out[0], bin=out[1], sbin=out[2], sorted=out[3])
+
+    def rt_tile_masks(self, frame=0):
+        """Diagnostic cg_rt_tile_masks: the latest lattice call's tile certificates of one frame as
+        (masks uint64[ty, tx, 2], obj uint64[ty, tx, slots] or None when none were built)."""
+        info = (C.c_int * 4)()
+        self._check(self.lib.cg_rt_tile_masks(self.h, frame, None, None, info), "cg_rt_tile_masks")
+        tx, ty, slots = info[0], info[1], info[2]
+        masks = np.zeros((ty, tx, 2), np.uint64)
+        obj = np.zeros((ty, tx, slots), np.uint64) if slots else None
+        self._check(self.lib.cg_rt_tile_masks(self.h, frame, masks.ctypes.data_as(P),
+                                              obj.ctypes.data_as(P) if slots else None, info), "cg_rt_tile_masks")
+        return masks, obj
 
     def rt_render(self, cam, lights=None, n_lights=None):
         lights = default_lights() if lights is None else lights

@@ -16,7 +16,12 @@ constexpr int kRtTileH = 8;
 constexpr int kRtThreads = 256;
 constexpr int kLatTileW = 16, kLatTileH = 15;   // RT lattice kernel tile (cg_rt.hip): 33 x 31 lattice rays
 constexpr int kSup = 4;              // lattice super-tile: kSup x kSup tiles (two-level certificates)
-constexpr int kMaxFrameBatch = 32;   // frames per batched RT launch (cg_rt_render_frames_device); 16: ~1 % slower on C2
+// Per-object shadow certificates of a lattice tile (rt_tile_cert_kernel): one mask per primary
+// candidate -- slot j < kObjTri = the j-th set triangle bit of the tile's primary mask, slot
+// kObjTri = the sphere -- certified over that candidate's own box of hit positions (bit 63: a
+// sphere may block).  Candidates past the last triangle slot use the tile's union mask.
+constexpr int kObjTri = 7, kObjSlots = kObjTri + 1;
+constexpr int kMaxFrameBatch = 32;  // frames per batched RT launch (cg_rt_render_frames_device); 16: ~1 % slower on C2
 
 constexpr int kMaxBlocks = 64;       // row blocks of one assembly launch (cg_rt_assemble_device)
 

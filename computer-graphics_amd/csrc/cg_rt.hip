@@ -401,8 +401,9 @@ __global__ __launch_bounds__(kRtThreads) void rt_prepare_kernel(const cg_tri *__
 // (cp = the candidate count rounded up to a power of two), segments aligned, so
 // the per-tile reductions are xor butterflies within a segment.  Phase 1:
 // primary certificate, occlusion, hit-position box, sphere; phase 2: shadow
-// certificate of the tile's box.  Same functions and exactness arguments as
-// rt_prepare_kernel's single-level path.
+// certificate of the tile's box; phase 3 (obj_masks): the shadow certificate
+// again per object, over each primary candidate's own box.  Same functions and
+// exactness arguments as rt_prepare_kernel's single-level path.
 
 __device__ __forceinline__ int pow2_at_least(int c)
 {
@@ -423,6 +424,15 @@ __device__ __forceinline__ unsigned long long seg_or(unsigned long long v, int c
         v |= ((unsigned long long)hi << 32) | lo;
     }
     return v;
+}
+
+// Whether a tile gets shadow masks per object (kObjSlots, cg_internal.h): several primary
+// candidates (pm: the primary mask, bit 62 the covered flag) and a shadow mask um that is not
+// already empty; every other tile's objects share the tile's mask.
+__device__ __forceinline__ bool obj_tile(bool cert, unsigned long long pm, unsigned long long um)
+{
+    const unsigned long long c = pm & ~(1ull << 62);
+    return cert && um != 0ull && (c & (c - 1ull)) != 0ull;
 }
 
 // The workgroup is 1 or 4 waves (blockDim.x 64 or 256): wave w takes
@@ -446,6 +456,7 @@ __global__ __launch_bounds__(256, CG_CERT_WAVES) void rt_tile_cert_kernel(const 
                                                            RtFrame F, const RtSphere *__restrict__ sph,
                                                            const unsigned long long *__restrict__ sup_masks,
                                                            unsigned long long *__restrict__ lat_masks,
+                                                           unsigned long long *__restrict__ obj_masks,
                                                            RtTri *__restrict__ tc_out,
                                                            int n_prep_blocks, int frame_fast, LatFlatten Z,
                                                            LatPublish P)
@@ -476,6 +487,7 @@ __global__ __launch_bounds__(256, CG_CERT_WAVES) void rt_tile_cert_kernel(const 
     const int sy = (tiles_y + kSup - 1) / kSup, ud = blk - n_prep_blocks;
     const int uw = (sy - 1 - ud / sxw) * sxw + ud % sxw, unit = (uw / sxw) * sx + s0 + uw % sxw;
     lat_masks += (size_t)frame * tiles_x * tiles_y * 2;
+    if (obj_masks) obj_masks += (size_t)frame * tiles_x * tiles_y * kObjSlots;
     // published certificates (LatPublish): the frame's RtTri stored by this workgroup too, so
     // that a published super-tile implies a complete RtTri (every workgroup of the frame
     // stores the same values)
@@ -505,6 +517,11 @@ __global__ __launch_bounds__(256, CG_CERT_WAVES) void rt_tile_cert_kernel(const 
     __shared__ unsigned long long s_pm[kT], s_own[kT];
     __shared__ float s_box[kT][6];
     __shared__ int s_sphsh[kT];
+    // per-object certificates (obj_masks): each slot's own box of hit positions, its flags (bit 0:
+    // the own-triangle certificate holds, bit 1: a sphere may block) and the tile's union mask
+    __shared__ float s_obox[kT][kObjSlots][6];
+    __shared__ uint8_t s_oflag[kT][kObjSlots];
+    __shared__ unsigned long long s_um[kT];
     auto tile_of = [&](int tl, int &t, LatTile &G) {
         const int bx = (unit % sx) * kSup + tl % kSup, by = (unit / sx) * kSup + tl / kSup;
         const bool in = tl < kT && bx < tiles_x && by < tiles_y;
@@ -569,10 +586,33 @@ __global__ __launch_bounds__(256, CG_CERT_WAVES) void rt_tile_cert_kernel(const 
             blo[q] = lo;
             bhi[q] = hi;
         }
+        // the candidate's slot among the tile's per-object masks (several candidates only: with
+        // one, the tile's masks are that object's)
+        const bool multi = (m & (m - 1ull)) != 0ull;
+        int slot = -1;
+        if (obj_masks && cert && multi && tl < kT) {
+            if (keep) slot = __popcll(m & ((1ull << k) - 1ull));
+            if (slot >= kObjTri) slot = -1;
+            if (sphere) slot = kObjTri;
+        }
+        // k never shadows its own hits (a lone candidate's box is the tile's box)
         bool own = false;
-        if (cert && keep && m == (1ull << k))
-            own = own_shadow_rejects(tris[k], c, pd, thi, camf, x0, x1, y0, y1, F.focal, Lp, F.lrho, blo, bhi);
-        const unsigned long long ownm = seg_or(own ? (1ull << k) : 0ull, cp);
+        if (cert && keep && (m == (1ull << k) || slot >= 0))
+            own = own_shadow_rejects(tris[k], c, pd, thi, camf, x0, x1, y0, y1, F.focal, Lp, F.lrho, pb.lo, pb.hi);
+        const unsigned long long ownm = seg_or((own && m == (1ull << k)) ? (1ull << k) : 0ull, cp);
+        if (slot >= 0) {
+            bool sphsh = F.n_sph > 0 && (SS >> 63);
+            if (sphsh && pb.lo[0] <= pb.hi[0]) {
+                bool any = false;
+                for (int q = 0; q < F.n_sph; ++q) any |= !sphere_shadow_surely_missed_set(sph[q], F, pb.lo, pb.hi);
+                sphsh = any;
+            }
+            for (int q = 0; q < 3; ++q) {
+                s_obox[tl][slot][q] = pb.lo[q];
+                s_obox[tl][slot][3 + q] = pb.hi[q];
+            }
+            s_oflag[tl][slot] = (uint8_t)((own ? 1 : 0) | (sphsh ? 2 : 0));
+        }
         if (tl < kT && ci == 0) {
             const bool live = tile_of(tl, t, G);
             const bool single = m != 0ull && (m & (m - 1ull)) == 0ull && !(m >> 63);
@@ -616,9 +656,79 @@ __global__ __launch_bounds__(256, CG_CERT_WAVES) void rt_tile_cert_kernel(const 
             if ((s_own[tl] >> k) & 1ull) keep_s = false;
         }
         const unsigned long long sm = seg_or(keep_s ? (1ull << k) : 0ull, sp);
-        if (tl < kT && ci == 0 && t >= 0) {
-            lat_masks[2 * t] = live ? pm : 0ull;
-            lat_masks[2 * t + 1] = (live && pm != 0ull) ? (sm | (s_sphsh[tl] ? (1ull << 63) : 0ull)) : 0ull;
+        if (tl < kT && ci == 0) {
+            const unsigned long long um = (live && pm != 0ull) ? (sm | (s_sphsh[tl] ? (1ull << 63) : 0ull)) : 0ull;
+            s_um[tl] = um;
+            if (t >= 0) {
+                lat_masks[2 * t] = live ? pm : 0ull;
+                lat_masks[2 * t + 1] = um;
+                // per object: the tile's mask, except the slots phase 3 fills (their objects')
+                if (obj_masks) {
+                    const bool own = obj_tile(cert, pm, um);
+                    const int nt = __popcll(pm & ~(3ull << 62));
+                    for (int j = 0; j < kObjSlots; ++j) {
+                        const bool on = live && (j < kObjTri ? j < nt : (bool)(pm >> 63));
+                        if (!(own && on)) obj_masks[(size_t)t * kObjSlots + j] = on ? um : 0ull;
+                    }
+                }
+            }
+        }
+    }
+    // Phase 3: per-object shadow masks.  One row per (tile, object with a slot) over the tiles
+    // with several primary candidates and a non-empty shadow mask, rows packed densely as phase
+    // 2's: sp3 lanes a row, lane ci = the ci-th triangle of the tile's shadow mask (sp3 = the
+    // longest such mask rounded up to a power of two).  The tile's shadow candidates are
+    // certified again over the object's own box of hit positions (cull_shadow; unbounded: all
+    // stay), without the object's own triangle where own_shadow_rejects holds.  A subset of the
+    // tile's mask by construction (only its bits are tried).
+    if (obj_masks) {
+        __syncthreads();   // s_um
+        const unsigned long long pmL = lane < kT ? s_pm[lane] : 0ull, umL = lane < kT ? s_um[lane] : 0ull;
+        const bool need = obj_tile(cert, pmL, umL);
+        int incl = need ? min(__popcll(pmL & ~(3ull << 62)), kObjTri) + (int)(pmL >> 63) : 0;
+        for (int o = 1; o < kT; o <<= 1) {   // rows up to and including tile `lane`
+            const int v = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += v;
+        }
+        const int rows = __builtin_amdgcn_readfirstlane(__shfl(incl, kT - 1, 64));
+        int mx = need ? __popcll(umL & ~(1ull << 63)) : 0;
+        for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o, 64));
+        const int sp3 = pow2_at_least(max(__builtin_amdgcn_readfirstlane(mx), 1)), rpi = 64 / sp3;
+        for (int it = wave; it * rpi < rows; it += nwaves) {
+            const int seg = lane / sp3, ci = lane - seg * sp3, row = it * rpi + seg;
+            const bool valid = row < rows;
+            int tl = 0, base = 0;   // the row's tile: the first whose inclusive count exceeds row
+            for (int j = 0; j < kT - 1; ++j) {
+                const int e = __shfl(incl, j, 64);
+                if (valid && row >= e) {
+                    tl = j + 1;
+                    base = e;
+                }
+            }
+            int t;
+            LatTile G;
+            tile_of(tl, t, G);
+            const unsigned long long pm = s_pm[tl], um = s_um[tl];
+            const unsigned long long pmt = pm & ~(3ull << 62), umt = um & ~(1ull << 63);
+            const int a = row - base;   // the object's rank among the tile's objects with a slot
+            const bool is_tri = valid && a < min(__popcll(pmt), kObjTri);
+            const int slot = is_tri ? a : kObjTri, kk = is_tri ? nth_bit(pmt, a) : -1;
+            const bool act = valid && ci < __popcll(umt);
+            const int k = act ? nth_bit(umt, ci) : 0;
+            const int flag = valid ? s_oflag[tl][slot] : 0;
+            bool keep_s = act;
+            if (act) {
+                const float blo[3] = {s_obox[tl][slot][0], s_obox[tl][slot][1], s_obox[tl][slot][2]};
+                const float bhi[3] = {s_obox[tl][slot][3], s_obox[tl][slot][4], s_obox[tl][slot][5]};
+                if (blo[0] <= bhi[0]) {
+                    const RtTri c = rt_tri_const(tris[k], camf[0], camf[1], camf[2], camf[3]);
+                    keep_s = !cull_shadow(c, v3(F.lc[0], F.lc[1], F.lc[2]), F.lrho, shadow_box_of_range(F, blo, bhi));
+                }
+                if (k == kk && (flag & 1)) keep_s = false;
+            }
+            const unsigned long long sm = seg_or(keep_s ? (1ull << k) : 0ull, sp3);
+            if (valid && ci == 0 && t >= 0)
+                obj_masks[(size_t)t * kObjSlots + slot] = sm | (((flag & 2) && (um >> 63)) ? (1ull << 63) : 0ull);
         }
     }
     if (P.flags) {   // publish: every wave's stores written back, then the word (agent-scope release)
@@ -1079,7 +1189,7 @@ __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__r
                                              const RtShade *__restrict__ shade, const RtSphere *__restrict__ sph,
                                              const unsigned long long *__restrict__ lat_masks, const RtFrameCams &cams,
                                              size_t out_stride, uint32_t *__restrict__ out, const LatSlot &S,
-                                             const LatReady &R)
+                                             const LatReady &R, const unsigned long long *__restrict__ obj_masks)
 {
     const int frame = S.frame;
     RtFrame F = F0;
@@ -1087,6 +1197,7 @@ __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__r
     for (int c = 0; c < 4; ++c) F.cam[c] = cams.c[frame][c];
     tc += (size_t)frame * F.n_tris;
     lat_masks += (size_t)frame * lat_tiles_x(F) * gridDim.y * 2;
+    if (obj_masks) obj_masks += (size_t)frame * lat_tiles_x(F) * gridDim.y * kObjSlots;
     const LatOut o = lat_out(F, frame, out_stride, out);
     // (wave as a uniform SGPR value -- readfirstlane -- measured 5 % slower here: 0.913 -> 0.960 ms
     // per 20-frame launch, more VGPRs and SGPRs; the yawed form 0.7 % faster; profiles/r05_ab_walk.json)
@@ -1178,6 +1289,12 @@ __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__r
     if (!(m0 >> 63)) Fp.n_sph = 0;
     RtFrame Fs = F;                        // pass 2: spheres only where one may block a shadow ray
     if (!(s0 >> 63)) Fs.n_sph = 0;
+    // per-object shadow masks (rt_tile_cert_kernel's phase 3; obj_tile(): the same condition)
+    const unsigned long long *objt =
+        (obj_masks && certified && obj_tile(true, m0, s0)) ? obj_masks + tix * kObjSlots : nullptr;
+    // lane j < kObjSlots holds slot j, every other lane the tile's mask (candidates past the last
+    // slot): one vector load ahead of pass 1 instead of dependent scalar loads inside pass 2
+    const unsigned long long vobj = (objt && lane < kObjSlots) ? objt[lane] : s0;
     if (m0 == 0ull) {
         lat_store_black(F, G, o);
         return;                            // the whole workgroup (m0 is uniform)
@@ -1203,9 +1320,9 @@ __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__r
         if (p0 >= p_hi) break;
         const int p = p0 + lane;
         const int cy = p / PITCH, cx = p - cy * PITCH, idx = p;
+        float t = 0.0f;
+        int bi = INT_MIN;
         if (p < p_hi && cx < cols) {
-            float t;
-            int bi;
             if constexpr (kSoA) {
                 const int h = s_h[idx];
                 bi = h == kLatSoaNoHit ? INT_MIN : h;
@@ -1215,17 +1332,34 @@ __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__r
                 bi = __float_as_int(q.w);
                 t = q.x;
             }
-            if (bi != INT_MIN) {
-                const float X = lat_x(F, G, cx), Y = 0.5f * (float)(ay0 + cy);
-                const vec3 pos = v3(F.cam[0] + t * X, F.cam[1] + t * Y, F.cam[2] + t * F.focal);
-                const vec3 dl = lat_direct_light(Fs, tc, sph, s_obj, F.lights[0], bi, pos, smask);
-                if constexpr (kSoA) {
-                    s_v[0][idx] = dl.x;
-                    s_v[1][idx] = dl.y;
-                    s_v[2][idx] = dl.z;
-                } else {
-                    s_pt[idx] = make_float4(dl.x, dl.y, dl.z, __int_as_float(bi));
-                }
+        }
+        // the chunk's shadow candidates: the masks of the objects its points hit, ORed (a point
+        // needs its own object's; the any-hit walk of a superset gives the same answer)
+        unsigned long long cmask = smask;
+        if (objt) {
+            unsigned long long cm = 0ull;
+            for (unsigned long long pend = __ballot(bi != INT_MIN); pend;) {
+                const int b = __builtin_amdgcn_readlane(bi, __builtin_ctzll(pend));
+                int sl = b < 0 ? kObjTri : __popcll(mask & ((1ull << b) - 1ull));
+                if (b >= 0 && sl >= kObjTri) sl = kObjSlots;   // a lane that holds the tile's mask
+                const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(vobj >> 32), sl);
+                const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)vobj, sl);
+                cm |= ((unsigned long long)hi << 32) | lo;
+                pend &= ~__ballot(bi == b);
+            }
+            cmask = cm & ~(1ull << 63);
+            Fs.n_sph = (cm >> 63) ? F.n_sph : 0;
+        }
+        if (bi != INT_MIN) {
+            const float X = lat_x(F, G, cx), Y = 0.5f * (float)(ay0 + cy);
+            const vec3 pos = v3(F.cam[0] + t * X, F.cam[1] + t * Y, F.cam[2] + t * F.focal);
+            const vec3 dl = lat_direct_light(Fs, tc, sph, s_obj, F.lights[0], bi, pos, cmask);
+            if constexpr (kSoA) {
+                s_v[0][idx] = dl.x;
+                s_v[1][idx] = dl.y;
+                s_v[2][idx] = dl.z;
+            } else {
+                s_pt[idx] = make_float4(dl.x, dl.y, dl.z, __int_as_float(bi));
             }
         }
     }
@@ -1731,14 +1865,15 @@ __global__ __launch_bounds__(kRtThreads, kRtMinWaves) void rt_lattice_kernel(RtF
                                                                   const unsigned long long *__restrict__ lat_masks,
                                                                   RtFrameCams cams, size_t out_stride,
                                                                   uint32_t *__restrict__ out, uint32_t *frame_done,
-                                                                  LatOrder O, LatReady R)
+                                                                  LatOrder O, LatReady R,
+                                                                  const unsigned long long *__restrict__ obj_masks)
 {
 #ifdef CG_WG_TIMING
     const unsigned long long wt0 = wall_clock64();
 #endif
     const unsigned long long t_start = wall_clock64();
     const LatSlot S = lat_slot_of(O);
-    lattice_body<PITCH>(F0, tc, shade, sph, lat_masks, cams, out_stride, out, S, R);
+    lattice_body<PITCH>(F0, tc, shade, sph, lat_masks, cams, out_stride, out, S, R, obj_masks);
     // the recording for the next call's order: frame 0's tiles, one class each
     if (O.cost && S.frame == 0 && threadIdx.x == 0)
         O.cost[S.by * (int)gridDim.x + S.bx] = (uint8_t)lat_cost_class(wall_clock64() - t_start);
@@ -1977,10 +2112,14 @@ hipError_t launch_rt_scene(const cg_tri *d_tris, int n, RtGeo *d_geo, RtShade *d
 hipError_t launch_rt_prepare(const cg_tri *d_tris, const RtGeo *d_geo, int n, const RtFrameCams &cams, int nframes,
                              RtTri *d_tc, hipStream_t st, const RtFrame *F, const RtSphere *d_sph,
                              unsigned long long *d_lat_masks, unsigned long long *d_sup_masks, LatFlatten *Z,
-                             LatPublish *pub)
+                             LatPublish *pub, unsigned long long **obj_masks)
 {
     const LatPublish P = pub ? *pub : LatPublish{};
     if (pub) pub->done = 0;
+    // per-object shadow masks (in: the buffer; out: null unless this launch filled it -- only
+    // rt_tile_cert_kernel does, and the lattice launch then walks the tiles' union masks)
+    unsigned long long *d_obj_masks = obj_masks ? *obj_masks : nullptr;
+    if (obj_masks) *obj_masks = nullptr;
     if (n <= 0) return hipSuccess;
     const int threads = kRtThreads, prep = (n + threads - 1) / threads;
     int cert = 0;
@@ -2031,9 +2170,10 @@ hipError_t launch_rt_prepare(const cg_tri *d_tris, const RtGeo *d_geo, int n, co
             const int ff = !P.flags && tprep + units_w <= 65535;
             const dim3 cg = ff ? dim3(nframes, tprep + units_w) : dim3(tprep + units_w, nframes);
             kt_launch(kt_id, rt_tile_cert_kernel, cg, dim3(tthreads), 0, st, d_tris, d_geo, n, cams, Fl, d_sph,
-                               (const unsigned long long *)nullptr, d_lat_masks, d_tc, tprep, ff,
+                               (const unsigned long long *)nullptr, d_lat_masks, d_obj_masks, d_tc, tprep, ff,
                                Z ? *Z : LatFlatten{}, P);
             if (pub) pub->done = P.flags != nullptr;
+            if (obj_masks) *obj_masks = d_obj_masks;
             if (Z) Z->n = -Z->n;   // done (the caller's flag: the lattice launch may use the order)
             return hipGetLastError();
         }
@@ -2052,7 +2192,8 @@ hipError_t launch_rt_prepare(const cg_tri *d_tris, const RtGeo *d_geo, int n, co
         const int ff = units <= 65535;
         kt_launch(kt_id, rt_tile_cert_kernel, ff ? dim3(nframes, units) : dim3(units, nframes), dim3(tthreads), 0, st,
                            d_tris, d_geo, n, cams, Fl, d_sph, (const unsigned long long *)d_sup_masks, d_lat_masks,
-                           (RtTri *)nullptr, 0, ff, LatFlatten{}, LatPublish{});
+                           d_obj_masks, (RtTri *)nullptr, 0, ff, LatFlatten{}, LatPublish{});
+        if (obj_masks) *obj_masks = d_obj_masks;
         return hipGetLastError();
     }
     if (F && d_lat_masks) {   // single-level: every tile (of the window) certified by rt_prepare_kernel
@@ -2136,7 +2277,8 @@ hipError_t launch_rt_lattice_frames(const RtFrame &F, const RtTri *d_tc, const R
                                     const RtSphere *d_sph, const unsigned long long *d_lat_masks,
                                     const unsigned long long *d_umask, const RtFrameCams &cams, int nframes,
                                     size_t out_stride, uint32_t *d_out, hipStream_t st, uint32_t *d_done,
-                                    const LatOrder *order, const LatReady *ready)
+                                    const LatOrder *order, const LatReady *ready,
+                                    const unsigned long long *d_obj_masks)
 {
     const LatOrder O = order ? *order : LatOrder{};
     const LatReady R = ready ? *ready : LatReady{};
@@ -2147,10 +2289,10 @@ hipError_t launch_rt_lattice_frames(const RtFrame &F, const RtTri *d_tc, const R
     const int kt_id = F.n_lights == 1 ? KT_RT_LATTICE : KT_RT_LATTICE_LIGHTS;
     if (F.n_lights == 1 && lat_yaw(F))
         kt_launch(kt_id, rt_lattice_kernel<kLatWY>, grid, dim3(kRtThreads), 0, st, F, d_tc, d_shade, d_sph,
-                           d_lat_masks, cams, out_stride, d_out, d_done, O, R);
+                           d_lat_masks, cams, out_stride, d_out, d_done, O, R, d_obj_masks);
     else if (F.n_lights == 1)
         kt_launch(kt_id, rt_lattice_kernel<kLatW>, grid, dim3(kRtThreads), 0, st, F, d_tc, d_shade, d_sph, d_lat_masks,
-                           cams, out_stride, d_out, d_done, O, R);
+                           cams, out_stride, d_out, d_done, O, R, d_obj_masks);
     else if (lat_yaw(F))
         kt_launch(kt_id, rt_lattice_lights_kernel<kLatWY>, grid, dim3(kRtThreads), 0, st, F, d_tc, d_shade, d_sph,
                            d_lat_masks, d_umask, cams, out_stride, d_out, d_done);
@@ -2162,7 +2304,8 @@ hipError_t launch_rt_lattice_frames(const RtFrame &F, const RtTri *d_tc, const R
 
 hipError_t launch_rt_pixels(const RtFrame &F, const RtTri *d_tc, const RtShade *d_shade,
                             const RtSphere *d_sph, const unsigned long long *d_lat_masks,
-                            unsigned long long *d_umask, uint32_t *d_out, hipStream_t st)
+                            unsigned long long *d_umask, uint32_t *d_out, hipStream_t st,
+                            const unsigned long long *d_obj_masks)
 {
     dim3 grid((F.W + kRtTileW - 1) / kRtTileW, (F.rows_out + kRtTileH - 1) / kRtTileH);
     if (d_lat_masks && rt_use_lattice(F)) {
@@ -2171,7 +2314,7 @@ hipError_t launch_rt_pixels(const RtFrame &F, const RtTri *d_tc, const RtShade *
         hipError_t e = launch_rt_lattice_units(F, d_tc, d_shade, d_sph, d_lat_masks, cams, 1, d_umask, st);
         if (e != hipSuccess) return e;
         return launch_rt_lattice_frames(F, d_tc, d_shade, d_sph, d_lat_masks, d_umask, cams, 1, 0, d_out, st,
-                                        nullptr, nullptr, nullptr);
+                                        nullptr, nullptr, nullptr, d_obj_masks);
     }
     const int kt_id = KT_RT_PIXEL;
     if (F.n_tris <= 64 && F.cull_primary)

@@ -22,20 +22,21 @@
 namespace cg {
 hipError_t launch_rt_prepare(const cg_tri *, const RtGeo *, int, const RtFrameCams &, int, RtTri *, hipStream_t,
                              const RtFrame *, const RtSphere *, unsigned long long *, unsigned long long *,
-                             LatFlatten * = nullptr, LatPublish * = nullptr);
+                             LatFlatten * = nullptr, LatPublish * = nullptr, unsigned long long ** = nullptr);
 hipError_t launch_rt_scene(const cg_tri *, int, RtGeo *, RtShade *, hipStream_t);
 hipError_t rt_render_brute(const RtFrame &, const cg_tri *, int, const RtSphere *, int, int, uint32_t *, hipStream_t);
 size_t rt_sup_units(const RtFrame &);
 hipError_t launch_rt_lattice_frames(const RtFrame &, const RtTri *, const RtShade *, const RtSphere *,
                                     const unsigned long long *, const unsigned long long *, const RtFrameCams &,
                                     int, size_t, uint32_t *, hipStream_t, uint32_t *, const LatOrder *,
-                                    const LatReady * = nullptr);
+                                    const LatReady * = nullptr, const unsigned long long * = nullptr);
 hipError_t launch_rt_lattice_units(const RtFrame &, const RtTri *, const RtShade *, const RtSphere *,
                                    const unsigned long long *, const RtFrameCams &, int, unsigned long long *,
                                    hipStream_t);
 size_t rt_lattice_unit_bytes(const RtFrame &, int);
 hipError_t launch_rt_pixels(const RtFrame &, const RtTri *, const RtShade *, const RtSphere *,
-                            const unsigned long long *, unsigned long long *, uint32_t *, hipStream_t);
+                            const unsigned long long *, unsigned long long *, uint32_t *, hipStream_t,
+                            const unsigned long long * = nullptr);
 bool rt_use_lattice(const RtFrame &);
 int rt_lattice_kind(const RtFrame &);
 void rt_scene_box(const cg_tri *tris, int n_tris, const cg_sphere *spheres, int n_spheres, double lo[3],
@@ -191,6 +192,14 @@ struct cg_ctx {
     DevBuf latmask;                     // lattice tiles' certificates (two masks per tile)
     DevBuf supmask;                     // their super-tiles' certificates (two-level path)
     DevBuf umask;                       // light sets: the tiles' per-unit shadow masks
+    DevBuf objmask, pobj[2];            // one-light lattice: shadow masks per object (kObjSlots a tile), as latmask / plat
+    // the latest lattice call's certificates, for cg_rt_tile_masks (null: none since the scene changed)
+    struct {
+        const unsigned long long *lat = nullptr, *obj = nullptr;
+        int tiles_x = 0, tiles_y = 0, frames = 0;
+        int col0 = 0, col1 = 0;   // the tile columns the call certified (a windowed launch: its super-tiles')
+        hipStream_t st = nullptr;
+    } last_masks;
     // Batched lattice launches pipeline their certificate kernels on `aux`:
     // call j+1's certificates run beside call j's lattice kernel, each call
     // with its own slot of buffers (rt_enqueue_lattice_batch).
@@ -389,7 +398,7 @@ extern "C" void cg_destroy(cg_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     DevBuf *bufs[] = {&c->tris, &c->geo, &c->tc, &c->shade, &c->sph, &c->frame,
                       &c->probe_a, &c->probe_b, &c->probe_c, &c->probe_d, &c->lights, &c->big,
-                      &c->gstart, &c->gtris};
+                      &c->gstart, &c->gtris, &c->objmask};
     if (c->big_ev) {
         (void)hipEventSynchronize(c->big_ev);
         (void)hipEventDestroy(c->big_ev);
@@ -416,7 +425,7 @@ extern "C" void cg_destroy(cg_ctx *c)
     if (c->start_ev) (void)hipEventDestroy(c->start_ev);
     for (int k = 0; k < 2; ++k) {
         c->ptc[k].release(); c->plat[k].release(); c->pflag[k].release(); c->psup[k].release();
-        c->pumask[k].release();
+        c->pumask[k].release(); c->pobj[k].release();
         if (c->ev_cert[k]) (void)hipEventDestroy(c->ev_cert[k]);
         if (c->ev_lat[k]) (void)hipEventDestroy(c->ev_lat[k]);
     }
@@ -450,6 +459,7 @@ extern "C" int cg_rt_set_scene(cg_ctx *c, const cg_tri *tris, int n_tris, const 
     // scene buffers rewritten below (triangles, RtGeo, RtShade): let them finish
     CG_TRY(c, hipDeviceSynchronize(), "scene change");
     ++c->rt_scene_gen;
+    c->last_masks = {};   // certificates of the previous scene
     size_t nt = n_tris > 0 ? (size_t)n_tris : 1;
     CG_TRY(c, c->tris.ensure(nt * sizeof(cg_tri)), "alloc tris");
     CG_TRY(c, c->tc.ensure(nt * sizeof(RtTri)), "alloc tri constants");
@@ -711,6 +721,36 @@ extern "C" int cg_rt_scratch_info(cg_ctx *c, uint64_t *out)
     return CG_OK;
 }
 
+extern "C" int cg_rt_tile_masks(cg_ctx *c, int frame, uint64_t *masks, uint64_t *obj_masks, int *info)
+{
+    if (!c || !info) return CG_E_INVALID;
+    const auto &L = c->last_masks;
+    info[0] = L.tiles_x;
+    info[1] = L.tiles_y;
+    info[2] = L.obj ? kObjSlots : 0;
+    info[3] = L.frames;
+    if (!L.lat) return CG_E_INVALID;
+    if (!masks && !obj_masks) return CG_OK;
+    if (frame < 0 || frame >= L.frames) return CG_E_INVALID;
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    CG_TRY(c, hipStreamSynchronize(L.st), "tile masks");
+    const size_t tiles = (size_t)L.tiles_x * L.tiles_y;
+    if (masks)
+        CG_TRY(c, hipMemcpy(masks, L.lat + (size_t)frame * tiles * 2, tiles * 2 * sizeof(uint64_t), hipMemcpyDeviceToHost),
+               "tile masks");
+    if (obj_masks && L.obj)
+        CG_TRY(c, hipMemcpy(obj_masks, L.obj + (size_t)frame * tiles * kObjSlots, tiles * kObjSlots * sizeof(uint64_t),
+                            hipMemcpyDeviceToHost), "tile masks");
+    // tile columns outside a windowed launch are black without a certificate: report empty masks
+    for (size_t t = 0; t < tiles; ++t) {
+        const int tx = (int)(t % L.tiles_x);
+        if (tx >= L.col0 && tx < L.col1) continue;
+        if (masks) masks[2 * t] = masks[2 * t + 1] = 0;
+        if (obj_masks && L.obj) std::fill(obj_masks + t * kObjSlots, obj_masks + (t + 1) * kObjSlots, (uint64_t)0);
+    }
+    return CG_OK;
+}
+
 extern "C" int cg_rt_pool_demand(cg_ctx *c, uint64_t *out)
 {
     if (!c || !out) return CG_E_INVALID;
@@ -859,6 +899,17 @@ static int rt_big_enqueue(cg_ctx *c, const RtFrame &F, uint32_t *d_out, hipStrea
     return CG_OK;
 }
 
+static int lat_tiles_x_host(const RtFrame &F) { return (F.W + kLatTileW - 1) / kLatTileW; }
+
+// Shadow masks per object for the one-light lattice kernel (kObjSlots, cg_internal.h): each
+// 64-point chunk walks the masks of the objects its points hit instead of the tile's union mask.
+// CG_OBJ_MASKS=0 (A/B runs and the tests, read per call): the union mask, as before.
+static bool obj_masks_on(const RtFrame &F)
+{
+    const char *e = std::getenv("CG_OBJ_MASKS");
+    return !(e && e[0] == '0') && F.n_lights == 1 && F.cull_shadow;
+}
+
 static int rt_enqueue_kernels(cg_ctx *c, const RtFrame &F, uint32_t *d_out, hipStream_t st, int slot)
 {
     // a large scene's whole frame (prepare .. shading), for the bench's frame figures
@@ -870,7 +921,11 @@ static int rt_enqueue_kernels(cg_ctx *c, const RtFrame &F, uint32_t *d_out, hipS
     }
     RtFrameCams cams{};
     for (int k = 0; k < 4; ++k) cams.c[0][k] = F.cam[k];
-    unsigned long long *supm = nullptr, *um = nullptr;
+    unsigned long long *supm = nullptr, *um = nullptr, *obj = nullptr;
+    if (lat && obj_masks_on(F)) {
+        CG_TRY(c, c->objmask.ensure(rt_lattice_tiles(F) * kObjSlots * sizeof(unsigned long long)), "alloc object masks");
+        obj = (unsigned long long *)c->objmask.p;
+    }
     if (lat && rt_lattice_unit_bytes(F, 1)) {
         CG_TRY(c, c->umask.ensure(rt_lattice_unit_bytes(F, 1)), "alloc lattice unit masks");
         um = (unsigned long long *)c->umask.p;
@@ -887,9 +942,20 @@ static int rt_enqueue_kernels(cg_ctx *c, const RtFrame &F, uint32_t *d_out, hipS
     // large scenes: the super-bin pass forms the frame's RtTri itself (no prepare launch)
     if (F.n_tris > 64 && F.cull_primary && F.cull_shadow) return rt_big_enqueue(c, F, d_out, st, slot);
     CG_TRY(c, launch_rt_prepare((const cg_tri *)c->tris.p, (const RtGeo *)c->geo.p, c->n_tris, cams, 1,
-                                (RtTri *)S.tc->p, st, &F, (const RtSphere *)c->sph.p, lat, supm), "rt_prepare launch");
+                                (RtTri *)S.tc->p, st, &F, (const RtSphere *)c->sph.p, lat, supm, nullptr, nullptr, &obj),
+           "rt_prepare launch");
     CG_TRY(c, launch_rt_pixels(F, (const RtTri *)c->tc.p, (const RtShade *)c->shade.p,
-                               (const RtSphere *)c->sph.p, lat, um, d_out, st), "rt_pixel launch");
+                               (const RtSphere *)c->sph.p, lat, um, d_out, st, obj), "rt_pixel launch");
+    if (lat) {
+        c->last_masks.lat = lat;
+        c->last_masks.obj = obj;
+        c->last_masks.tiles_x = lat_tiles_x_host(F);
+        c->last_masks.tiles_y = (int)(rt_lattice_tiles(F) / lat_tiles_x_host(F));
+        c->last_masks.frames = 1;
+        c->last_masks.col0 = 0;
+        c->last_masks.col1 = lat_tiles_x_host(F);
+        c->last_masks.st = st;
+    }
     return CG_OK;
 }
 
@@ -908,7 +974,6 @@ extern "C" int cg_rt_render_device(cg_ctx *c, const cg_light *lights, int n_ligh
 
 // Frames f0 .. f0 + nf - 1 of a batch, one prepare + one lattice launch
 // (rt_use_lattice(F) holds for every frame; they differ only in cameraPos).
-static int lat_tiles_x_host(const RtFrame &F) { return (F.W + kLatTileW - 1) / kLatTileW; }
 
 // The launch geometry a lattice order is recorded for (0 never occurs): the
 // same key means the same tiles in the same window, so the recording predicts
@@ -1050,6 +1115,8 @@ static int rt_enqueue_lattice_batch(cg_ctx *c, const RtFrame &F0, const cg_rt_ca
         CG_TRY(c, c->plat[q].ensure(nfa * tiles * 2 * sizeof(unsigned long long)), "alloc lattice masks");
         CG_TRY(c, c->ptc[q].ensure(nfa * std::max(F.n_tris, 1) * sizeof(RtTri)), "alloc tri constants");
         CG_TRY(c, c->psup[q].ensure(nfa * rt_sup_units(F) * 2 * sizeof(unsigned long long)), "alloc super-tile masks");
+        if (obj_masks_on(F))
+            CG_TRY(c, c->pobj[q].ensure(nfa * tiles * kObjSlots * sizeof(unsigned long long)), "alloc object masks");
     }
     if (rt_lattice_unit_bytes(F, nf)) {
         c->umask_frames = std::max(c->umask_frames, nf);
@@ -1063,6 +1130,7 @@ static int rt_enqueue_lattice_batch(cg_ctx *c, const RtFrame &F0, const cg_rt_ca
     }
     unsigned long long *lat = (unsigned long long *)blat.p;
     unsigned long long *supm = (unsigned long long *)bsup.p;
+    unsigned long long *obj = obj_masks_on(F) ? (unsigned long long *)c->pobj[k].p : nullptr;
     // certificates on aux, after the slot's previous reader, so that they run
     // beside the lattice launch still queued before them.  A cold call (every
     // earlier lattice launch of this context complete: nothing to run beside)
@@ -1127,7 +1195,7 @@ static int rt_enqueue_lattice_batch(cg_ctx *c, const RtFrame &F0, const cg_rt_ca
     }
     CG_TRY(c, launch_rt_prepare((const cg_tri *)c->tris.p, (const RtGeo *)c->geo.p, c->n_tris, fc, nf,
                                 (RtTri *)btc.p, cst, &F, (const RtSphere *)c->sph.p, lat, supm,
-                                flat.n > 0 ? &flat : nullptr, conc ? &pub : nullptr),
+                                flat.n > 0 ? &flat : nullptr, conc ? &pub : nullptr, &obj),
            "rt_prepare launch");
     if (conc && !pub.done) ready = LatReady{};   // not published (the split certificate form): nothing to wait for
     if (ordered) {
@@ -1155,8 +1223,16 @@ static int rt_enqueue_lattice_batch(cg_ctx *c, const RtFrame &F0, const cg_rt_ca
     if (!cold && !conc) CG_TRY(c, hipStreamWaitEvent(st, c->ev_cert[k], 0), "aux wait");
     CG_TRY(c, launch_rt_lattice_frames(F, (const RtTri *)btc.p, (const RtShade *)c->shade.p,
                                        (const RtSphere *)c->sph.p, lat, um, fc, nf, stride, (uint32_t *)d_out, st,
-                                       d_done, ordered ? &order : nullptr, ready.flags ? &ready : nullptr),
+                                       d_done, ordered ? &order : nullptr, ready.flags ? &ready : nullptr, obj),
            "rt_lattice launch");
+    c->last_masks.lat = lat;
+    c->last_masks.obj = obj;
+    c->last_masks.tiles_x = lat_tiles_x_host(F);
+    c->last_masks.tiles_y = (int)(tiles / lat_tiles_x_host(F));
+    c->last_masks.frames = nf;
+    c->last_masks.col0 = F.txn ? F.tx0 / kSup * kSup : 0;
+    c->last_masks.col1 = F.txn ? std::min(lat_tiles_x_host(F), (F.tx0 + F.txn + kSup - 1) / kSup * kSup) : lat_tiles_x_host(F);
+    c->last_masks.st = st;
     // published: whatever the caller queues after this call follows the certificates too
     if (conc) CG_TRY(c, hipStreamWaitEvent(st, c->ev_cert[k], 0), "aux wait");
     CG_TRY(c, hipEventRecord(c->ev_lat[k], st), "aux record");

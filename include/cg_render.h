@@ -248,6 +248,17 @@ int cg_rt_scratch_info(cg_ctx *ctx, uint64_t *out);
  * super-bin lists, out[1] bin lists, out[2] many-light shadow lists, out[3]
  * bucketed (per half-bin) lists, in entries. */
 int cg_rt_pool_demand(cg_ctx *ctx, uint64_t *out);
+/* Diagnostic: the lattice tile certificates of frame `frame` of the latest
+ * lattice call on this context (waits for it).  info[0..3] = tile columns,
+ * tile rows, shadow masks per object a tile holds (0: none were built) and
+ * the call's frames.  masks (optional): two 64-bit words per tile, row-major
+ * -- the primary mask (bit k: triangle k may be hit; bit 63: a sphere; bit
+ * 62: the one candidate covers the tile) and the shadow mask (bit k: triangle
+ * k may block a shadow ray of the tile; bit 63: a sphere).  obj_masks
+ * (optional): info[2] words per tile -- word j < info[2] - 1 the shadow mask
+ * for hits on the j-th set triangle of the primary mask, the last word for
+ * hits on a sphere.  With both null only info is filled. */
+int cg_rt_tile_masks(cg_ctx *ctx, int frame, uint64_t *masks, uint64_t *obj_masks, int *info);
 /* Test hook: pin the large-scene pool capacities (entries: super-bin, bin,
  * many-light shadow and bucketed lists; all 0 = automatic sizing).  Lists past a capacity take the fallback over every triangle; the
  * image is the same. */
