@@ -76,6 +76,11 @@ class Stats(C.Structure):
                 ("n_spans", C.c_int), ("n_shaded", C.c_longlong)]
 
 
+class RastSeqFrame(C.Structure):   # cg_rast_seq_frame: one record of a frame sequence's d_info
+    _fields_ = [("rand_offset", C.c_uint64), ("n_shaded", C.c_int64), ("status", C.c_int32), ("pad", C.c_int32)]
+
+
+assert C.sizeof(RastSeqFrame) == 24
 assert C.sizeof(Tri) == 76 and C.sizeof(Sphere) == 44 and C.sizeof(Light) == 28
 assert C.sizeof(Isect) == 28 and C.sizeof(RTri) == 84
 
@@ -143,6 +148,9 @@ _SIGS = {
     "cg_rast_draw": (C.c_int, [P, C.POINTER(RastParams), P, P, P, C.POINTER(Stats)]),
     "cg_rast_draw_device": (C.c_int, [P, C.POINTER(RastParams), P, P, P, P]),
     "cg_rast_draw_frames_device": (C.c_int, [P, C.POINTER(RastParams), C.c_int, P, P, P, C.c_size_t, P]),
+    "cg_rast_draw_sequence_device": (C.c_int, [P, C.POINTER(RastParams), C.c_int, P, P, P, C.c_size_t, P, P]),
+    "cg_rast_set_rand_capacity": (C.c_int, [P, C.c_longlong]),
+    "cg_glibc_rand_device": (C.c_int, [P, P, C.c_int, P, P]),
     "cg_dist_unique_id": (C.c_int, [P]),
     "cg_dist_create": (C.c_int, [P, C.c_int, C.c_int, P, C.POINTER(P)]),
     "cg_dist_create_timed": (C.c_int, [P, C.c_int, C.c_int, P, C.c_int, C.POINTER(P)]),
@@ -760,6 +768,27 @@ class Context:
             self.h, arr, len(params_list), P(d_argb), P(d_depth) if d_depth else None,
             P(d_shadow) if d_shadow else None, frame_stride, P(stream) if stream else None),
             "cg_rast_draw_frames_device")
+
+    def rast_draw_sequence_device(self, params_list, d_argb, d_depth=None, d_shadow=None, frame_stride=0,
+                                  d_info=None, stream=None):
+        """len(params_list) successive Draws in any mix of colour modes 0-2, enqueued on `stream`
+        in order; the rand() call index starts at params_list[0].rand_offset and is chained on the
+        device.  d_info: device memory for len(params_list) + 1 RastSeqFrame records (24 B each)."""
+        arr = (RastParams * max(len(params_list), 1))(*params_list)
+        self._check(self.lib.cg_rast_draw_sequence_device(
+            self.h, arr, len(params_list), P(d_argb), P(d_depth) if d_depth else None,
+            P(d_shadow) if d_shadow else None, frame_stride, P(d_info) if d_info else None,
+            P(stream) if stream else None), "cg_rast_draw_sequence_device")
+
+    def rast_set_rand_capacity(self, n):
+        """Test hook: fragments the sequence's materialised rand() stream holds (0 = 4 * W * H)."""
+        self._check(self.lib.cg_rast_set_rand_capacity(self.h, n), "cg_rast_set_rand_capacity")
+
+    def glibc_rand_device(self, d_offset, n, d_out, stream=None):
+        """cg_glibc_rand_device: n values of rand() into d_out (int32, device), from the uint64
+        call index at d_offset (device), by the sequence's device seek and generator."""
+        self._check(self.lib.cg_glibc_rand_device(self.h, P(d_offset), n, P(d_out), P(stream) if stream else None),
+                    "cg_glibc_rand_device")
 
     def rast_render_device(self, d_tris, n, params, light, d_argb, d_depth=None, d_shadow=None,
                            stream=None):

@@ -594,7 +594,8 @@ __device__ __forceinline__ float darken_at(const T *sh, int ld, int cy, int cx)
 // itself and its up/left neighbours are seen darkened, down/right not (a
 // darkening of 0 subtracts exactly nothing).  DIRECT (colour modes 1-2): the
 // state is the colour fill's float4 (cg_rast_colour.hip) instead of the fill's
-// record word, and the shadow marks come from the shadow plane.
+// record word, and the shadow marks come from the shadow plane; skip (may be
+// null): a sequence frame's status word, non-zero = the frame is not drawn.
 constexpr int kPostTW = 64, kPostTH = 8;
 constexpr int kPostHW = kPostTW + 2, kPostHH = kPostTH + 2;      // shade halo 1
 constexpr int kPostSW = kPostTW + 4, kPostSH = kPostTH + 4;      // shadow halo 2
@@ -604,8 +605,10 @@ __global__ __launch_bounds__(256) void rast_post_kernel(const cg_rtri *__restric
                                                        const void *__restrict__ state_v,
                                                        const RowRec *__restrict__ recs,
                                                        const int32_t *__restrict__ sh,
-                                                       uint32_t *__restrict__ argb)
+                                                       uint32_t *__restrict__ argb,
+                                                       const int32_t *__restrict__ skip)
 {
+    if (DIRECT && skip && *skip != 0) return;             // sequence frame over the capacity: plane untouched
     RastArgs A = A0;
     if (!DIRECT && A.d_light) {                           // light from the device geometry (:223)
         const cg_vec4 L = *A.d_light;
@@ -781,6 +784,10 @@ __global__ __launch_bounds__(256) void rast_post_kernel(const cg_rtri *__restric
 int rast_colour_fill(cg_ctx *c, const RastArgs &A, const cg_rast_params *p, const RowRec *recs, const int *count,
                      const RastHdr *hdr, const int *n_dev, int max_recs, float4 *state, float *d_depth,
                      int32_t *shadow, hipStream_t st, long long *n_shaded);
+int rast_seq_colour_fill(cg_ctx *c, const RastArgs &A, const cg_rast_params *p, const RowRec *recs, const int *count,
+                         const RastHdr *hdr, const int *n_dev, int max_recs, float4 *state, float *d_depth,
+                         int32_t *shadow, hipStream_t st, const RastSeq &q);
+int rast_seq_chain_mode0(cg_ctx *c, hipStream_t st, const RastSeq &q);
 
 hipError_t launch_rast_clip(const cg_rast_params &prm, const cg_rtri *d_room, int n_room, const cg_rtri *d_boxes,
                             int n_boxes, cg_rtri *d_stage, int *d_counts, cg_vec4 *d_light, int *d_first,
@@ -798,7 +805,7 @@ struct RastStage {
 static int rast_pipeline(cg_ctx *c, cg_rtri *d_tris, int n, int *n_dev, const cg_rast_params *p,
                          cg_vec4 light, const cg_vec4 *d_light, uint32_t *d_argb, float *d_depth,
                          int32_t *d_shadow, hipStream_t st, cg_stats *stats, bool events_open, int tex_mask,
-                         RastStage sg);
+                         RastStage sg, const RastSeq *seq = nullptr);
 int rast_tex_maps(cg_ctx *c, RastTexMaps *m);
 
 // glm::inverse for mat4 (glm/detail/type_mat4x4.inl:37-90), column-major
@@ -846,10 +853,11 @@ int rast_render_device(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_pa
 }
 
 // Whole rasteriser Draw on the device: geometry (shadow volumes + clip) then
-// fill + post.  room/boxes are device pointers (cg_rast_set_scene).
+// fill + post.  room/boxes are device pointers (cg_rast_set_scene).  seq: the
+// frame belongs to a sequence (cg_rast_draw_sequence_device).
 int rast_draw_device(cg_ctx *c, const cg_rtri *d_room, int n_room, const cg_rtri *d_boxes, int n_boxes,
                      const cg_rast_params *p, uint32_t *d_argb, float *d_depth, int32_t *d_shadow,
-                     hipStream_t st, cg_stats *stats, int **n_out, int tex_mask)
+                     hipStream_t st, cg_stats *stats, int **n_out, int tex_mask, const RastSeq *seq)
 {
     if (p->width <= 2 || p->height <= 2 || p->height > kRastMaxRows || p->focal == 0.0f) return CG_E_INVALID;
     const int n_in = n_room + 7 * n_boxes;
@@ -871,13 +879,13 @@ int rast_draw_device(cg_ctx *c, const cg_rtri *d_room, int n_room, const cg_rtri
         return ctx_fail(c, e, "rast_clip launch");
     if (n_out) *n_out = geo;
     return rast_pipeline(c, tris, cap, geo, p, cg_vec4{0, 0, 0, 1}, (const cg_vec4 *)(geo + 4), d_argb, d_depth,
-                         d_shadow, st, stats, true, tex_mask, RastStage{tris + cap, geo + 16, n_in});
+                         d_shadow, st, stats, true, tex_mask, RastStage{tris + cap, geo + 16, n_in}, seq);
 }
 
 static int rast_pipeline(cg_ctx *c, cg_rtri *d_tris, int n, int *n_dev, const cg_rast_params *p,
                          cg_vec4 light, const cg_vec4 *d_light, uint32_t *d_argb, float *d_depth,
                          int32_t *d_shadow, hipStream_t st, cg_stats *stats, bool events_open, int tex_mask,
-                         RastStage sg)
+                         RastStage sg, const RastSeq *seq)
 {
     if (p->width <= 2 || p->height <= 2 || p->height > kRastMaxRows) return CG_E_INVALID;
     const int W = p->width, H = p->height;
@@ -942,12 +950,16 @@ static int rast_pipeline(cg_ctx *c, cg_rtri *d_tris, int n, int *n_dev, const cg
     if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "rast_rows launch");
     const int post_grid = xcd_grid(H, (W + kPostTW - 1) / kPostTW);
     if (p->colour_mode != 0) {
-        long long ns = 0;
-        const int rc = rast_colour_fill(c, A, p, recs, count, hdr, n_dev, nn, (float4 *)state, d_depth, shadow, st, &ns);
+        long long ns = -1;
+        const int rc = seq ? rast_seq_colour_fill(c, A, p, recs, count, hdr, n_dev, nn, (float4 *)state, d_depth,
+                                                  shadow, st, *seq)
+                           : rast_colour_fill(c, A, p, recs, count, hdr, n_dev, nn, (float4 *)state, d_depth, shadow,
+                                              st, &ns);
         if (rc) return rc;
         if (stats) stats->n_shaded = ns;
         hipLaunchKernelGGL((rast_post_kernel<true, false>), dim3(post_grid), dim3(256), 0, st, d_tris, A,
-                           (const void *)state, (const RowRec *)recs, shadow, d_argb);
+                           (const void *)state, (const RowRec *)recs, shadow, d_argb,
+                           seq ? (const int32_t *)&seq->info->status : (const int32_t *)nullptr);
     } else {
         const int fgrid = xcd_grid(H, ((W + kFillPx - 1) / kFillPx * kXcdRows + 3) / 4);
         {
@@ -962,11 +974,17 @@ static int rast_pipeline(cg_ctx *c, cg_rtri *d_tris, int n, int *n_dev, const cg
         const int kt_id = KT_RAST_POST;
         if (A.textured)
             kt_launch(kt_id, (rast_post_kernel<false, true>), dim3(post_grid), dim3(256), 0, st, d_tris, A,
-                               (const void *)state, (const RowRec *)recs, (const int32_t *)nullptr, d_argb);
+                               (const void *)state, (const RowRec *)recs, (const int32_t *)nullptr, d_argb,
+                               (const int32_t *)nullptr);
         else
             kt_launch(kt_id, (rast_post_kernel<false, false>), dim3(post_grid), dim3(256), 0, st, d_tris, A,
-                               (const void *)state, (const RowRec *)recs, (const int32_t *)nullptr, d_argb);
+                               (const void *)state, (const RowRec *)recs, (const int32_t *)nullptr, d_argb,
+                               (const int32_t *)nullptr);
         if (stats) stats->n_shaded = -1;
+        if (seq) {
+            const int rc = rast_seq_chain_mode0(c, st, *seq);
+            if (rc) return rc;
+        }
     }
     if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "rast_post launch");
     if (stats && (e = hipEventRecord(e1, st)) != hipSuccess) return ctx_fail(c, e, "event");

@@ -14,6 +14,16 @@
 //                          (base of its (triangle, row) + rank in the row), the
 //                          last one per pixel shaded with its three values.
 // The post-pass is shared with colour mode 0 (kStateDirect state).
+//
+// A frame sequence (cg_rast_draw_sequence_device) chains the call index on the
+// device instead of on the host, with nothing read back:
+//   rast_seq_chain_kernel  frame f's record {offset_f, S_f, status_f} and
+//                          offset_{f+1} = offset_f + 3 S_f;
+//   rast_seq_seek_kernel   the 61-word window at offset_f: x^(offset_f + 341)
+//                          mod P by square-and-multiply in one wave;
+//   rast_rand_dev_kernel   rast_rand_kernel with the window and the length
+//                          read from device memory, launched over the chunks
+//                          of the stream's capacity.
 #include <vector>
 
 #include "cg_glibc_rand.h"
@@ -156,21 +166,20 @@ struct RandWindow {
     uint32_t w[61];
 };
 
-// Thread b produces values [b C, (b + 1) C) of the frame's stream: its window
+// Values [b C, (b + 1) C) of a stream whose window is w: the chunk's window
 // r[idx + b C + j] = sum_i J_b[i] w[i + j] (J_b = x^(b C) mod P), then the
 // recurrence r[i] = r[i - 31] + r[i - 3], 31 values per round in registers.
-__global__ __launch_bounds__(256) void rast_rand_kernel(RandWindow W, const uint32_t *__restrict__ jt, int nb,
-                                                      long long nvals, int32_t *__restrict__ out)
+template <class Win>   // the 61 window words, indexable
+__device__ __forceinline__ void rand_chunk(const Win &w, const uint32_t *__restrict__ jt, int b, long long nvals,
+                                           int32_t *__restrict__ out)
 {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= nb) return;
     uint32_t o[kRandDeg];
 #pragma unroll
     for (int j = 0; j < kRandDeg; ++j) o[j] = 0u;
     for (int i = 0; i < kRandDeg; ++i) {
         const uint32_t c = jt[(size_t)b * kRandDeg + i];
 #pragma unroll
-        for (int j = 0; j < kRandDeg; ++j) o[j] += c * W.w[i + j];
+        for (int j = 0; j < kRandDeg; ++j) o[j] += c * w[i + j];
     }
     const long long p0 = (long long)b * kRandChunk;
     for (int m0 = 0; m0 < kRandChunk; m0 += kRandDeg) {
@@ -183,6 +192,126 @@ __global__ __launch_bounds__(256) void rast_rand_kernel(RandWindow W, const uint
 #pragma unroll
         for (int j = 0; j < kRandDeg; ++j) o[j] = nn[j];
     }
+}
+
+// Thread b produces values [b C, (b + 1) C) of the frame's stream.
+__global__ __launch_bounds__(256) void rast_rand_kernel(RandWindow W, const uint32_t *__restrict__ jt, int nb,
+                                                      long long nvals, int32_t *__restrict__ out)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= nb) return;
+    rand_chunk(W.w, jt, b, nvals, out);
+}
+
+// ---- frame sequences: the chain, the seek and the generator on the device ----
+
+// Word offsets in the context's generator tables (rast_seq_tables): the
+// sequence's window, the probe's window (cg_glibc_rand_device), the seed-1
+// state words r[3 .. 94], then J_b for every chunk of the capacity.
+constexpr int kSeqWin = 0, kSeqProbeWin = 64, kSeqSeed = 128, kSeqJump = 224;
+
+// Frame f's record and the next frame's start: info[0] = {offset_f, S_f,
+// status_f}, info[1] = {offset_f + 3 S_f, -1, 0} (the closing record after the
+// last frame).  offset_f is `start` for the call's first frame, else what the
+// previous frame's step left in info[0].  mode 0: no fragments draw, S = -1.
+__global__ __launch_bounds__(64) void rast_seq_chain_kernel(const long long *__restrict__ total,
+                                                          cg_rast_seq_frame *info, int first,
+                                                          unsigned long long start, long long cap, int mode)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const unsigned long long off = first ? start : (unsigned long long)info[0].rand_offset;
+    const long long S = mode != 0 ? total[0] : -1;
+    cg_rast_seq_frame cur, next;
+    cur.rand_offset = off;
+    cur.n_shaded = S;
+    cur.status = S > cap ? CG_E_CAPACITY : 0;
+    cur.pad = 0;
+    next.rand_offset = off + (S > 0 ? 3ull * (unsigned long long)S : 0ull);
+    next.n_shaded = -1;
+    next.status = 0;
+    next.pad = 0;
+    info[0] = cur;
+    info[1] = next;
+}
+
+// c = a b mod P in one wave: lane i holds coefficient i (lanes >= 31 hold 0).
+// s_b is b at [31, 62) between zeros, so lane k sums a_i b_(k - i) over every
+// i without a bounds test; the 61-term product goes to s_t (zeros above it)
+// and x^k = x^(k - 3) + x^(k - 31), k = 60 .. 31, folds to
+//   c_i = t_i + h'_i + (i >= 28 ? h'_(i - 28) : 0),  h'_m = sum_r t_(31 + m + 3 r)
+// (rand_poly_mulmod's loop, summed per coefficient).
+__device__ __forceinline__ uint32_t rand_poly_mulmod_wave(uint32_t a, uint32_t b, uint32_t *s_b, uint32_t *s_t,
+                                                          int lane)
+{
+    __syncthreads();
+    s_b[kRandDeg + lane] = b;
+    __syncthreads();
+    uint32_t t = 0u;
+#pragma unroll
+    for (int i = 0; i < kRandDeg; ++i)
+        t += (uint32_t)__builtin_amdgcn_readlane((int)a, i) * s_b[kRandDeg + lane - i];
+    s_t[lane] = t;                                        // lanes 61-63: 0
+    __syncthreads();
+    uint32_t h = 0u;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) h += s_t[kRandDeg + lane + 3 * r];
+    const uint32_t h0 = (uint32_t)__builtin_amdgcn_readlane((int)h, 0), h1 = (uint32_t)__builtin_amdgcn_readlane((int)h, 1),
+                   h2 = (uint32_t)__builtin_amdgcn_readlane((int)h, 2);
+    const uint32_t c = t + h + (lane == 28 ? h0 : lane == 29 ? h1 : lane == 30 ? h2 : 0u);
+    return lane < kRandDeg ? c : 0u;
+}
+
+// The 61 state words at call index *d_off (rand_window on the device): one
+// wave, x^(k + 341) mod P by square-and-multiply (rand_poly_xpow), applied to
+// seed[j] = r[3 + j], j < 92.  skip: the frame's status (non-zero: nothing to do).
+__global__ __launch_bounds__(64) void rast_seq_seek_kernel(const unsigned long long *__restrict__ d_off,
+                                                         const int32_t *__restrict__ skip,
+                                                         const uint32_t *__restrict__ seed,
+                                                         uint32_t *__restrict__ win)
+{
+    __shared__ uint32_t s_b[128], s_t[128];
+    const int lane = threadIdx.x;
+    if (skip && *skip != 0) return;
+    s_b[lane] = 0u; s_b[64 + lane] = 0u;
+    s_t[lane] = 0u; s_t[64 + lane] = 0u;
+    const unsigned long long k = *d_off + 344ull - 3ull;
+    uint32_t elo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)k);
+    uint32_t ehi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(k >> 32));
+    uint32_t res = lane == 0 ? 1u : 0u, base = lane == 1 ? 1u : 0u;
+    while (elo | ehi) {
+        if (elo & 1u) res = rand_poly_mulmod_wave(res, base, s_b, s_t, lane);
+        elo = (elo >> 1) | (ehi << 31);
+        ehi >>= 1;
+        if (elo | ehi) base = rand_poly_mulmod_wave(base, base, s_b, s_t, lane);
+    }
+    uint32_t v = 0u;
+#pragma unroll
+    for (int i = 0; i < kRandDeg; ++i) {
+        const int j = i + lane < 92 ? i + lane : 91;
+        v += (uint32_t)__builtin_amdgcn_readlane((int)res, i) * seed[j];
+    }
+    if (lane < 61) win[lane] = v;
+}
+
+// rast_rand_kernel with the window and the stream's length in device memory:
+// launched over the nb_cap chunks of the capacity, chunks past the length exit
+// at once.  info: the frame's record (3 n_shaded values; a non-zero status
+// generates nothing); null: nfixed values (the probe).
+__global__ __launch_bounds__(256) void rast_rand_dev_kernel(const uint32_t *__restrict__ win,
+                                                          const cg_rast_seq_frame *__restrict__ info,
+                                                          long long nfixed, const uint32_t *__restrict__ jt,
+                                                          int nb_cap, int32_t *__restrict__ out)
+{
+    __shared__ uint32_t s_w[64];                          // every thread reads the same word: LDS broadcasts
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (info && info->status != 0) return;
+    const long long nvals = info ? 3 * info->n_shaded : nfixed;
+    if ((long long)blockIdx.x * blockDim.x * kRandChunk >= nvals) return;   // the whole workgroup
+    if (threadIdx.x < 61) s_w[threadIdx.x] = win[threadIdx.x];
+    __syncthreads();
+    if (b >= nb_cap || (long long)b * kRandChunk >= nvals) return;
+    const uint32_t *w = s_w;
+    rand_chunk(w, jt, b, nvals, out);
 }
 
 // LO + rand() / (RAND_MAX/HI - LO), all float (skeleton.cpp:563-565, :649-651)
@@ -198,12 +327,14 @@ __global__ __launch_bounds__(64) void rast_fill_rand_kernel(RastArgs A0, const R
                                                           const long long *__restrict__ tbase,
                                                           const int32_t *__restrict__ rnd, int mode,
                                                           float4 *__restrict__ state, float *__restrict__ depth_out,
-                                                          int32_t *__restrict__ shadow_out)
+                                                          int32_t *__restrict__ shadow_out,
+                                                          const cg_rast_seq_frame *__restrict__ info)
 {
     extern __shared__ long long s_run[];                  // next fragment number per record
     const RastArgs A = with_device_light(A0);
     const int y = blockIdx.x, lane = threadIdx.x;
     if (y >= A.H) return;
+    if (info && info->status != 0) return;                // sequence frame over the capacity: planes untouched
     const int cnt = count[y];
     const RowRec *rr = recs + (size_t)y * A.n;
     const unsigned long long lt = (1ull << lane) - 1ull;
@@ -271,6 +402,24 @@ __global__ __launch_bounds__(64) void rast_fill_rand_kernel(RastArgs A0, const R
     }
 }
 
+// J_b = x^(b C) mod P for b < nb, grown once per process as callers need more
+static const std::vector<uint32_t> &rand_jump_table(long long nb)
+{
+    static std::vector<uint32_t> jtab;
+    static uint32_t step[kRandDeg];
+    if (jtab.empty()) {
+        rand_poly_xpow(kRandChunk, step);
+        jtab.assign(kRandDeg, 0u);
+        jtab[0] = 1u;
+    }
+    while ((long long)(jtab.size() / kRandDeg) < nb) {
+        uint32_t next[kRandDeg];
+        rand_poly_mulmod(&jtab[jtab.size() - kRandDeg], step, next);
+        jtab.insert(jtab.end(), next, next + kRandDeg);
+    }
+    return jtab;
+}
+
 // Host side of colour modes 1-2, between rast_rows_kernel and the post-pass.
 // Synchronises once (the stream's length S decides the generator's size).
 int rast_colour_fill(cg_ctx *c, const RastArgs &A, const cg_rast_params *p, const RowRec *recs, const int *count,
@@ -301,19 +450,7 @@ int rast_colour_fill(cg_ctx *c, const RastArgs &A, const cg_rast_params *p, cons
     int32_t *rnd = (int32_t *)ctx_buf(c, 12, (size_t)(nvals > 0 ? nvals : 1) * sizeof(int32_t), &e);
     if (!rnd) return ctx_fail(c, e, "alloc rand stream");
     if (nb > 0) {
-        // J_b = x^(b C) mod P, grown once per process as frames need more
-        static std::vector<uint32_t> jtab;
-        static uint32_t step[kRandDeg];
-        if (jtab.empty()) {
-            rand_poly_xpow(kRandChunk, step);
-            jtab.assign(kRandDeg, 0u);
-            jtab[0] = 1u;
-        }
-        while ((int)(jtab.size() / kRandDeg) < nb) {
-            uint32_t next[kRandDeg];
-            rand_poly_mulmod(&jtab[jtab.size() - kRandDeg], step, next);
-            jtab.insert(jtab.end(), next, next + kRandDeg);
-        }
+        const std::vector<uint32_t> &jtab = rand_jump_table(nb);
         uint32_t *jt = (uint32_t *)ctx_buf(c, 13, (size_t)nb * kRandDeg * sizeof(uint32_t), &e);
         if (!jt) return ctx_fail(c, e, "alloc jump table");
         if ((e = hipMemcpyAsync(jt, jtab.data(), (size_t)nb * kRandDeg * sizeof(uint32_t), hipMemcpyHostToDevice, st)) !=
@@ -324,12 +461,104 @@ int rast_colour_fill(cg_ctx *c, const RastArgs &A, const cg_rast_params *p, cons
         hipLaunchKernelGGL(rast_rand_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, W, jt, nb, nvals, rnd);
     }
     hipLaunchKernelGGL(rast_fill_rand_kernel, dim3(H), dim3(64), (size_t)(max_recs > 0 ? max_recs : 1) * 8, st, A,
-                       recs, count, pc, tbase, rnd, p->colour_mode, state, d_depth, shadow);
+                       recs, count, pc, tbase, rnd, p->colour_mode, state, d_depth, shadow,
+                       (const cg_rast_seq_frame *)nullptr);
     if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "colour fill launch");
     // the jump table upload reads host memory: keep it alive until the copy ran
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return ctx_fail(c, e, "colour fill");
     return CG_OK;
 }
+
+// The context's generator tables with J_b for nb chunks (kSeqWin ..): built
+// and uploaded when a call needs more chunks than *have holds (first use of a
+// capacity; synchronous), untouched otherwise.
+int rast_seq_tables(cg_ctx *c, long long nb, long long *have, uint32_t **tables)
+{
+    hipError_t e;
+    const size_t words = (size_t)kSeqJump + (size_t)(nb > *have ? nb : *have) * kRandDeg;
+    uint32_t *t = (uint32_t *)ctx_buf(c, 18, words * sizeof(uint32_t), &e);
+    if (!t) return ctx_fail(c, e, "alloc generator tables");
+    *tables = t;
+    if (nb <= *have) return CG_OK;
+    *have = 0;
+    const std::vector<uint32_t> &jtab = rand_jump_table(nb);
+    const std::vector<uint32_t> r = rand_state_prefix(3 + 92);
+    if ((e = hipMemcpy(t + kSeqSeed, r.data() + 3, 92 * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy(t + kSeqJump, jtab.data(), (size_t)nb * kRandDeg * sizeof(uint32_t), hipMemcpyHostToDevice)) !=
+            hipSuccess)
+        return ctx_fail(c, e, "upload generator tables");
+    *have = nb;
+    return CG_OK;
+}
+
+// Colour modes 1-2 of a sequence frame, between rast_rows_kernel and the
+// post-pass: rast_colour_fill with the chain, the seek and the generator's
+// length on the device.  Enqueues only.
+int rast_seq_colour_fill(cg_ctx *c, const RastArgs &A, const cg_rast_params *p, const RowRec *recs, const int *count,
+                         const RastHdr *hdr, const int *n_dev, int max_recs, float4 *state, float *d_depth,
+                         int32_t *shadow, hipStream_t st, const RastSeq &q)
+{
+    hipError_t e;
+    const int n = A.n > 0 ? A.n : 1, H = A.H;
+    int *pc = (int *)ctx_buf(c, 10, (size_t)n * H * sizeof(int), &e);
+    if (!pc) return ctx_fail(c, e, "alloc pass counts");
+    long long *tl = (long long *)ctx_buf(c, 11, (2 * (size_t)n + 2) * sizeof(long long), &e);
+    if (!tl) return ctx_fail(c, e, "alloc triangle counts");
+    int32_t *rnd = (int32_t *)ctx_buf(c, 12, 3 * (size_t)(q.cap > 0 ? q.cap : 1) * sizeof(int32_t), &e);
+    if (!rnd) return ctx_fail(c, e, "alloc rand stream");
+    long long *tot = tl, *tbase = tl + n, *total = tl + 2 * n;
+    if ((e = hipMemsetAsync(pc, 0, (size_t)n * H * sizeof(int), st)) != hipSuccess) return ctx_fail(c, e, "memset");
+    const size_t lds_cnt = (size_t)(max_recs > 0 ? max_recs : 1) * sizeof(int);
+    hipLaunchKernelGGL(rast_count_kernel, dim3(H), dim3(64), lds_cnt, st, A, recs, count, pc);
+    hipLaunchKernelGGL(rast_scan_rows_kernel, dim3(n < 1024 ? n : 1024), dim3(256), 0, st, hdr, n_dev, A.n, H, pc,
+                       tot);
+    hipLaunchKernelGGL(rast_scan_tris_kernel, dim3(1), dim3(256), 0, st, tot, n_dev, A.n, tbase, total);
+    // everything above is offset-independent; from here on the frame follows its predecessor
+    uint32_t *win = q.win ? q.win : q.tables + kSeqWin;
+    if (q.wait_ev && (e = hipStreamWaitEvent(st, q.wait_ev, 0)) != hipSuccess) return ctx_fail(c, e, "chain wait");
+    hipLaunchKernelGGL(rast_seq_chain_kernel, dim3(1), dim3(64), 0, st, (const long long *)total, q.info, q.first,
+                       (unsigned long long)q.start, q.cap, 1);
+    if (q.done_ev && (e = hipEventRecord(q.done_ev, st)) != hipSuccess) return ctx_fail(c, e, "chain event");
+    hipLaunchKernelGGL(rast_seq_seek_kernel, dim3(1), dim3(64), 0, st,
+                       (const unsigned long long *)&q.info->rand_offset, (const int32_t *)&q.info->status,
+                       (const uint32_t *)(q.tables + kSeqSeed), win);
+    if (q.nb_cap > 0)
+        hipLaunchKernelGGL(rast_rand_dev_kernel, dim3((q.nb_cap + 255) / 256), dim3(256), 0, st,
+                           (const uint32_t *)win, (const cg_rast_seq_frame *)q.info, 0ll,
+                           (const uint32_t *)(q.tables + kSeqJump), q.nb_cap, rnd);
+    hipLaunchKernelGGL(rast_fill_rand_kernel, dim3(H), dim3(64), (size_t)(max_recs > 0 ? max_recs : 1) * 8, st, A,
+                       recs, count, pc, tbase, rnd, p->colour_mode, state, d_depth, shadow,
+                       (const cg_rast_seq_frame *)q.info);
+    if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "sequence colour fill launch");
+    return CG_OK;
+}
+
+// A colour mode 0 frame of a sequence: its record, the offset passed on unchanged.
+int rast_seq_chain_mode0(cg_ctx *c, hipStream_t st, const RastSeq &q)
+{
+    hipError_t e;
+    if (q.wait_ev && (e = hipStreamWaitEvent(st, q.wait_ev, 0)) != hipSuccess) return ctx_fail(c, e, "chain wait");
+    hipLaunchKernelGGL(rast_seq_chain_kernel, dim3(1), dim3(64), 0, st, (const long long *)nullptr, q.info, q.first,
+                       (unsigned long long)q.start, q.cap, 0);
+    if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "sequence chain launch");
+    if (q.done_ev && (e = hipEventRecord(q.done_ev, st)) != hipSuccess) return ctx_fail(c, e, "chain event");
+    return CG_OK;
+}
+
+// cg_glibc_rand_device: n values from the call index at d_off, by the seek and
+// the generator of the sequence (their own window slot).
+int rast_rand_probe(cg_ctx *c, uint32_t *tables, int nb, const uint64_t *d_off, int n, int32_t *d_out, hipStream_t st)
+{
+    hipLaunchKernelGGL(rast_seq_seek_kernel, dim3(1), dim3(64), 0, st, (const unsigned long long *)d_off,
+                       (const int32_t *)nullptr, (const uint32_t *)(tables + kSeqSeed), tables + kSeqProbeWin);
+    hipLaunchKernelGGL(rast_rand_dev_kernel, dim3((nb + 255) / 256), dim3(256), 0, st,
+                       (const uint32_t *)(tables + kSeqProbeWin), (const cg_rast_seq_frame *)nullptr, (long long)n,
+                       (const uint32_t *)(tables + kSeqJump), nb, d_out);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? ctx_fail(c, e, "rand probe launch") : CG_OK;
+}
+
+long long rast_rand_chunks(long long nvals) { return (nvals + kRandChunk - 1) / kRandChunk; }
 
 }  // namespace cg
 

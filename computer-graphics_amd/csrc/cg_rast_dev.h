@@ -47,6 +47,22 @@ struct RastHdr {
     int tex, index, pad;    // texture, object index
 };
 
+// One frame of cg_rast_draw_sequence_device as the pipeline sees it: where the
+// frame's record lives, where the rand() call index comes from, and the
+// generator's capacity and tables (cg_rast_colour.hip).
+struct RastSeq {
+    cg_rast_seq_frame *info;   // d_info + f; info[1] receives the next frame's start
+    int first;                 // the call's first frame: it starts at `start`, not at info[0].rand_offset
+    uint64_t start;
+    long long cap;             // fragments the materialised stream holds
+    uint32_t *tables;          // the context's generator tables for nb_cap chunks
+    int nb_cap;
+    uint32_t *win;             // the 61-word window of this frame's lane (null: the tables' own slot)
+    // frames on several lanes: the frame's chain step waits for the previous frame's (wait_ev,
+    // null for the first) and announces itself (done_ev); null on one stream
+    hipEvent_t wait_ev, done_ev;
+};
+
 // Ordered per-row records (one wave per screen row): for every triangle in
 // order whose span on this row has a fragment on screen, a 48-byte record
 // with everything the fill needs -- no dependent loads in the fill loop (the

@@ -64,7 +64,10 @@ int rast_render_device(cg_ctx *ctx, const cg_rtri *d_tris, int n, const cg_rast_
                        hipStream_t st, cg_stats *stats, int tex_mask);
 int rast_draw_device(cg_ctx *c, const cg_rtri *d_room, int n_room, const cg_rtri *d_boxes, int n_boxes,
                      const cg_rast_params *p, uint32_t *d_argb, float *d_depth, int32_t *d_shadow,
-                     hipStream_t st, cg_stats *stats, int **n_out, int tex_mask);
+                     hipStream_t st, cg_stats *stats, int **n_out, int tex_mask, const RastSeq *seq = nullptr);
+int rast_seq_tables(cg_ctx *c, long long nb, long long *have, uint32_t **tables);
+int rast_rand_probe(cg_ctx *c, uint32_t *tables, int nb, const uint64_t *d_off, int n, int32_t *d_out, hipStream_t st);
+long long rast_rand_chunks(long long nvals);
 void rast_release(cg_ctx *ctx);
 }  // namespace cg
 
@@ -256,6 +259,10 @@ struct cg_ctx {
     // RAST scratch (owned by cg_rast.hip)
     DevBuf rtris, rhdr, rspan, rpix, rargb, rdepth, rshadow, rcount, rrecs, rgeo, rroom, rboxes;
     DevBuf rpc, rtl, rrnd, rjt;          // colour modes 1-2 (cg_rast_colour.hip)
+    // cg_rast_draw_sequence_device: the generator's tables (windows, seed words, J_b for
+    // rseq_chunks chunks) and the stream's capacity in fragments (0: 4 * W * H)
+    DevBuf rseq;
+    long long rseq_chunks = 0, rand_cap = 0;
     DevBuf sstars, sframe;               // starfield (cg_starfield.hip)
     DevBuf iscratch;                     // JPEG decode (cg_image.hip)
     int n_room = -1, n_boxes = 0;
@@ -269,6 +276,7 @@ struct cg_ctx {
     static constexpr int kRastLanes = 8;
     cg_ctx *lanes[kRastLanes] = {};
     hipEvent_t lane_ev[kRastLanes] = {};
+    hipEvent_t seq_ev[kRastLanes] = {};   // cg_rast_draw_sequence_device: a lane's latest chain step
     hipEvent_t start_ev = nullptr;
     unsigned scene_gen = 0, lane_gen[kRastLanes] = {};
 };
@@ -308,6 +316,7 @@ void *ctx_buf(cg_ctx *c, int which, size_t bytes, hipError_t *e)
     case 15: b = &c->sframe; break;
     case 16: b = &c->rtexel; break;
     case 17: b = &c->iscratch; break;
+    case 18: b = &c->rseq; break;
     default: *e = hipErrorInvalidValue; return nullptr;
     }
     *e = b->ensure(bytes);
@@ -336,6 +345,7 @@ void rast_release(cg_ctx *c)
     c->rargb.release(); c->rdepth.release(); c->rshadow.release(); c->rcount.release();
     c->rrecs.release(); c->rgeo.release(); c->rroom.release(); c->rboxes.release();
     c->rpc.release(); c->rtl.release(); c->rrnd.release(); c->rjt.release();
+    c->rseq.release();
     c->sstars.release(); c->sframe.release();
     c->tmarble.release(); c->tnoise.release(); c->twoven.release(); c->twoven_ao.release();
     c->twoven_op.release(); c->twoven_nrm.release(); c->tgrill.release(); c->tgrill_op.release();
@@ -421,6 +431,7 @@ extern "C" void cg_destroy(cg_ctx *c)
     for (int k = 0; k < cg_ctx::kRastLanes; ++k) {
         if (c->lanes[k]) cg_destroy(c->lanes[k]);
         if (c->lane_ev[k]) (void)hipEventDestroy(c->lane_ev[k]);
+        if (c->seq_ev[k]) (void)hipEventDestroy(c->seq_ev[k]);
     }
     if (c->start_ev) (void)hipEventDestroy(c->start_ev);
     for (int k = 0; k < 2; ++k) {
@@ -1759,6 +1770,8 @@ extern "C" int cg_rast_set_scene(cg_ctx *c, const cg_rtri *room, int n_room, con
     return CG_OK;
 }
 
+static int rast_lanes_ready(cg_ctx *c, int L);
+
 extern "C" int cg_rast_draw_frames_device(cg_ctx *c, const cg_rast_params *ps, int n_frames, uint32_t *d_argb,
                                           float *d_depth, int32_t *d_shadow, size_t frame_stride, void *stream)
 {
@@ -1786,6 +1799,32 @@ extern "C" int cg_rast_draw_frames_device(cg_ctx *c, const cg_rast_params *ps, i
         return std::max(1, std::min(v, (int)cg_ctx::kRastLanes));
     }();
     const int L = std::min(lanes, n_frames);
+    const int rc_lanes = rast_lanes_ready(c, L);
+    if (rc_lanes) return rc_lanes;
+    CG_TRY(c, hipEventRecord(c->start_ev, st), "event");
+    for (int k = 0; k < L; ++k) CG_TRY(c, hipStreamWaitEvent(c->lanes[k]->stream, c->start_ev, 0), "lane wait");
+    for (int f = 0; f < n_frames; ++f) {
+        cg_ctx *l = c->lanes[f % L];
+        const size_t o = (size_t)f * stride;
+        int rc = rast_draw_device(l, (const cg_rtri *)l->rroom.p, l->n_room, (const cg_rtri *)l->rboxes.p, l->n_boxes,
+                                  &ps[f], d_argb + o, d_depth ? d_depth + o : nullptr, d_shadow ? d_shadow + o : nullptr,
+                                  l->stream, nullptr, nullptr, l->scene_tex);
+        if (rc) {
+            c->err = std::string("lane: ") + l->err;
+            return rc;
+        }
+    }
+    for (int k = 0; k < L; ++k) {
+        CG_TRY(c, hipEventRecord(c->lane_ev[k], c->lanes[k]->stream), "event");
+        CG_TRY(c, hipStreamWaitEvent(st, c->lane_ev[k], 0), "lane join");
+    }
+    return CG_OK;
+}
+
+// The first L lane contexts with the parent's scene (created on first use; the scene is copied
+// device to device when it changed, which waits).
+static int rast_lanes_ready(cg_ctx *c, int L)
+{
     if (!c->start_ev) CG_TRY(c, hipEventCreateWithFlags(&c->start_ev, hipEventDisableTiming), "event");
     for (int k = 0; k < L; ++k) {
         if (!c->lanes[k]) {
@@ -1810,24 +1849,122 @@ extern "C" int cg_rast_draw_frames_device(cg_ctx *c, const cg_rast_params *ps, i
             c->lane_gen[k] = c->scene_gen;
         }
     }
-    CG_TRY(c, hipEventRecord(c->start_ev, st), "event");
-    for (int k = 0; k < L; ++k) CG_TRY(c, hipStreamWaitEvent(c->lanes[k]->stream, c->start_ev, 0), "lane wait");
+    return CG_OK;
+}
+
+// Largest generator the tables are built for (chunks of 992 values; 31 words each).
+static constexpr long long kRastSeqMaxChunks = 1ll << 22;
+
+extern "C" int cg_rast_set_rand_capacity(cg_ctx *c, long long fragments)
+{
+    if (!c || fragments < 0 || fragments > (1ll << 40) || rast_rand_chunks(3 * fragments) > kRastSeqMaxChunks)
+        return CG_E_INVALID;
+    c->rand_cap = fragments;
+    return CG_OK;
+}
+
+extern "C" int cg_rast_draw_sequence_device(cg_ctx *c, const cg_rast_params *ps, int n_frames, uint32_t *d_argb,
+                                            float *d_depth, int32_t *d_shadow, size_t frame_stride,
+                                            cg_rast_seq_frame *d_info, void *stream)
+{
+    if (!c || n_frames < 0 || (n_frames && (!ps || !d_argb))) return CG_E_INVALID;
+    if (c->n_room < 0) {
+        c->err = "draw before cg_rast_set_scene";
+        return CG_E_NOSCENE;
+    }
+    if (n_frames == 0) return CG_OK;
+    if (!d_info) return ctx_invalid(c, "draw_sequence: d_info is required");
+    if (ps[0].width <= 2 || ps[0].height <= 2) return ctx_invalid(c, "draw_sequence: frame size");
+    const size_t px = (size_t)ps[0].width * ps[0].height;
+    const size_t stride = frame_stride ? frame_stride : px;
+    bool colour = false;
     for (int f = 0; f < n_frames; ++f) {
-        cg_ctx *l = c->lanes[f % L];
+        if (ps[f].colour_mode < 0 || ps[f].colour_mode > 2 || ps[f].width != ps[0].width ||
+            ps[f].height != ps[0].height || stride < px)
+            return ctx_invalid(c, "draw_sequence: colour modes 0-2, frames of one size, frame_stride >= W * H");
+        colour = colour || ps[f].colour_mode != 0;
+    }
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    RastSeq q{};
+    q.start = ps[0].rand_offset;
+    q.cap = c->rand_cap > 0 ? c->rand_cap : 4 * (long long)px;
+    const long long nb = rast_rand_chunks(3 * q.cap);
+    if (nb > kRastSeqMaxChunks) return ctx_invalid(c, "draw_sequence: rand() stream capacity");
+    q.nb_cap = (int)nb;
+    // Lanes (CG_RAST_SEQ_LANES for A/B runs): a frame's front end up to its fragment count does
+    // not depend on the call index, so the frames run round-robin on the context's lane streams
+    // and only their chain steps follow each other (events): frame f + 1's front end runs beside
+    // frame f's seek, generator, fill and post.  1: every frame on `stream` itself.  6 -- 1080p
+    // colour mode 1, 64 frames per call (scripts/rast_sequence_rate.py, two runs each): 1 lane
+    // 2.75k frames/s, 2 3.5-4.0k, 3 3.3-3.4k, 4 3.8k, 5 4.3-4.4k, 6 4.75-4.80k, 7 4.4k, 8 4.5-4.6k.
+    static const int lanes = [] {
+        const char *e = std::getenv("CG_RAST_SEQ_LANES");
+        const int v = e ? std::atoi(e) : 6;
+        return std::max(1, std::min(v, (int)cg_ctx::kRastLanes));
+    }();
+    const int L = std::min(lanes, n_frames);
+    if (L > 1) {
+        const int rc = rast_lanes_ready(c, L);
+        if (rc) return rc;
+    }
+    if (colour) {
+        const int rc = rast_seq_tables(c, nb, &c->rseq_chunks, &q.tables);
+        if (rc) return rc;
+    }
+    uint32_t *win[cg_ctx::kRastLanes] = {};
+    for (int k = 0; k < L; ++k) {
+        cg_ctx *l = L > 1 ? c->lanes[k] : c;
+        hipError_t e;
+        if (L > 1) {
+            if (!c->seq_ev[k]) CG_TRY(c, hipEventCreateWithFlags(&c->seq_ev[k], hipEventDisableTiming), "event");
+            if (!(win[k] = (uint32_t *)ctx_buf(l, 18, 64 * sizeof(uint32_t), &e))) return ctx_fail(c, e, "alloc window");
+        }
+        if (!colour) continue;
+        // everything a colour frame sizes differently from a mode 0 frame, before the first
+        // launch: the frames then find every buffer in place (a buffer that grows waits)
+        if (!ctx_buf(l, 3, px * sizeof(float4), &e)) return ctx_fail(c, e, "alloc state");
+        if (!d_shadow && !ctx_buf(l, 6, px * sizeof(int32_t), &e)) return ctx_fail(c, e, "alloc shadow");
+        if (!ctx_buf(l, 12, 3 * (size_t)q.cap * sizeof(int32_t), &e)) return ctx_fail(c, e, "alloc rand stream");
+    }
+    if (L > 1) {
+        CG_TRY(c, hipEventRecord(c->start_ev, st), "event");
+        for (int k = 0; k < L; ++k) CG_TRY(c, hipStreamWaitEvent(c->lanes[k]->stream, c->start_ev, 0), "lane wait");
+    }
+    for (int f = 0; f < n_frames; ++f) {
         const size_t o = (size_t)f * stride;
-        int rc = rast_draw_device(l, (const cg_rtri *)l->rroom.p, l->n_room, (const cg_rtri *)l->rboxes.p, l->n_boxes,
-                                  &ps[f], d_argb + o, d_depth ? d_depth + o : nullptr, d_shadow ? d_shadow + o : nullptr,
-                                  l->stream, nullptr, nullptr, l->scene_tex);
+        cg_ctx *l = L > 1 ? c->lanes[f % L] : c;
+        q.info = d_info + f;
+        q.first = f == 0;
+        q.win = win[f % L];
+        q.wait_ev = L > 1 && f > 0 ? c->seq_ev[(f - 1) % L] : nullptr;
+        q.done_ev = L > 1 ? c->seq_ev[f % L] : nullptr;
+        const int rc = rast_draw_device(l, (const cg_rtri *)l->rroom.p, l->n_room, (const cg_rtri *)l->rboxes.p,
+                                        l->n_boxes, &ps[f], d_argb + o, d_depth ? d_depth + o : nullptr,
+                                        d_shadow ? d_shadow + o : nullptr, L > 1 ? l->stream : st, nullptr, nullptr,
+                                        l->scene_tex, &q);
         if (rc) {
-            c->err = std::string("lane: ") + l->err;
+            if (l != c) c->err = std::string("lane: ") + l->err;
             return rc;
         }
     }
-    for (int k = 0; k < L; ++k) {
+    for (int k = 0; L > 1 && k < L; ++k) {
         CG_TRY(c, hipEventRecord(c->lane_ev[k], c->lanes[k]->stream), "event");
         CG_TRY(c, hipStreamWaitEvent(st, c->lane_ev[k], 0), "lane join");
     }
     return CG_OK;
+}
+
+extern "C" int cg_glibc_rand_device(cg_ctx *c, const uint64_t *d_offset, int n, int32_t *d_out, void *stream)
+{
+    if (!c || n < 0 || (n && (!d_offset || !d_out))) return CG_E_INVALID;
+    if (n == 0) return CG_OK;
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    const long long nb = rast_rand_chunks(n);
+    uint32_t *tables = nullptr;
+    const int rc = rast_seq_tables(c, nb, &c->rseq_chunks, &tables);
+    if (rc) return rc;
+    return rast_rand_probe(c, tables, (int)nb, d_offset, n, d_out, stream ? (hipStream_t)stream : c->stream);
 }
 
 extern "C" int cg_rast_opacity_map(const uint8_t *bgr, int n, uint8_t *out)

@@ -407,6 +407,36 @@ int cg_rast_draw_device(cg_ctx *ctx, const cg_rast_params *p, uint32_t *d_argb, 
 int cg_rast_draw_frames_device(cg_ctx *ctx, const cg_rast_params *ps, int n_frames, uint32_t *d_argb,
                                float *d_depth, int32_t *d_shadow, size_t frame_stride, void *stream);
 
+/* One record per frame of a sequence, plus one closing record. */
+typedef struct { uint64_t rand_offset; int64_t n_shaded; int32_t status; int32_t pad; } cg_rast_seq_frame; /* 24 B */
+
+/* n_frames successive whole Draws as the main loop makes them (skeleton.cpp:203-308),
+ * any mix of colour modes 0/1/2, one size.  The rand() call index starts at
+ * ps[0].rand_offset; ps[f > 0].rand_offset is ignored.  A mode 1-2 frame starts at
+ * the chained index and advances it by 3 * its shaded fragments; a mode 0 frame
+ * leaves it alone.  Planes as cg_rast_draw_frames_device.  d_info (device,
+ * n_frames + 1 records, required): record f = the index frame f started at, its
+ * shaded fragments (-1 in mode 0) and its status; record n_frames = the index
+ * after the last frame, n_shaded -1, status 0.  Enqueued on `stream`: the frames
+ * start after the work already on it and it waits for all of them; between
+ * those points they overlap on internal streams, only the index passing from
+ * each frame to the next in order.  Nothing is read back, so after the first
+ * call of a size and capacity (which allocates and uploads the generator's
+ * tables) the call never waits.
+ * A mode 1-2 frame that shades more fragments than the rand() stream's capacity
+ * gets status CG_E_CAPACITY and its planes are left as they were; its record
+ * and every later frame stay exact (render it alone with cg_rast_draw at
+ * d_info[f].rand_offset).  One sequence per context at a time. */
+int cg_rast_draw_sequence_device(cg_ctx *ctx, const cg_rast_params *ps, int n_frames, uint32_t *d_argb,
+                                 float *d_depth, int32_t *d_shadow, size_t frame_stride,
+                                 cg_rast_seq_frame *d_info, void *stream);
+/* Test hook: capacity of the materialised rand() stream in fragments (3 values each);
+ * 0 = automatic, 4 * W * H. */
+int cg_rast_set_rand_capacity(cg_ctx *ctx, long long fragments);
+/* Probe: n values of glibc rand() starting at the 64-bit call index held in device
+ * memory, produced by the device seek + generator the sequence uses. */
+int cg_glibc_rand_device(cg_ctx *ctx, const uint64_t *d_offset, int n, int32_t *d_out, void *stream);
+
 /* Texture modes 1-3 (skeleton.cpp:588-645; a triangle's `texture` field,
  * TestModelH.h:21: 1 marble, 2 metal grill, 3 woven wood -- set it on the
  * room/boxes lists, as `setting` / `settingBoxes` do, TestModelH.h:9-10).
