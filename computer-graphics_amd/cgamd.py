@@ -123,6 +123,12 @@ _SIGS = {
                                       C.POINTER(RtShard), P, P]),
     "cg_rt_render_frames_device": (C.c_int, [P, C.POINTER(Light), C.c_int, C.POINTER(RtCamera), C.c_int,
                                              C.POINTER(RtShard), P, C.c_size_t, C.c_int, P]),
+    "cg_rt_render_sequence_device": (C.c_int, [P, C.POINTER(Light), C.c_int, C.POINTER(RtCamera), C.c_int,
+                                               C.POINTER(RtShard), P, C.c_size_t, C.c_int, P]),
+    "cg_rt_render_sequence": (C.c_int, [P, C.POINTER(Light), C.c_int, C.POINTER(RtCamera), C.c_int, P,
+                                        C.c_size_t, C.c_int, C.POINTER(Stats)]),
+    "cg_rt_sequence_runs": (C.c_int, [C.POINTER(RtCamera), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RtShard),
+                                      C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
     "cg_rt_assemble_device": (C.c_int, [P, P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int,
                                         C.c_int, C.c_int, P, C.c_size_t, C.c_int, C.c_int, P]),
     "cg_rt_frame_columns": (C.c_int, [C.POINTER(Tri), C.c_int, C.POINTER(Sphere), C.c_int, C.POINTER(RtCamera),
@@ -230,6 +236,37 @@ def rt_route(cam, n_tris, n_spheres, n_lights, shard=None):
     if rc < 0:
         raise ValueError(f"cg_rt_route: {rc}")
     return ROUTES[rc]
+
+
+def rt_sequence_runs(cams, n_tris, n_spheres, n_lights, shard=None):
+    """cg_rt_sequence_runs: how a frame sequence is launched (host-only; no GPU needed), as a
+    list of (start, stop, route name): consecutive frames on the same route form a run."""
+    lib = load()
+    arr = (RtCamera * max(len(cams), 1))(*cams)
+    sh = C.byref(shard) if shard is not None else None
+    cap = 8
+    while True:
+        start, route = (C.c_int * (cap + 1))(), (C.c_int * cap)()
+        n = lib.cg_rt_sequence_runs(arr, len(cams), n_tris, n_spheres, n_lights, sh, start, route, cap)
+        if n < 0:
+            raise ValueError(f"cg_rt_sequence_runs: {n}")
+        if n <= cap:
+            return [(start[r], start[r + 1], ROUTES[route[r]]) for r in range(n)]
+        cap = n
+
+
+def sequence_lights(lights_per_frame):
+    """A sequence's lights as one Light array, frame-major, and the common count per frame:
+    lights_per_frame is a list of per-frame light lists (or Light arrays) of equal length."""
+    n = len(lights_per_frame[0]) if len(lights_per_frame) else 0
+    if any(len(fl) != n for fl in lights_per_frame):
+        raise ValueError("every frame of a sequence has the same number of lights")
+    arr = (Light * max(len(lights_per_frame) * n, 1))()
+    for f, fl in enumerate(lights_per_frame):
+        for k in range(n):
+            arr[f * n + k].position = fl[k].position
+            arr[f * n + k].colour = fl[k].colour
+    return arr, n
 
 
 def rt_camera(width, height, focal=256.0, cam=(0.0, 0.0, -3.0, 1.0), R=None, indirect=0.5):
@@ -644,6 +681,43 @@ class Context:
         self._check(self.lib.cg_rt_render_frames_device(self.h, lights, len(lights), arr, len(cams), sh, P(d_out),
                                                         frame_stride, pix_format, P(stream) if stream else None),
                     "cg_rt_render_frames_device")
+
+    def rt_render_sequence_device(self, cams, lights, d_out, shard=None, stream=None, frame_stride=0,
+                                  pix_format=PIX_ARGB8888):
+        """cg_rt_render_sequence_device: frame f with camera cams[f] and lights lights[f] (a list of
+        per-frame light lists of equal length) into d_out + f * frame_stride pixels."""
+        if len(lights) != len(cams):
+            raise ValueError("one light list per frame")
+        larr, n = sequence_lights(lights)
+        arr = (RtCamera * max(len(cams), 1))(*cams)
+        sh = C.byref(shard) if shard is not None else None
+        self._check(self.lib.cg_rt_render_sequence_device(self.h, larr, n, arr, len(cams), sh, P(d_out), frame_stride,
+                                                          pix_format, P(stream) if stream else None),
+                    "cg_rt_render_sequence_device")
+
+    def rt_render_sequence(self, cams, lights, out=None, chunk=0, frame_stride=0):
+        """cg_rt_render_sequence: the sequence into host memory `out` (as rt_render_frames)."""
+        if len(lights) != len(cams):
+            raise ValueError("one light list per frame")
+        if not cams:   # the C entry returns CG_OK for n_frames == 0
+            return (np.zeros(0, np.uint32) if out is None else out), Stats()
+        larr, n = sequence_lights(lights)
+        arr = (RtCamera * max(len(cams), 1))(*cams)
+        npx = cams[0].width * cams[0].height
+        stride = frame_stride or npx
+        if stride < npx:
+            raise ValueError(f"frame_stride {stride} < W*H = {npx}")
+        if out is None:
+            out = np.zeros(len(cams) * stride, np.uint32)
+        need = (len(cams) - 1) * stride + npx
+        have = (out.nbytes if isinstance(out, np.ndarray) else out.numel() * out.element_size()) // 4
+        if have < need:
+            raise ValueError(f"out holds {have} pixels, {len(cams)} frames at stride {stride} need {need}")
+        ptr = out.ctypes.data if isinstance(out, np.ndarray) else out.data_ptr()
+        st = Stats()
+        self._check(self.lib.cg_rt_render_sequence(self.h, larr, n, arr, len(cams), P(ptr), stride, chunk, C.byref(st)),
+                    "cg_rt_render_sequence")
+        return out, st
 
     def rt_assemble_device(self, d_src, pix_format, row0, rows, width, height, nframes, d_frames, frame_stride=0,
                            stream=None, col0=0, cols=0):

@@ -52,7 +52,7 @@
 namespace cg {
 int rt_render_frames(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams, int n_frames,
                      const cg_rt_shard *shard, void *d_out, size_t frame_stride, int pix_format, void *stream,
-                     uint32_t *d_done, uint32_t *target, const int *group_starts, int ngroups);
+                     uint32_t *d_done, uint32_t *target, const int *group_starts, int ngroups, int light_stride);
 int ctx_device(const cg_ctx *c);
 hipStream_t ctx_stream(const cg_ctx *c);
 void ctx_set_error(cg_ctx *c, const std::string &e);
@@ -442,7 +442,7 @@ int render_band(cg_dist *d, const cg_light *lights, int n_lights, const cg_rt_ca
     t->frames = nf;
     DT(d, hipEventRecord(t->a, st), "event");
     rc = rt_render_frames(d->ctx, lights, n_lights, cams, nf, &sh, dst, stride, fmt, st, d_done, target,
-                          groups ? groups->data() : nullptr, groups ? (int)groups->size() - 1 : 0);
+                          groups ? groups->data() : nullptr, groups ? (int)groups->size() - 1 : 0, 0);
     if (rc) return rc;
     DT(d, hipEventRecord(t->b, st), "event");
     return CG_OK;

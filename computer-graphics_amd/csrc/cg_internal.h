@@ -91,6 +91,22 @@ struct RtFrameCams {
     float c[kMaxFrameBatch][4];
 };
 
+// Frame sequences (cg_rt_render_sequence_device): everything a frame of a run may change, one
+// record per frame in device memory.  The sequence kernels install record `frame` (workgroup-
+// uniform: scalar loads) into their RtFrame where the batched kernels install cams.c[frame].
+// lmin .. lrho: the frame's light-set summary, set_lights' expressions on the frame's lights.
+struct alignas(16) RtFrameRec {
+    float cam[4];
+    float focal, indirect;
+    float lmin[3], lmax[3], lc[3];
+    float pad;
+    float R[16];
+    double lrho;
+    uint32_t light_off;      // the frame's lights: entries light_off .. of the call's uploaded array (RtFrame::lights)
+    uint32_t pad1;
+};
+static_assert(sizeof(RtFrameRec) == 144, "RtFrameRec is 144 B");
+
 // Per-frame, per-triangle constants of ClosestIntersection for rays that
 // start at the camera (skeleton.cpp:279-306).  Every field is computed with
 // exactly the reference's float ops, so reusing it across rays is exact:

@@ -358,14 +358,83 @@ __device__ __forceinline__ void prep_block(const RtGeo *__restrict__ geo, int n,
     }
 }
 
-__global__ __launch_bounds__(kRtThreads) void rt_prepare_kernel(const cg_tri *__restrict__ tris,
-                                                                const RtGeo *__restrict__ geo, int n, RtFrameCams cams,
-                                                                RtTri *__restrict__ out, int n_prep_blocks,
-                                                                RtFrame F, const RtSphere *__restrict__ sph,
-                                                                unsigned long long *__restrict__ lat_masks, int sup)
+// The per-frame table of a batched launch: RtFrameCams by value (the batched entry points: frames
+// that differ in cameraPos only) or RtFrameSeq, a pointer to the launch's RtFrameRec records in
+// device memory (frame sequences: focal, indirect, R and the lights per frame too).  frame_cam:
+// the frame's cameraPos; frame_install: the rest of the record into F (nothing for RtFrameCams,
+// so the batched kernels are what they were).  `frame` is workgroup-uniform: scalar loads.
+struct RtFrameSeq {
+    const RtFrameRec *__restrict__ rec;
+};
+struct FrameCam {
+    float c[4];
+};
+__device__ __forceinline__ FrameCam frame_cam(const RtFrameCams &t, int frame)
+{
+    return FrameCam{{t.c[frame][0], t.c[frame][1], t.c[frame][2], t.c[frame][3]}};
+}
+// a workgroup-uniform value into an SGPR wherever the load itself was issued
+__device__ __forceinline__ float uniform_f(float x)
+{
+    return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x)));
+}
+__device__ __forceinline__ FrameCam frame_cam(const RtFrameSeq &t, int frame)
+{
+    const RtFrameRec &r = t.rec[frame];
+    return FrameCam{{uniform_f(r.cam[0]), uniform_f(r.cam[1]), uniform_f(r.cam[2]), uniform_f(r.cam[3])}};
+}
+__device__ __forceinline__ void frame_install(const RtFrameCams &, int, RtFrame &) {}
+__device__ __forceinline__ void frame_install(const RtFrameSeq &t, int frame, RtFrame &F)
+{
+    const RtFrameRec &r = t.rec[frame];
+    F.focal = uniform_f(r.focal);
+    F.indirect = uniform_f(r.indirect);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) F.R[k] = uniform_f(r.R[k]);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        F.lmin[k] = uniform_f(r.lmin[k]);
+        F.lmax[k] = uniform_f(r.lmax[k]);
+        F.lc[k] = uniform_f(r.lc[k]);
+    }
+    const unsigned long long rho = (unsigned long long)__double_as_longlong(r.lrho);
+    F.lrho = __longlong_as_double((long long)(
+        ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(rho >> 32)) << 32) |
+        (unsigned)__builtin_amdgcn_readfirstlane((int)rho)));
+    F.lights += (unsigned)__builtin_amdgcn_readfirstlane((int)r.light_off);   // F.lights: the call's uploaded array (a kernarg pointer, as the batched kernels')
+}
+
+// The frame a certificate kernel works on: the kernel's own RtFrame argument (RtFrameCams: read in
+// place, as before) or a copy with the frame's record installed (RtFrameSeq).
+template <class FT>
+struct FrameOf;
+template <>
+struct FrameOf<RtFrameCams> {
+    const RtFrame &F;
+    __device__ __forceinline__ FrameOf(const RtFrameCams &, int, const RtFrame &F0) : F(F0) {}
+};
+template <>
+struct FrameOf<RtFrameSeq> {
+    RtFrame F;
+    __device__ __forceinline__ FrameOf(const RtFrameSeq &t, int frame, const RtFrame &F0) : F(F0)
+    {
+        frame_install(t, frame, F);
+    }
+};
+
+// (The bodies' pointer parameters carry no __restrict__: inlined, they are the kernels' own
+// __restrict__ arguments, which keeps the aliasing facts of the kernels as they were written.)
+template <class FT>
+__device__ __forceinline__ void prepare_body(const cg_tri *tris, const RtGeo *geo, int n,
+                                             const FT &cams, RtTri *out, int n_prep_blocks,
+                                             const RtFrame &F0, const RtSphere *sph,
+                                             unsigned long long *lat_masks, int sup)
 {
     const int frame = blockIdx.y;
-    const float camf[4] = {cams.c[frame][0], cams.c[frame][1], cams.c[frame][2], cams.c[frame][3]};
+    const FrameCam cf = frame_cam(cams, frame);
+    const float camf[4] = {cf.c[0], cf.c[1], cf.c[2], cf.c[3]};
+    const FrameOf<FT> fo(cams, frame, F0);
+    const RtFrame &F = fo.F;
     if ((int)blockIdx.x < n_prep_blocks) {
         prep_block(geo, n, blockIdx.x, frame, camf, out);
         return;
@@ -389,6 +458,24 @@ __global__ __launch_bounds__(kRtThreads) void rt_prepare_kernel(const cg_tri *__
         lat_masks[2 * tile] = m;
         lat_masks[2 * tile + 1] = sm;
     }
+}
+
+__global__ __launch_bounds__(kRtThreads) void rt_prepare_kernel(const cg_tri *__restrict__ tris,
+                                                                const RtGeo *__restrict__ geo, int n, RtFrameCams cams,
+                                                                RtTri *__restrict__ out, int n_prep_blocks,
+                                                                RtFrame F, const RtSphere *__restrict__ sph,
+                                                                unsigned long long *__restrict__ lat_masks, int sup)
+{
+    prepare_body(tris, geo, n, cams, out, n_prep_blocks, F, sph, lat_masks, sup);
+}
+__global__ __launch_bounds__(kRtThreads) void rt_prepare_seq_kernel(const cg_tri *__restrict__ tris,
+                                                                    const RtGeo *__restrict__ geo, int n,
+                                                                    RtFrameSeq cams, RtTri *__restrict__ out,
+                                                                    int n_prep_blocks, RtFrame F,
+                                                                    const RtSphere *__restrict__ sph,
+                                                                    unsigned long long *__restrict__ lat_masks, int sup)
+{
+    prepare_body(tris, geo, n, cams, out, n_prep_blocks, F, sph, lat_masks, sup);
 }
 
 
@@ -451,15 +538,14 @@ __device__ __forceinline__ void lat_flatten(const LatFlatten &Z);   // below, wi
 // (CG_KTIME_ALL, four runs each; profiles/r06_ab_session2.json); 5 waves (236 B of scratch) slower
 #define CG_CERT_WAVES 3
 #endif
-__global__ __launch_bounds__(256, CG_CERT_WAVES) void rt_tile_cert_kernel(const cg_tri *__restrict__ tris,
-                                                           const RtGeo *__restrict__ geo, int n, RtFrameCams cams,
-                                                           RtFrame F, const RtSphere *__restrict__ sph,
-                                                           const unsigned long long *__restrict__ sup_masks,
-                                                           unsigned long long *__restrict__ lat_masks,
-                                                           unsigned long long *__restrict__ obj_masks,
-                                                           RtTri *__restrict__ tc_out,
-                                                           int n_prep_blocks, int frame_fast, LatFlatten Z,
-                                                           LatPublish P)
+template <class FT>
+__device__ __forceinline__ void tile_cert_body(const cg_tri *tris, const RtGeo *geo, int n,
+                                               const FT &cams, const RtFrame &F0, const RtSphere *sph,
+                                               const unsigned long long *sup_masks,
+                                               unsigned long long *lat_masks,
+                                               unsigned long long *obj_masks, RtTri *tc_out,
+                                               int n_prep_blocks, int frame_fast, const LatFlatten &Z,
+                                               const LatPublish &P)
 {
     constexpr int kT = kSup * kSup;
     // frame_fast: blockIdx.x = frame (dispatched fastest), blockIdx.y = prep block, then
@@ -467,7 +553,10 @@ __global__ __launch_bounds__(256, CG_CERT_WAVES) void rt_tile_cert_kernel(const 
     const int frame = frame_fast ? blockIdx.x : blockIdx.y, blk = frame_fast ? blockIdx.y : blockIdx.x;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-    const float camf[4] = {cams.c[frame][0], cams.c[frame][1], cams.c[frame][2], cams.c[frame][3]};
+    const FrameCam cf = frame_cam(cams, frame);
+    const float camf[4] = {cf.c[0], cf.c[1], cf.c[2], cf.c[3]};
+    const FrameOf<FT> fo(cams, frame, F0);
+    const RtFrame &F = fo.F;
     if (blk < n_prep_blocks) {
         prep_tri(geo, n, blk * blockDim.x + threadIdx.x, frame, camf, tc_out);
         // the first block (dispatched first) also sorts the lattice launch's order
@@ -742,6 +831,32 @@ __global__ __launch_bounds__(256, CG_CERT_WAVES) void rt_tile_cert_kernel(const 
     WGT_STAMP(wt3);
     wgt_record(1, wt0, wt1, wt2, wt3);
 #endif
+}
+
+__global__ __launch_bounds__(256, CG_CERT_WAVES) void rt_tile_cert_kernel(const cg_tri *__restrict__ tris,
+                                                           const RtGeo *__restrict__ geo, int n, RtFrameCams cams,
+                                                           RtFrame F, const RtSphere *__restrict__ sph,
+                                                           const unsigned long long *__restrict__ sup_masks,
+                                                           unsigned long long *__restrict__ lat_masks,
+                                                           unsigned long long *__restrict__ obj_masks,
+                                                           RtTri *__restrict__ tc_out,
+                                                           int n_prep_blocks, int frame_fast, LatFlatten Z,
+                                                           LatPublish P)
+{
+    tile_cert_body(tris, geo, n, cams, F, sph, sup_masks, lat_masks, obj_masks, tc_out, n_prep_blocks, frame_fast, Z, P);
+}
+// Frame sequences: each frame's record installed first (RtFrameSeq), never published.
+__global__ __launch_bounds__(256, CG_CERT_WAVES) void rt_tile_cert_seq_kernel(const cg_tri *__restrict__ tris,
+                                                           const RtGeo *__restrict__ geo, int n, RtFrameSeq cams,
+                                                           RtFrame F, const RtSphere *__restrict__ sph,
+                                                           const unsigned long long *__restrict__ sup_masks,
+                                                           unsigned long long *__restrict__ lat_masks,
+                                                           unsigned long long *__restrict__ obj_masks,
+                                                           RtTri *__restrict__ tc_out,
+                                                           int n_prep_blocks, int frame_fast, LatFlatten Z)
+{
+    tile_cert_body(tris, geo, n, cams, F, sph, sup_masks, lat_masks, obj_masks, tc_out, n_prep_blocks, frame_fast, Z,
+                   LatPublish{});
 }
 
 
@@ -1184,17 +1299,19 @@ __device__ __forceinline__ void lat_flatten(const LatFlatten &Z)
 // out + frame * out_stride.
 // PITCH: the LDS row pitch of the lattice, kLatW (shared columns) or kLatWY
 // (per-pixel columns; rt_lattice_ok).
-template <int PITCH>
+template <int PITCH, class FT>
 __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__restrict__ tc,
                                              const RtShade *__restrict__ shade, const RtSphere *__restrict__ sph,
-                                             const unsigned long long *__restrict__ lat_masks, const RtFrameCams &cams,
+                                             const unsigned long long *__restrict__ lat_masks, const FT &cams,
                                              size_t out_stride, uint32_t *__restrict__ out, const LatSlot &S,
                                              const LatReady &R, const unsigned long long *__restrict__ obj_masks)
 {
     const int frame = S.frame;
     RtFrame F = F0;
+    const FrameCam cf = frame_cam(cams, frame);
 #pragma unroll
-    for (int c = 0; c < 4; ++c) F.cam[c] = cams.c[frame][c];
+    for (int c = 0; c < 4; ++c) F.cam[c] = cf.c[c];
+    frame_install(cams, frame, F);
     tc += (size_t)frame * F.n_tris;
     lat_masks += (size_t)frame * lat_tiles_x(F) * gridDim.y * 2;
     if (obj_masks) obj_masks += (size_t)frame * lat_tiles_x(F) * gridDim.y * kObjSlots;
@@ -1471,19 +1588,21 @@ struct LatLightsTile {
     size_t tix;
     int nhalf;
 };
-template <int PITCH>
+template <int PITCH, class FT>
 __device__ __forceinline__ bool lat_lights_tile(const RtFrame &F0, const RtTri *__restrict__ &tc,
                                                 const RtShade *__restrict__ shade, const RtSphere *__restrict__ sph,
                                                 const unsigned long long *__restrict__ lat_masks,
-                                                const RtFrameCams &cams, size_t out_stride, uint32_t *out,
+                                                const FT &cams, size_t out_stride, uint32_t *out,
                                                 bool store_black, float *s_t, int8_t *s_bi, LatObj *s_obj,
                                                 LatLightsTile &T)
 {
     const int frame = blockIdx.z;
     RtFrame &F = T.F;
     F = F0;
+    const FrameCam cf = frame_cam(cams, frame);
 #pragma unroll
-    for (int c = 0; c < 4; ++c) F.cam[c] = cams.c[frame][c];
+    for (int c = 0; c < 4; ++c) F.cam[c] = cf.c[c];
+    frame_install(cams, frame, F);
     tc += (size_t)frame * F.n_tris;
     lat_masks += (size_t)frame * lat_tiles_x(F) * gridDim.y * 2;
     T.o = lat_out(F, frame, out_stride, out);
@@ -1575,12 +1694,12 @@ __device__ __forceinline__ unsigned long long lat_unit_mask(uint32_t code, unsig
 // rt_tile_cert_kernel, over a box of up to 11 points instead of the tile's.
 // A kernel of its own: the FP64 certificates need ~120 VGPRs, which would
 // cost the sweep (82) its fifth wave per SIMD or spill.
-template <int PITCH>
+template <int PITCH, class FT>
 __device__ __forceinline__ void lattice_units_body(const RtFrame &F0, const RtTri *__restrict__ tc,
                                                    const RtShade *__restrict__ shade,
                                                    const RtSphere *__restrict__ sph,
                                                    const unsigned long long *__restrict__ lat_masks,
-                                                   const RtFrameCams &cams, unsigned long long *__restrict__ umask)
+                                                   const FT &cams, unsigned long long *__restrict__ umask)
 {
     __shared__ float s_t[PITCH * kLatH];                               // pass 1: t and hit index
     __shared__ int8_t s_bi[PITCH * kLatH];
@@ -1678,13 +1797,13 @@ __device__ __forceinline__ void lattice_units_body(const RtFrame &F0, const RtTr
     }
 }
 
-template <int PITCH>
+template <int PITCH, class FT>
 __device__ __forceinline__ void lattice_lights_body(const RtFrame &F0, const RtTri *__restrict__ tc,
                                                     const RtShade *__restrict__ shade,
                                                     const RtSphere *__restrict__ sph,
                                                     const unsigned long long *__restrict__ lat_masks,
                                                     const unsigned long long *__restrict__ umask,
-                                                    const RtFrameCams &cams, size_t out_stride,
+                                                    const FT &cams, size_t out_stride,
                                                     uint32_t *__restrict__ out)
 {
     __shared__ float s_t[PITCH * kLatH];                              // pass 1: t and hit index
@@ -1914,6 +2033,38 @@ __global__ __launch_bounds__(kRtThreads, 6) void rt_lattice_lights_kernel(RtFram
     lat_signal(frame_done, blockIdx.z);
 }
 
+// Frame sequences: the same bodies over the launch's RtFrameRec records (RtFrameSeq) -- focal,
+// indirect, R and the lights per frame; certificates always complete before the launch.
+template <int PITCH>
+__global__ __launch_bounds__(kRtThreads, kRtMinWaves) void rt_lattice_seq_kernel(
+    RtFrame F0, const RtTri *__restrict__ tc, const RtShade *__restrict__ shade, const RtSphere *__restrict__ sph,
+    const unsigned long long *__restrict__ lat_masks, RtFrameSeq cams, size_t out_stride, uint32_t *__restrict__ out,
+    uint32_t *frame_done, LatOrder O, const unsigned long long *__restrict__ obj_masks)
+{
+    const unsigned long long t_start = wall_clock64();
+    const LatSlot S = lat_slot_of(O);
+    lattice_body<PITCH>(F0, tc, shade, sph, lat_masks, cams, out_stride, out, S, LatReady{}, obj_masks);
+    if (O.cost && S.frame == 0 && threadIdx.x == 0)
+        O.cost[S.by * (int)gridDim.x + S.bx] = (uint8_t)lat_cost_class(wall_clock64() - t_start);
+    lat_signal(frame_done, S.frame);
+}
+template <int PITCH>
+__global__ __launch_bounds__(kRtThreads, CG_UNITS_WAVES) void rt_lattice_units_seq_kernel(
+    RtFrame F0, const RtTri *__restrict__ tc, const RtShade *__restrict__ shade, const RtSphere *__restrict__ sph,
+    const unsigned long long *__restrict__ lat_masks, RtFrameSeq cams, unsigned long long *__restrict__ umask)
+{
+    lattice_units_body<PITCH>(F0, tc, shade, sph, lat_masks, cams, umask);
+}
+template <int PITCH>
+__global__ __launch_bounds__(kRtThreads, 6) void rt_lattice_lights_seq_kernel(
+    RtFrame F0, const RtTri *__restrict__ tc, const RtShade *__restrict__ shade, const RtSphere *__restrict__ sph,
+    const unsigned long long *__restrict__ lat_masks, const unsigned long long *__restrict__ umask, RtFrameSeq cams,
+    size_t out_stride, uint32_t *__restrict__ out, uint32_t *frame_done)
+{
+    lattice_lights_body<PITCH>(F0, tc, shade, sph, lat_masks, umask, cams, out_stride, out);
+    lat_signal(frame_done, blockIdx.z);
+}
+
 // ARGB8888 -> RGB24 wire format (kernels without a fused RGB24 store): rows
 // of W pixels -> rows of the window's wcols pixels (columns wcol0 ..), four
 // pixels per lane, three dwords out when aligned.
@@ -2112,8 +2263,11 @@ hipError_t launch_rt_scene(const cg_tri *d_tris, int n, RtGeo *d_geo, RtShade *d
 hipError_t launch_rt_prepare(const cg_tri *d_tris, const RtGeo *d_geo, int n, const RtFrameCams &cams, int nframes,
                              RtTri *d_tc, hipStream_t st, const RtFrame *F, const RtSphere *d_sph,
                              unsigned long long *d_lat_masks, unsigned long long *d_sup_masks, LatFlatten *Z,
-                             LatPublish *pub, unsigned long long **obj_masks)
+                             LatPublish *pub, unsigned long long **obj_masks, const RtFrameRec *recs)
 {
+    // recs: the launch's per-frame records (frame sequences; never published): the *_seq kernels
+    const RtFrameSeq seq{recs};
+    if (recs && pub && pub->flags) return hipErrorInvalidValue;
     const LatPublish P = pub ? *pub : LatPublish{};
     if (pub) pub->done = 0;
     // per-object shadow masks (in: the buffer; out: null unless this launch filled it -- only
@@ -2169,9 +2323,14 @@ hipError_t launch_rt_prepare(const cg_tri *d_tris, const RtGeo *d_geo, int n, co
             // takes its tiles, so its first frames' super-tiles come first
             const int ff = !P.flags && tprep + units_w <= 65535;
             const dim3 cg = ff ? dim3(nframes, tprep + units_w) : dim3(tprep + units_w, nframes);
-            kt_launch(kt_id, rt_tile_cert_kernel, cg, dim3(tthreads), 0, st, d_tris, d_geo, n, cams, Fl, d_sph,
-                               (const unsigned long long *)nullptr, d_lat_masks, d_obj_masks, d_tc, tprep, ff,
-                               Z ? *Z : LatFlatten{}, P);
+            if (recs)
+                kt_launch(kt_id, rt_tile_cert_seq_kernel, cg, dim3(tthreads), 0, st, d_tris, d_geo, n, seq, Fl, d_sph,
+                          (const unsigned long long *)nullptr, d_lat_masks, d_obj_masks, d_tc, tprep, ff,
+                          Z ? *Z : LatFlatten{});
+            else
+                kt_launch(kt_id, rt_tile_cert_kernel, cg, dim3(tthreads), 0, st, d_tris, d_geo, n, cams, Fl, d_sph,
+                                   (const unsigned long long *)nullptr, d_lat_masks, d_obj_masks, d_tc, tprep, ff,
+                                   Z ? *Z : LatFlatten{}, P);
             if (pub) pub->done = P.flags != nullptr;
             if (obj_masks) *obj_masks = d_obj_masks;
             if (Z) Z->n = -Z->n;   // done (the caller's flag: the lattice launch may use the order)
@@ -2183,16 +2342,25 @@ hipError_t launch_rt_prepare(const cg_tri *d_tris, const RtGeo *d_geo, int n, co
         cert = (units + tpw * (threads / 64) - 1) / (tpw * (threads / 64));
         {
             const int kt_id = KT_RT_PREPARE;
-            kt_launch(kt_id, rt_prepare_kernel, dim3(prep + cert, nframes), dim3(threads), 0, st, d_tris, d_geo, n,
-                               cams, d_tc, prep, Fl, d_sph, d_sup_masks, 1);
+            if (recs)
+                kt_launch(kt_id, rt_prepare_seq_kernel, dim3(prep + cert, nframes), dim3(threads), 0, st, d_tris, d_geo,
+                          n, seq, d_tc, prep, Fl, d_sph, d_sup_masks, 1);
+            else
+                kt_launch(kt_id, rt_prepare_kernel, dim3(prep + cert, nframes), dim3(threads), 0, st, d_tris, d_geo, n,
+                                   cams, d_tc, prep, Fl, d_sph, d_sup_masks, 1);
         }
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         const int kt_id = KT_RT_TILE_CERT;
         const int ff = units <= 65535;
-        kt_launch(kt_id, rt_tile_cert_kernel, ff ? dim3(nframes, units) : dim3(units, nframes), dim3(tthreads), 0, st,
-                           d_tris, d_geo, n, cams, Fl, d_sph, (const unsigned long long *)d_sup_masks, d_lat_masks,
-                           d_obj_masks, (RtTri *)nullptr, 0, ff, LatFlatten{}, LatPublish{});
+        if (recs)
+            kt_launch(kt_id, rt_tile_cert_seq_kernel, ff ? dim3(nframes, units) : dim3(units, nframes), dim3(tthreads), 0,
+                      st, d_tris, d_geo, n, seq, Fl, d_sph, (const unsigned long long *)d_sup_masks, d_lat_masks,
+                      d_obj_masks, (RtTri *)nullptr, 0, ff, LatFlatten{});
+        else
+            kt_launch(kt_id, rt_tile_cert_kernel, ff ? dim3(nframes, units) : dim3(units, nframes), dim3(tthreads), 0,
+                      st, d_tris, d_geo, n, cams, Fl, d_sph, (const unsigned long long *)d_sup_masks, d_lat_masks,
+                      d_obj_masks, (RtTri *)nullptr, 0, ff, LatFlatten{}, LatPublish{});
         if (obj_masks) *obj_masks = d_obj_masks;
         return hipGetLastError();
     }
@@ -2203,8 +2371,12 @@ hipError_t launch_rt_prepare(const cg_tri *d_tris, const RtGeo *d_geo, int n, co
         cert = (units + tpw * (threads / 64) - 1) / (tpw * (threads / 64));
     }
     const int kt_id = KT_RT_PREPARE;
-    kt_launch(kt_id, rt_prepare_kernel, dim3(prep + cert, nframes), dim3(threads), 0, st, d_tris, d_geo, n, cams,
-                       d_tc, prep, Fl, d_sph, d_lat_masks, 0);
+    if (recs)
+        kt_launch(kt_id, rt_prepare_seq_kernel, dim3(prep + cert, nframes), dim3(threads), 0, st, d_tris, d_geo, n, seq,
+                  d_tc, prep, Fl, d_sph, d_lat_masks, 0);
+    else
+        kt_launch(kt_id, rt_prepare_kernel, dim3(prep + cert, nframes), dim3(threads), 0, st, d_tris, d_geo, n, cams,
+                           d_tc, prep, Fl, d_sph, d_lat_masks, 0);
     return hipGetLastError();
 }
 
@@ -2259,12 +2431,20 @@ size_t rt_lattice_unit_bytes(const RtFrame &F, int nframes)
 
 hipError_t launch_rt_lattice_units(const RtFrame &F, const RtTri *d_tc, const RtShade *d_shade,
                                    const RtSphere *d_sph, const unsigned long long *d_lat_masks,
-                                   const RtFrameCams &cams, int nframes, unsigned long long *d_umask, hipStream_t st)
+                                   const RtFrameCams &cams, int nframes, unsigned long long *d_umask, hipStream_t st,
+                                   const RtFrameRec *recs)
 {
     if (F.n_lights <= 1) return hipSuccess;
     const dim3 grid(F.txn ? F.txn : lat_tiles_x(F), (F.rows_out + kLatTileH - 1) / kLatTileH, nframes);
     const int kt_id = KT_RT_LATTICE_UNITS;
-    if (lat_yaw(F))
+    const RtFrameSeq seq{recs};
+    if (recs && lat_yaw(F))
+        kt_launch(kt_id, rt_lattice_units_seq_kernel<kLatWY>, grid, dim3(kRtThreads), 0, st, F, d_tc, d_shade, d_sph,
+                  d_lat_masks, seq, d_umask);
+    else if (recs)
+        kt_launch(kt_id, rt_lattice_units_seq_kernel<kLatW>, grid, dim3(kRtThreads), 0, st, F, d_tc, d_shade, d_sph,
+                  d_lat_masks, seq, d_umask);
+    else if (lat_yaw(F))
         kt_launch(kt_id, rt_lattice_units_kernel<kLatWY>, grid, dim3(kRtThreads), 0, st, F, d_tc, d_shade, d_sph,
                            d_lat_masks, cams, d_umask);
     else
@@ -2278,7 +2458,7 @@ hipError_t launch_rt_lattice_frames(const RtFrame &F, const RtTri *d_tc, const R
                                     const unsigned long long *d_umask, const RtFrameCams &cams, int nframes,
                                     size_t out_stride, uint32_t *d_out, hipStream_t st, uint32_t *d_done,
                                     const LatOrder *order, const LatReady *ready,
-                                    const unsigned long long *d_obj_masks)
+                                    const unsigned long long *d_obj_masks, const RtFrameRec *recs)
 {
     const LatOrder O = order ? *order : LatOrder{};
     const LatReady R = ready ? *ready : LatReady{};
@@ -2287,6 +2467,23 @@ hipError_t launch_rt_lattice_frames(const RtFrame &F, const RtTri *d_tc, const R
     if (F.n_lights > 1 && !d_umask) return hipErrorInvalidValue;
     if (F.txn && (F.tx0 < 0 || F.tx0 + F.txn > lat_tiles_x(F))) return hipErrorInvalidValue;
     const int kt_id = F.n_lights == 1 ? KT_RT_LATTICE : KT_RT_LATTICE_LIGHTS;
+    if (recs) {   // frame sequences: per-frame records, certificates first
+        const RtFrameSeq seq{recs};
+        if (R.flags) return hipErrorInvalidValue;
+        if (F.n_lights == 1 && lat_yaw(F))
+            kt_launch(kt_id, rt_lattice_seq_kernel<kLatWY>, grid, dim3(kRtThreads), 0, st, F, d_tc, d_shade, d_sph,
+                      d_lat_masks, seq, out_stride, d_out, d_done, O, d_obj_masks);
+        else if (F.n_lights == 1)
+            kt_launch(kt_id, rt_lattice_seq_kernel<kLatW>, grid, dim3(kRtThreads), 0, st, F, d_tc, d_shade, d_sph,
+                      d_lat_masks, seq, out_stride, d_out, d_done, O, d_obj_masks);
+        else if (lat_yaw(F))
+            kt_launch(kt_id, rt_lattice_lights_seq_kernel<kLatWY>, grid, dim3(kRtThreads), 0, st, F, d_tc, d_shade,
+                      d_sph, d_lat_masks, d_umask, seq, out_stride, d_out, d_done);
+        else
+            kt_launch(kt_id, rt_lattice_lights_seq_kernel<kLatW>, grid, dim3(kRtThreads), 0, st, F, d_tc, d_shade,
+                      d_sph, d_lat_masks, d_umask, seq, out_stride, d_out, d_done);
+        return hipGetLastError();
+    }
     if (F.n_lights == 1 && lat_yaw(F))
         kt_launch(kt_id, rt_lattice_kernel<kLatWY>, grid, dim3(kRtThreads), 0, st, F, d_tc, d_shade, d_sph,
                            d_lat_masks, cams, out_stride, d_out, d_done, O, R, d_obj_masks);
@@ -2311,10 +2508,10 @@ hipError_t launch_rt_pixels(const RtFrame &F, const RtTri *d_tc, const RtShade *
     if (d_lat_masks && rt_use_lattice(F)) {
         RtFrameCams cams{};
         for (int c = 0; c < 4; ++c) cams.c[0][c] = F.cam[c];
-        hipError_t e = launch_rt_lattice_units(F, d_tc, d_shade, d_sph, d_lat_masks, cams, 1, d_umask, st);
+        hipError_t e = launch_rt_lattice_units(F, d_tc, d_shade, d_sph, d_lat_masks, cams, 1, d_umask, st, nullptr);
         if (e != hipSuccess) return e;
         return launch_rt_lattice_frames(F, d_tc, d_shade, d_sph, d_lat_masks, d_umask, cams, 1, 0, d_out, st,
-                                        nullptr, nullptr, nullptr, d_obj_masks);
+                                        nullptr, nullptr, nullptr, d_obj_masks, nullptr);
     }
     const int kt_id = KT_RT_PIXEL;
     if (F.n_tris <= 64 && F.cull_primary)

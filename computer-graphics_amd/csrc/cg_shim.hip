@@ -22,17 +22,19 @@
 namespace cg {
 hipError_t launch_rt_prepare(const cg_tri *, const RtGeo *, int, const RtFrameCams &, int, RtTri *, hipStream_t,
                              const RtFrame *, const RtSphere *, unsigned long long *, unsigned long long *,
-                             LatFlatten * = nullptr, LatPublish * = nullptr, unsigned long long ** = nullptr);
+                             LatFlatten * = nullptr, LatPublish * = nullptr, unsigned long long ** = nullptr,
+                             const RtFrameRec * = nullptr);
 hipError_t launch_rt_scene(const cg_tri *, int, RtGeo *, RtShade *, hipStream_t);
 hipError_t rt_render_brute(const RtFrame &, const cg_tri *, int, const RtSphere *, int, int, uint32_t *, hipStream_t);
 size_t rt_sup_units(const RtFrame &);
 hipError_t launch_rt_lattice_frames(const RtFrame &, const RtTri *, const RtShade *, const RtSphere *,
                                     const unsigned long long *, const unsigned long long *, const RtFrameCams &,
                                     int, size_t, uint32_t *, hipStream_t, uint32_t *, const LatOrder *,
-                                    const LatReady * = nullptr, const unsigned long long * = nullptr);
+                                    const LatReady * = nullptr, const unsigned long long * = nullptr,
+                                    const RtFrameRec * = nullptr);
 hipError_t launch_rt_lattice_units(const RtFrame &, const RtTri *, const RtShade *, const RtSphere *,
                                    const unsigned long long *, const RtFrameCams &, int, unsigned long long *,
-                                   hipStream_t);
+                                   hipStream_t, const RtFrameRec * = nullptr);
 size_t rt_lattice_unit_bytes(const RtFrame &, int);
 hipError_t launch_rt_pixels(const RtFrame &, const RtTri *, const RtShade *, const RtSphere *,
                             const unsigned long long *, unsigned long long *, uint32_t *, hipStream_t,
@@ -256,6 +258,18 @@ struct cg_ctx {
     // the scene (1M triangles: ~6 ms on the host) and no per-camera cache
     double box_lo[3] = {1e300, 1e300, 1e300}, box_hi[3] = {-1e300, -1e300, -1e300};
     std::vector<RtLight> lights_host;   // what `lights` holds (re-uploaded only on change)
+    // Frame sequences (cg_rt_render_sequence_device): a call's n_frames x n_lights lights and its
+    // RtFrameRec table, uploaded once through pinned staging memory into one of two slots, so that
+    // two calls queued back to back read their own (ev_lat's discipline): `up` after the slot's
+    // upload (the staging memory is free again), `done` after the call's last kernel (the device
+    // copy is).  Both slots grow together, so only the first call of a size allocates.
+    struct SeqSlot {
+        DevBuf dev;
+        void *host = nullptr;
+        size_t host_bytes = 0;
+        hipEvent_t up = nullptr, done = nullptr;
+    } seq[2];
+    int seq_slot = 0;
     // RAST scratch (owned by cg_rast.hip)
     DevBuf rtris, rhdr, rspan, rpix, rargb, rdepth, rshadow, rcount, rrecs, rgeo, rroom, rboxes;
     DevBuf rpc, rtl, rrnd, rjt;          // colour modes 1-2 (cg_rast_colour.hip)
@@ -448,6 +462,12 @@ extern "C" void cg_destroy(cg_ctx *c)
         if (c->ev_cdone[k]) (void)hipEventDestroy(c->ev_cdone[k]);
     }
     if (c->xfer) (void)hipStreamDestroy(c->xfer);
+    for (auto &q : c->seq) {
+        q.dev.release();
+        if (q.host) (void)hipHostFree(q.host);
+        if (q.up) (void)hipEventDestroy(q.up);
+        if (q.done) (void)hipEventDestroy(q.done);
+    }
     rast_release(c);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -554,30 +574,41 @@ extern "C" int cg_rt_set_scene(cg_ctx *c, const cg_tri *tris, int n_tris, const 
 
 // Lights to the device buffer (ordered on `st`; skipped when unchanged) and
 // the light-set summary the shadow certificate uses.
+static RtLight rt_light_of(const cg_light &l)
+{
+    return RtLight{l.position.x, l.position.y, l.position.z, l.position.w, l.colour.x, l.colour.y, l.colour.z, 0.f};
+}
+// The light set as the shadow certificates see it (RtFrame::lmin .. lrho), for one frame's lights.
+static void light_summary(const RtLight *L, int n, float lmin[3], float lmax[3], float lc[3], double &lrho)
+{
+    for (int k = 0; k < 3; ++k) lmin[k] = lmax[k] = lc[k] = 0.f;
+    lrho = 0.0;
+    if (n > 0) {
+        for (int k = 0; k < 3; ++k) lmin[k] = lmax[k] = (&L[0].x)[k];
+        for (int l = 0; l < n; ++l) {
+            const RtLight &q = L[l];
+            for (int k = 0; k < 3; ++k) {
+                lmin[k] = std::min(lmin[k], (&q.x)[k]);
+                lmax[k] = std::max(lmax[k], (&q.x)[k]);
+            }
+        }
+        for (int k = 0; k < 3; ++k) lc[k] = 0.5f * lmin[k] + 0.5f * lmax[k];
+        double rho = 0.0;
+        for (int l = 0; l < n; ++l) {
+            const RtLight &q = L[l];
+            double dx = (double)q.x - lc[0], dy = (double)q.y - lc[1], dz = (double)q.z - lc[2];
+            rho = std::max(rho, std::sqrt(dx * dx + dy * dy + dz * dz));
+        }
+        lrho = rho > 0.0 ? rho * (1.0 + 1e-9) + 1e-12 : 0.0;
+    }
+}
+
 static int set_lights(cg_ctx *c, const cg_light *lights, int n, hipStream_t st, RtFrame &F)
 {
     std::vector<RtLight> L((size_t)n);
-    for (int l = 0; l < n; ++l)
-        L[l] = RtLight{lights[l].position.x, lights[l].position.y, lights[l].position.z, lights[l].position.w,
-                       lights[l].colour.x,   lights[l].colour.y,   lights[l].colour.z,   0.f};
+    for (int l = 0; l < n; ++l) L[l] = rt_light_of(lights[l]);
     F.n_lights = n;
-    for (int k = 0; k < 3; ++k) F.lmin[k] = F.lmax[k] = F.lc[k] = 0.f;
-    F.lrho = 0.0;
-    if (n > 0) {
-        for (int k = 0; k < 3; ++k) F.lmin[k] = F.lmax[k] = (&L[0].x)[k];
-        for (const RtLight &q : L)
-            for (int k = 0; k < 3; ++k) {
-                F.lmin[k] = std::min(F.lmin[k], (&q.x)[k]);
-                F.lmax[k] = std::max(F.lmax[k], (&q.x)[k]);
-            }
-        for (int k = 0; k < 3; ++k) F.lc[k] = 0.5f * F.lmin[k] + 0.5f * F.lmax[k];
-        double rho = 0.0;
-        for (const RtLight &q : L) {
-            double dx = (double)q.x - F.lc[0], dy = (double)q.y - F.lc[1], dz = (double)q.z - F.lc[2];
-            rho = std::max(rho, std::sqrt(dx * dx + dy * dy + dz * dz));
-        }
-        F.lrho = rho > 0.0 ? rho * (1.0 + 1e-9) + 1e-12 : 0.0;
-    }
+    light_summary(L.data(), n, F.lmin, F.lmax, F.lc, F.lrho);
     const bool same = L.size() == c->lights_host.size() &&
                       (L.empty() || std::memcmp(L.data(), c->lights_host.data(), L.size() * sizeof(RtLight)) == 0);
     CG_TRY(c, c->lights.ensure(std::max<size_t>(L.size(), 1) * sizeof(RtLight)), "alloc lights");
@@ -666,6 +697,19 @@ extern "C" int cg_rt_render_brute_device(cg_ctx *c, const cg_light *lights, int 
     return CG_OK;
 }
 
+// CG_RT_ROUTE_* of a frame whose shape and counts are set (host only)
+static int frame_route(const RtFrame &F)
+{
+    if (F.n_tris > 64) {   // rt_enqueue_kernels: the large-scene path
+        const int m = rt_big_mode(F);
+        return m == 0 ? CG_RT_ROUTE_BIG_PIXEL : m == 1 ? CG_RT_ROUTE_BIG_LATTICE : CG_RT_ROUTE_BIG_LATTICE_YAW;
+    }
+    const int k = rt_lattice_kind(F);
+    if (k == 0) return CG_RT_ROUTE_PIXEL;
+    if (F.n_lights == 1) return k == 1 ? CG_RT_ROUTE_LATTICE : CG_RT_ROUTE_LATTICE_YAW;
+    return k == 1 ? CG_RT_ROUTE_LIGHTS : CG_RT_ROUTE_LIGHTS_YAW;
+}
+
 extern "C" int cg_rt_route(const cg_rt_camera *cam, int n_tris, int n_spheres, int n_lights, const cg_rt_shard *shard)
 {
     if (!cam || cam->width <= 0 || cam->height <= 0 || n_tris < 0 || n_spheres < 0 || n_lights < 0 ||
@@ -677,14 +721,53 @@ extern "C" int cg_rt_route(const cg_rt_camera *cam, int n_tris, int n_spheres, i
     F.n_tris = n_tris;
     F.n_sph = n_spheres;
     F.n_lights = n_lights;
-    if (F.n_tris > 64) {   // rt_enqueue_kernels: the large-scene path
-        const int m = rt_big_mode(F);
-        return m == 0 ? CG_RT_ROUTE_BIG_PIXEL : m == 1 ? CG_RT_ROUTE_BIG_LATTICE : CG_RT_ROUTE_BIG_LATTICE_YAW;
+    return frame_route(F);
+}
+
+// A sequence's runs (cg_rt_sequence_runs): consecutive frames on the same route.  Size, shard and
+// light count are the call's, so the route alone separates runs; frames of a lattice run share
+// batched launches, the other routes' runs are enqueued frame by frame.
+static int sequence_runs(const cg_rt_camera *cams, int n_frames, int n_tris, int n_spheres, int n_lights,
+                         const cg_rt_shard *shard, std::vector<int> &start, std::vector<int> &route)
+{
+    start.clear();
+    route.clear();
+    if (n_frames < 0 || (n_frames && !cams) || n_tris < 0 || n_spheres < 0 || n_lights < 0 || n_lights > kMaxLights)
+        return CG_E_INVALID;
+    for (int f = 0; f < n_frames; ++f) {
+        if (cams[f].width <= 0 || cams[f].height <= 0 || cams[f].width != cams[0].width ||
+            cams[f].height != cams[0].height)
+            return CG_E_INVALID;
+        RtFrame F;
+        const int rc = frame_shape(&cams[f], shard, F);
+        if (rc) return rc;
+        F.n_tris = n_tris;
+        F.n_sph = n_spheres;
+        F.n_lights = n_lights;
+        const int r = frame_route(F);
+        if (route.empty() || route.back() != r) {
+            start.push_back(f);
+            route.push_back(r);
+        }
     }
-    const int k = rt_lattice_kind(F);
-    if (k == 0) return CG_RT_ROUTE_PIXEL;
-    if (n_lights == 1) return k == 1 ? CG_RT_ROUTE_LATTICE : CG_RT_ROUTE_LATTICE_YAW;
-    return k == 1 ? CG_RT_ROUTE_LIGHTS : CG_RT_ROUTE_LIGHTS_YAW;
+    start.push_back(n_frames);
+    return CG_OK;
+}
+
+extern "C" int cg_rt_sequence_runs(const cg_rt_camera *cams, int n_frames, int n_tris, int n_spheres, int n_lights,
+                                   const cg_rt_shard *shard, int *run_start, int *run_route, int cap)
+{
+    if (cap < 0 || (cap && (!run_start || !run_route))) return CG_E_INVALID;
+    std::vector<int> start, route;
+    const int rc = sequence_runs(cams, n_frames, n_tris, n_spheres, n_lights, shard, start, route);
+    if (rc) return rc;
+    const int runs = (int)route.size(), n = std::min(runs, cap);
+    for (int r = 0; r < n; ++r) {
+        run_start[r] = start[r];
+        run_route[r] = route[r];
+    }
+    if (cap > 0) run_start[n] = start[n];   // run_start has cap + 1 entries
+    return runs;
 }
 
 // A large-scene frame slot's buffers (slot 0: the context's own; slot 1: the
@@ -984,7 +1067,8 @@ extern "C" int cg_rt_render_device(cg_ctx *c, const cg_light *lights, int n_ligh
 }
 
 // Frames f0 .. f0 + nf - 1 of a batch, one prepare + one lattice launch
-// (rt_use_lattice(F) holds for every frame; they differ only in cameraPos).
+// (rt_use_lattice(F) holds for every frame; they differ only in cameraPos, or -- a frame
+// sequence, d_recs -- in whatever an RtFrameRec holds).
 
 // The launch geometry a lattice order is recorded for (0 never occurs): the
 // same key means the same tiles in the same window, so the recording predicts
@@ -1052,8 +1136,14 @@ static long long lat_resident_wgs()
 
 static int rt_enqueue_lattice_batch(cg_ctx *c, const RtFrame &F0, const cg_rt_camera *cams, int nf,
                                     void *d_out, size_t stride, hipStream_t st, uint32_t *d_done,
-                                    uint32_t *tiles_per_frame, const uint8_t *groups, int ngroups)
+                                    uint32_t *tiles_per_frame, const uint8_t *groups, int ngroups,
+                                    const RtFrameRec *d_recs = nullptr, bool uniform = true,
+                                    hipEvent_t uploaded = nullptr)
 {
+    // d_recs (frame sequences): the launch's per-frame records on the device -- the frames may
+    // differ in focal, indirect, R (within F0's lattice kind) and lights too; F0 is the first
+    // frame's.  uniform: every frame shares F0's focal and R (the measured order is keyed on them).
+    // uploaded: recorded on st after the records' upload (certificates on aux wait for it).
     // Workgroups only for the tile columns the scene's box can be seen in by
     // some camera of the batch (O(1) per camera from the box, rt_box_columns);
     // the launch's edge workgroups store the rest black.  C2: 73 of 120 tile
@@ -1157,7 +1247,7 @@ static int rt_enqueue_lattice_batch(cg_ctx *c, const RtFrame &F0, const cg_rt_ca
     const unsigned long long key = lat_order_key(c, F);
     LatOrder order{};
     LatFlatten flat{};
-    const bool ordered = lat_order_mode() > 0 && F.n_lights == 1 &&
+    const bool ordered = lat_order_mode() > 0 && F.n_lights == 1 && uniform &&
                          (long long)gx * gy * nf <= kLatOrderRounds * lat_resident_wgs();
     // Published certificates (LatReady, cg_internal.h): the one-light lattice
     // launch starts beside its certificate launch instead of after it, each
@@ -1165,7 +1255,7 @@ static int rt_enqueue_lattice_batch(cg_ctx *c, const RtFrame &F0, const cg_rt_ca
     // order: whole frames; band calls keep the measured order, whose sort the
     // certificate launch does first)
     const bool conc = cert_concurrent() && !ordered && F.n_lights == 1 && F.n_tris <= 62 &&
-                      !rt_lattice_unit_bytes(F, nf);
+                      !rt_lattice_unit_bytes(F, nf) && !d_recs;   // sequences: certificates first
     // certificates on aux, after the slot's previous reader, so that they run
     // beside the lattice launch still queued before them (or, published, beside
     // this call's own).  A cold call with unpublished certificates (every
@@ -1174,6 +1264,7 @@ static int rt_enqueue_lattice_batch(cg_ctx *c, const RtFrame &F0, const cg_rt_ca
     // the GPU idle for ~12 us between certificates and lattice.
     hipStream_t cst = (cold && !conc) ? st : c->aux;
     if (!cold) CG_TRY(c, hipStreamWaitEvent(cst, c->ev_lat[k], 0), "aux wait");
+    if (d_recs && cst != st) CG_TRY(c, hipStreamWaitEvent(cst, uploaded, 0), "aux wait");
     LatPublish pub{};
     LatReady ready{};
     if (conc) {
@@ -1206,7 +1297,7 @@ static int rt_enqueue_lattice_batch(cg_ctx *c, const RtFrame &F0, const cg_rt_ca
     }
     CG_TRY(c, launch_rt_prepare((const cg_tri *)c->tris.p, (const RtGeo *)c->geo.p, c->n_tris, fc, nf,
                                 (RtTri *)btc.p, cst, &F, (const RtSphere *)c->sph.p, lat, supm,
-                                flat.n > 0 ? &flat : nullptr, conc ? &pub : nullptr, &obj),
+                                flat.n > 0 ? &flat : nullptr, conc ? &pub : nullptr, &obj, d_recs),
            "rt_prepare launch");
     if (conc && !pub.done) ready = LatReady{};   // not published (the split certificate form): nothing to wait for
     if (ordered) {
@@ -1227,14 +1318,15 @@ static int rt_enqueue_lattice_batch(cg_ctx *c, const RtFrame &F0, const cg_rt_ca
     if (rt_lattice_unit_bytes(F, nf)) {
         um = (unsigned long long *)bum.p;
         CG_TRY(c, launch_rt_lattice_units(F, (const RtTri *)btc.p, (const RtShade *)c->shade.p, (const RtSphere *)c->sph.p,
-                                          lat, fc, nf, um, cst),
+                                          lat, fc, nf, um, cst, d_recs),
                "rt_lattice_units launch");
     }
     if (!cold || conc) CG_TRY(c, hipEventRecord(c->ev_cert[k], cst), "aux record");
     if (!cold && !conc) CG_TRY(c, hipStreamWaitEvent(st, c->ev_cert[k], 0), "aux wait");
     CG_TRY(c, launch_rt_lattice_frames(F, (const RtTri *)btc.p, (const RtShade *)c->shade.p,
                                        (const RtSphere *)c->sph.p, lat, um, fc, nf, stride, (uint32_t *)d_out, st,
-                                       d_done, ordered ? &order : nullptr, ready.flags ? &ready : nullptr, obj),
+                                       d_done, ordered ? &order : nullptr, ready.flags ? &ready : nullptr, obj,
+                                       d_recs),
            "rt_lattice launch");
     c->last_masks.lat = lat;
     c->last_masks.obj = obj;
@@ -1266,7 +1358,7 @@ static size_t pix_bytes(int fmt) { return fmt == CG_PIX_RGB24 ? 3 : 4; }
 namespace cg {
 int rt_render_frames(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams, int n_frames,
                      const cg_rt_shard *shard, void *d_out, size_t frame_stride, int pix_format, void *stream,
-                     uint32_t *d_done, uint32_t *target, const int *group_starts, int ngroups);
+                     uint32_t *d_done, uint32_t *target, const int *group_starts, int ngroups, int light_stride);
 }
 
 extern "C" int cg_rt_render_frames_device(cg_ctx *c, const cg_light *lights, int n_lights,
@@ -1274,7 +1366,167 @@ extern "C" int cg_rt_render_frames_device(cg_ctx *c, const cg_light *lights, int
                                           void *d_out, size_t frame_stride, int pix_format, void *stream)
 {
     return rt_render_frames(c, lights, n_lights, cams, n_frames, shard, d_out, frame_stride, pix_format, stream,
-                            nullptr, nullptr, nullptr, 0);
+                            nullptr, nullptr, nullptr, 0, 0);
+}
+
+extern "C" int cg_rt_render_sequence_device(cg_ctx *c, const cg_light *lights, int n_lights,
+                                            const cg_rt_camera *cams, int n_frames, const cg_rt_shard *shard,
+                                            void *d_out, size_t frame_stride, int pix_format, void *stream)
+{
+    if (n_lights < 0 || n_lights > kMaxLights || (n_lights && !lights)) return CG_E_INVALID;
+    return rt_render_frames(c, lights, n_lights, cams, n_frames, shard, d_out, frame_stride, pix_format, stream,
+                            nullptr, nullptr, nullptr, 0, std::max(n_lights, 1));
+}
+
+// Frames first .. first + count - 1 of a call one by one (rt_enqueue), frame f as fill(f, F) sets
+// it.  Large scenes: consecutive frames are dealt round-robin to big_slots() slots, each with its
+// own buffers and stream: independent frames in flight.
+template <class Fill>
+static int rt_enqueue_each(cg_ctx *c, int first, int count, bool big, uint8_t *out, size_t fbytes, hipStream_t st,
+                           uint32_t *d_done, uint32_t *target, Fill fill)
+{
+    const int ns = (count > 1 && big) ? std::min(big_slots(), count) : 1;
+    if (ns > 1) {
+        if (!c->bev_start) CG_TRY(c, hipEventCreateWithFlags(&c->bev_start, hipEventDisableTiming), "slot event");
+        // the other slots start after what the caller queued before this
+        // call (the scene, the lights just uploaded on st)
+        CG_TRY(c, hipEventRecord(c->bev_start, st), "slot event");
+        for (int q = 1; q < ns; ++q) {
+            cg_ctx::ExtraSlot &x = c->xs[q - 1];
+            if (!x.st) {
+                CG_TRY(c, hipStreamCreateWithFlags(&x.st, hipStreamNonBlocking), "slot stream");
+                CG_TRY(c, hipEventCreateWithFlags(&x.done, hipEventDisableTiming), "slot event");
+            }
+            CG_TRY(c, hipStreamWaitEvent(x.st, c->bev_start, 0), "slot wait");
+        }
+    }
+    for (int i = 0; i < count; ++i) {
+        const int f = first + i;
+        RtFrame F;
+        int rc = fill(f, F);
+        if (rc) return rc;
+        const int q = i % ns;
+        hipStream_t fs = q ? c->xs[q - 1].st : st;
+        rc = rt_enqueue(c, F, out + (size_t)f * fbytes, fs, q);
+        if (rc) return rc;
+        if (d_done) {
+            CG_TRY(c, hipStreamWriteValue32(fs, d_done + f, 1u, 0), "frame signal");
+            target[f] = 1u;
+        }
+    }
+    for (int q = 1; q < ns; ++q) {   // the call ends on the caller's stream
+        cg_ctx::ExtraSlot &x = c->xs[q - 1];
+        CG_TRY(c, hipEventRecord(x.done, x.st), "slot event");
+        CG_TRY(c, hipStreamWaitEvent(st, x.done, 0), "slot wait");
+    }
+    return CG_OK;
+}
+
+// cg_rt_render_sequence_device (validated by rt_render_frames; F0: frame 0's shape): the call's
+// lights and per-frame records go to the device once, then each run (sequence_runs) is enqueued --
+// lattice runs kMaxFrameBatch frames a launch over their records, the others frame by frame, each
+// frame with its own region of the uploaded lights.
+static int rt_enqueue_sequence(cg_ctx *c, const RtFrame &F0, const cg_light *lights, int n_lights,
+                               const cg_rt_camera *cams, int n_frames, const cg_rt_shard *shard, uint8_t *out,
+                               size_t stride, size_t fbytes, int pix_format, hipStream_t st)
+{
+    std::vector<int> start, route;
+    int rc = sequence_runs(cams, n_frames, c->n_tris, c->n_sph, n_lights, shard, start, route);
+    if (rc) return rc;
+    // the slot: lights (n_frames x n_lights RtLight), then the records
+    const size_t lbytes = (size_t)n_frames * n_lights * sizeof(RtLight), rbytes = (size_t)n_frames * sizeof(RtFrameRec);
+    const size_t bytes = lbytes + rbytes;
+    if (bytes > c->seq[0].dev.bytes || bytes > c->seq[0].host_bytes) {
+        const size_t grow = bytes + bytes / 2;   // a somewhat longer call later allocates nothing
+        CG_TRY(c, hipDeviceSynchronize(), "drain before resizing sequence slots");
+        for (auto &q : c->seq) {
+            CG_TRY(c, q.dev.ensure(grow), "alloc sequence slot");
+            if (q.host) (void)hipHostFree(q.host);
+            q.host = nullptr;
+            q.host_bytes = 0;
+            CG_TRY(c, hipHostMalloc(&q.host, grow, hipHostMallocDefault), "alloc sequence staging");
+            q.host_bytes = grow;
+            if (!q.up) {
+                CG_TRY(c, hipEventCreateWithFlags(&q.up, hipEventDisableTiming), "sequence event");
+                CG_TRY(c, hipEventCreateWithFlags(&q.done, hipEventDisableTiming), "sequence event");
+                CG_TRY(c, hipEventRecord(q.up, st), "sequence event");
+                CG_TRY(c, hipEventRecord(q.done, st), "sequence event");
+            }
+        }
+    }
+    cg_ctx::SeqSlot &S = c->seq[c->seq_slot];
+    c->seq_slot ^= 1;
+    // the staging memory: free once the slot's previous upload (two calls ago, at the head of that
+    // call's work) is done -- the one host wait of a sequence call: a third call queued with no
+    // wait since the first blocks here until the stream has reached the first call's upload; the
+    // device copy: once that call's kernels are (any stream, no host wait)
+    CG_TRY(c, hipEventSynchronize(S.up), "sequence staging");
+    CG_TRY(c, hipStreamWaitEvent(st, S.done, 0), "sequence slot wait");
+    // from here on the slot is this call's: whatever happens below, `done` is recorded behind what
+    // was enqueued, so that a later call's wait on the slot covers it and nothing more
+    struct Done {
+        hipEvent_t ev;
+        hipStream_t st;
+        ~Done() { (void)hipEventRecord(ev, st); }
+    } done_on_exit{S.done, st};
+    RtLight *hl = (RtLight *)S.host;
+    RtFrameRec *hr = (RtFrameRec *)((uint8_t *)S.host + lbytes);
+    const RtLight *dl = (const RtLight *)S.dev.p;
+    const RtFrameRec *dr = (const RtFrameRec *)((const uint8_t *)S.dev.p + lbytes);
+    for (size_t l = 0; l < (size_t)n_frames * n_lights; ++l) hl[l] = rt_light_of(lights[l]);
+    for (int f = 0; f < n_frames; ++f) {
+        RtFrameRec &r = hr[f];
+        std::memset(&r, 0, sizeof(r));
+        r.cam[0] = cams[f].camera.x; r.cam[1] = cams[f].camera.y; r.cam[2] = cams[f].camera.z; r.cam[3] = cams[f].camera.w;
+        r.focal = cams[f].focal;
+        r.indirect = cams[f].indirect;
+        std::memcpy(r.R, cams[f].R, sizeof(r.R));
+        light_summary(hl + (size_t)f * n_lights, n_lights, r.lmin, r.lmax, r.lc, r.lrho);
+        r.light_off = (uint32_t)((size_t)f * n_lights);
+    }
+    CG_TRY(c, hipMemcpyAsync(S.dev.p, S.host, bytes, hipMemcpyHostToDevice, st), "upload sequence");
+    CG_TRY(c, hipEventRecord(S.up, st), "sequence event");
+    // frame f as rt_enqueue and the lattice launches take it: its shape, the scene, its record
+    auto frame_of = [&](int f, RtFrame &F) -> int {
+        const int e = frame_shape(&cams[f], shard, F);
+        if (e) return e;
+        F.n_tris = F0.n_tris;
+        F.n_sph = F0.n_sph;
+        F.nbound = F0.nbound;
+        F.n_lights = n_lights;
+        for (int k = 0; k < 3; ++k) {
+            F.lmin[k] = hr[f].lmin[k];
+            F.lmax[k] = hr[f].lmax[k];
+            F.lc[k] = hr[f].lc[k];
+        }
+        F.lrho = hr[f].lrho;
+        F.lights = dl + (size_t)f * n_lights;
+        F.out_fmt = pix_format;
+        return CG_OK;
+    };
+    for (size_t r = 0; r < route.size() && !rc; ++r) {
+        const int a = start[r], b = start[r + 1], rt = route[r];
+        const bool lattice = rt == CG_RT_ROUTE_LATTICE || rt == CG_RT_ROUTE_LATTICE_YAW || rt == CG_RT_ROUTE_LIGHTS ||
+                             rt == CG_RT_ROUTE_LIGHTS_YAW;
+        if (!lattice) {
+            rc = rt_enqueue_each(c, a, b - a, c->n_tris > 64, out, fbytes, st, nullptr, nullptr, frame_of);
+            continue;
+        }
+        for (int f0 = a; f0 < b && !rc; f0 += kMaxFrameBatch) {
+            const int nf = std::min(kMaxFrameBatch, b - f0);
+            RtFrame F;
+            if ((rc = frame_of(f0, F))) break;
+            F.lights = dl;   // the records' light_off counts from the call's array
+            bool uniform = true;
+            for (int f = f0 + 1; f < f0 + nf && uniform; ++f)
+                uniform = std::memcmp(&cams[f].focal, &cams[f0].focal, sizeof(float)) == 0 &&
+                          std::memcmp(cams[f].R, cams[f0].R, sizeof(cams[f0].R)) == 0;
+            uint32_t wg = 0;
+            rc = rt_enqueue_lattice_batch(c, F, cams + f0, nf, out + (size_t)f0 * fbytes, stride, st, nullptr, &wg,
+                                          nullptr, 0, dr + f0, uniform, S.up);
+        }
+    }
+    return rc;
 }
 
 namespace cg {
@@ -1286,7 +1538,7 @@ namespace cg {
 // dispatched group after group (cg_dist's chunks, sent as each completes).
 int rt_render_frames(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams, int n_frames,
                      const cg_rt_shard *shard, void *d_out, size_t frame_stride, int pix_format, void *stream,
-                     uint32_t *d_done, uint32_t *target, const int *group_starts, int ngroups)
+                     uint32_t *d_done, uint32_t *target, const int *group_starts, int ngroups, int light_stride)
 {
     if (!c || !d_out || n_frames < 0 || (n_frames && !cams)) return CG_E_INVALID;
     if (pix_format != CG_PIX_ARGB8888 && pix_format != CG_PIX_RGB24) return CG_E_INVALID;
@@ -1304,53 +1556,26 @@ int rt_render_frames(cg_ctx *c, const cg_light *lights, int n_lights, const cg_r
     if (stride < px) return CG_E_INVALID;
     uint8_t *out = (uint8_t *)d_out;
     const size_t fbytes = stride * pix_bytes(pix_format);
+    // light_stride != 0: frame f has its own lights, lights[f * n_lights ..] (cg_rt_render_sequence_device)
+    if (light_stride) return rt_enqueue_sequence(c, F, lights, n_lights, cams, n_frames, shard, out, stride, fbytes,
+                                                 pix_format, st);
     // one batched launch needs the lattice path for every frame, frames that
     // differ only in cameraPos (same focal, R, indirect)
     bool batch = rt_use_lattice(F);
     for (int f = 1; batch && f < n_frames; ++f)
         batch = cams[f].focal == cams[0].focal && cams[f].indirect == cams[0].indirect &&
                 std::memcmp(cams[f].R, cams[0].R, sizeof(cams[0].R)) == 0;
-    if (!batch) {
-        // Large scenes: consecutive frames are dealt round-robin to big_slots()
-        // slots, each with its own buffers and stream: independent frames in flight
-        const int ns = (n_frames > 1 && F.n_tris > 64 && F.cull_primary && F.cull_shadow)
-                           ? std::min(big_slots(), n_frames) : 1;
-        if (ns > 1) {
-            if (!c->bev_start) CG_TRY(c, hipEventCreateWithFlags(&c->bev_start, hipEventDisableTiming), "slot event");
-            // the other slots start after what the caller queued before this
-            // call (the scene, the lights just uploaded on st)
-            CG_TRY(c, hipEventRecord(c->bev_start, st), "slot event");
-            for (int q = 1; q < ns; ++q) {
-                cg_ctx::ExtraSlot &x = c->xs[q - 1];
-                if (!x.st) {
-                    CG_TRY(c, hipStreamCreateWithFlags(&x.st, hipStreamNonBlocking), "slot stream");
-                    CG_TRY(c, hipEventCreateWithFlags(&x.done, hipEventDisableTiming), "slot event");
-                }
-                CG_TRY(c, hipStreamWaitEvent(x.st, c->bev_start, 0), "slot wait");
-            }
-        }
-        for (int f = 0; f < n_frames; ++f) {
-            if (f) {
-                rc = fill_frame(c, lights, n_lights, &cams[f], shard, st, F);
-                if (rc) return rc;
-                F.out_fmt = pix_format;
-            }
-            const int q = f % ns;
-            hipStream_t fs = q ? c->xs[q - 1].st : st;
-            rc = rt_enqueue(c, F, out + (size_t)f * fbytes, fs, q);
-            if (rc) return rc;
-            if (d_done) {
-                CG_TRY(c, hipStreamWriteValue32(fs, d_done + f, 1u, 0), "frame signal");
-                target[f] = 1u;
-            }
-        }
-        for (int q = 1; q < ns; ++q) {   // the call ends on the caller's stream
-            cg_ctx::ExtraSlot &x = c->xs[q - 1];
-            CG_TRY(c, hipEventRecord(x.done, x.st), "slot event");
-            CG_TRY(c, hipStreamWaitEvent(st, x.done, 0), "slot wait");
-        }
-        return CG_OK;
-    }
+    if (!batch)
+        return rt_enqueue_each(c, 0, n_frames, F.n_tris > 64 && F.cull_primary && F.cull_shadow, out, fbytes, st, d_done,
+                               target, [&](int f, RtFrame &Ff) -> int {
+                                   if (f == 0) {   // filled above
+                                       Ff = F;
+                                       return CG_OK;
+                                   }
+                                   const int e = fill_frame(c, lights, n_lights, &cams[f], shard, st, Ff);
+                                   Ff.out_fmt = pix_format;
+                                   return e;
+                               });
     // (A cold call split into a head batch, whose lattice launch runs beside
     // the rest's certificates on a high-priority auxiliary stream, measured
     // slower: 16.0k against 17.2k frames/s for the driver's 20-frame C2 call --
@@ -1454,9 +1679,22 @@ static HostFill *host_black_outside(cg_ctx *c, std::vector<HostFill::Frame> fram
 // dst (frame stride `stride`): the window's columns only (one pitched copy
 // when the frames are contiguous on both sides), or everything.
 static hipError_t download_frames(uint32_t *dst, size_t stride, const uint32_t *src, int W, int H, int nf, int c0,
-                                  int c1, bool window, hipStream_t st)
+                                  int c1, bool window, hipStream_t st, size_t sstride = 0)
 {
-    const size_t px = (size_t)W * H;
+    // sstride: the source's frame stride in pixels (0 = W * H; more when the frames' rows pad to stripes)
+    const size_t px = sstride ? sstride : (size_t)W * H;
+    if (sstride && sstride != (size_t)W * H) {
+        for (int f = 0; f < nf; ++f) {
+            const hipError_t e = window
+                ? (c1 <= c0 ? hipSuccess
+                            : hipMemcpy2DAsync(dst + (size_t)f * stride + c0, (size_t)W * 4, src + (size_t)f * px + c0,
+                                               (size_t)W * 4, (size_t)(c1 - c0) * 4, H, hipMemcpyDeviceToHost, st))
+                : hipMemcpyAsync(dst + (size_t)f * stride, src + (size_t)f * px, (size_t)W * H * 4,
+                                 hipMemcpyDeviceToHost, st);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
     if (!window) {
         if (stride == px) return hipMemcpyAsync(dst, src, (size_t)nf * px * 4, hipMemcpyDeviceToHost, st);
         for (int f = 0; f < nf; ++f) {
@@ -1519,8 +1757,25 @@ extern "C" int cg_rt_render(cg_ctx *c, const cg_light *lights, int n_lights, con
 // destination makes hipMemcpyAsync stage through the runtime's pinned buffers
 // and return only when the copy is done, so issued in the other order the
 // host would hold back the next render.
+static int rt_render_frames_host(cg_ctx *c, const cg_light *lights, int n_lights, int light_stride,
+                                 const cg_rt_camera *cams, int n_frames, uint32_t *argb, size_t frame_stride, int chunk,
+                                 cg_stats *stats);
 extern "C" int cg_rt_render_frames(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
                                    int n_frames, uint32_t *argb, size_t frame_stride, int chunk, cg_stats *stats)
+{
+    return rt_render_frames_host(c, lights, n_lights, 0, cams, n_frames, argb, frame_stride, chunk, stats);
+}
+extern "C" int cg_rt_render_sequence(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
+                                     int n_frames, uint32_t *argb, size_t frame_stride, int chunk, cg_stats *stats)
+{
+    if (n_lights < 0 || n_lights > kMaxLights || (n_lights && !lights)) return CG_E_INVALID;
+    return rt_render_frames_host(c, lights, n_lights, std::max(n_lights, 1), cams, n_frames, argb, frame_stride, chunk,
+                                 stats);
+}
+// light_stride: 0 (common lights), else frame f's lights at lights + f * n_lights
+static int rt_render_frames_host(cg_ctx *c, const cg_light *lights, int n_lights, int light_stride,
+                                 const cg_rt_camera *cams, int n_frames, uint32_t *argb, size_t frame_stride, int chunk,
+                                 cg_stats *stats)
 {
     if (!c || !argb || n_frames < 0 || (n_frames && !cams) || chunk < 0) return CG_E_INVALID;
     if (n_frames == 0) return CG_OK;
@@ -1553,7 +1808,9 @@ extern "C" int cg_rt_render_frames(cg_ctx *c, const cg_light *lights, int n_ligh
             (void)hipStreamSynchronize(c->stream);
         }
     } drain_on_exit{c};
-    for (int k = 0; k < 2; ++k) CG_TRY(c, c->hslot[k].ensure((size_t)ch * px * sizeof(uint32_t)), "alloc frame slots");
+    // a slot's frames: the whole frame's rows in device memory (H padded to its 8-row stripes)
+    const size_t spx = (size_t)cg_rt_shard_rows(H, nullptr) * W;
+    for (int k = 0; k < 2; ++k) CG_TRY(c, c->hslot[k].ensure((size_t)ch * spx * sizeof(uint32_t)), "alloc frame slots");
     const int nchunks = (n_frames + ch - 1) / ch;
     auto download = [&](int j) -> int {
         const int s = j & 1, f0 = j * ch, nf = std::min(ch, n_frames - f0);
@@ -1576,7 +1833,7 @@ extern "C" int cg_rt_render_frames(cg_ctx *c, const cg_light *lights, int n_ligh
             host_black_outside(c, std::move(fr), W, H, a, b);
         }
         CG_TRY(c, download_frames(argb + (size_t)f0 * stride, stride, (const uint32_t *)c->hslot[s].p, W, H, nf, a, b,
-                                  window, c->xfer), "download frames");
+                                  window, c->xfer, spx), "download frames");
         CG_TRY(c, hipEventRecord(c->ev_cdone[s], c->xfer), "copy event");
         return CG_OK;
     };
@@ -1584,8 +1841,9 @@ extern "C" int cg_rt_render_frames(cg_ctx *c, const cg_light *lights, int n_ligh
     for (int j = 0; j < nchunks; ++j) {
         const int s = j & 1, f0 = j * ch, nf = std::min(ch, n_frames - f0);
         if (j >= 2) CG_TRY(c, hipStreamWaitEvent(c->stream, c->ev_cdone[s], 0), "slot wait");   // chunk j - 2 downloaded
-        int rc = rt_render_frames(c, lights, n_lights, cams + f0, nf, nullptr, c->hslot[s].p, px, CG_PIX_ARGB8888,
-                                  c->stream, nullptr, nullptr, nullptr, 0);
+        int rc = rt_render_frames(c, lights && light_stride ? lights + (size_t)f0 * n_lights : lights, n_lights,
+                                  cams + f0, nf, nullptr, c->hslot[s].p, spx, CG_PIX_ARGB8888, c->stream, nullptr, nullptr,
+                                  nullptr, 0, light_stride);
         if (rc) return rc;
         CG_TRY(c, hipEventRecord(c->ev_rdone[s], c->stream), "render event");
         if (j >= 1 && (rc = download(j - 1))) return rc;

@@ -8,7 +8,11 @@
 // arrows, n m = yaw, i o = focal, x = ESC).  The per-pixel loop runs on the
 // GPU through the C-ABI (include/cg_render.h).
 //
-//   raytracer [--width W] [--height H] [--focal F] [--keys KEYS] [--out FILE]
+//   raytracer [--width W] [--height H] [--focal F] [--keys KEYS] [--out FILE] [--batch]
+//
+// --batch: Update() runs over the whole key script first, each frame's globals
+// are recorded, and one cg_rt_render_sequence call renders every frame; the
+// screenshot is the last frame, as without the flag.
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -59,12 +63,10 @@ static void die(int rc, const char *what)
     exit(1);
 }
 
-// skeleton.cpp:104-169: the pixel loop runs in rt_pixel_kernel.
-void Draw(screen *screen)
+// LoadTestModel every frame as the reference does (:113-116); the scene
+// is constant, so it is uploaded to the device once.
+static void UploadScene()
 {
-    memset(screen->buffer, 0, screen->height * screen->width * sizeof(uint32_t));
-    // LoadTestModel every frame as the reference does (:113-116); the scene
-    // is constant, so it is uploaded to the device once.
     static bool uploaded = false;
     vector<rt::Triangle> triangles;
     vector<rt::Sphere> spheres;
@@ -77,6 +79,11 @@ void Draw(screen *screen)
         if (rc) die(rc, "cg_rt_set_scene");
         uploaded = true;
     }
+}
+
+// the globals as Draw hands them to the library
+static cg_rt_camera CurrentCamera(const screen *screen)
+{
     cg_rt_camera cam;
     cam.width = screen->width;
     cam.height = screen->height;
@@ -84,6 +91,15 @@ void Draw(screen *screen)
     cam.camera = cg_vec4{cameraPos.x, cameraPos.y, cameraPos.z, cameraPos.w};
     memcpy(cam.R, R.data(), sizeof(cam.R));
     cam.indirect = 0.5f;                                              // :110
+    return cam;
+}
+
+// skeleton.cpp:104-169: the pixel loop runs in rt_pixel_kernel.
+void Draw(screen *screen)
+{
+    memset(screen->buffer, 0, screen->height * screen->width * sizeof(uint32_t));
+    UploadScene();
+    const cg_rt_camera cam = CurrentCamera(screen);
     int rc = cg_rt_render(g_ctx, reinterpret_cast<const cg_light *>(lights.data()),
                           (int)lights.size(), &cam, screen->buffer, nullptr);
     if (rc) die(rc, "cg_rt_render");
@@ -129,8 +145,15 @@ bool Update()
 int main(int argc, char *argv[])
 {
     string out = "screenshot.bmp";
-    for (int i = 1; i + 1 < argc; i += 2) {
+    bool batch = false;
+    for (int i = 1; i < argc; i += 2) {
         string a = argv[i];
+        if (a == "--batch") {
+            batch = true;
+            --i;
+            continue;
+        }
+        if (i + 1 >= argc) break;
         if (a == "--width") SCREEN_WIDTH = atoi(argv[i + 1]);
         else if (a == "--height") SCREEN_HEIGHT = atoi(argv[i + 1]);
         else if (a == "--focal") focalLength = (float)atof(argv[i + 1]);
@@ -144,9 +167,29 @@ int main(int argc, char *argv[])
     light1.position = vec4(0, -0.5, -0.7, 1.0);
     light1.colour = 14.f * vec3(1, 1, 1);
     lights.push_back(light1);
-    while (Update()) {
-        Draw(screen);
-        SDL_Renderframe(screen);
+    if (batch) {
+        // the main loop's frames in one call: each Update()'s globals recorded, then every Draw()
+        vector<cg_rt_camera> cams;
+        vector<Light> seq;   // frame-major, lights.size() per frame
+        while (Update()) {
+            cams.push_back(CurrentCamera(screen));
+            seq.insert(seq.end(), lights.begin(), lights.end());
+        }
+        if (!cams.empty()) {
+            UploadScene();
+            const size_t px = (size_t)screen->width * screen->height;
+            vector<uint32_t> frames(cams.size() * px);
+            rc = cg_rt_render_sequence(g_ctx, reinterpret_cast<const cg_light *>(seq.data()), (int)lights.size(),
+                                       cams.data(), (int)cams.size(), frames.data(), 0, 0, nullptr);
+            if (rc) die(rc, "cg_rt_render_sequence");
+            memcpy(screen->buffer, frames.data() + (cams.size() - 1) * px, px * sizeof(uint32_t));
+            SDL_Renderframe(screen);
+        }
+    } else {
+        while (Update()) {
+            Draw(screen);
+            SDL_Renderframe(screen);
+        }
     }
     SDL_SaveImage(screen, out.c_str());
     KillSDL(screen);

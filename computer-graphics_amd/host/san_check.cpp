@@ -179,6 +179,30 @@ int main(int argc, char **argv)
                         if (cg_rt_route(&rc, nt, 1, nl, &sh) < 0) fail("cg_rt_route", -1);
         }
     }
+    {
+        // a sequence's runs (host-only): route changes, every cap from none to more than the runs,
+        // the output arrays exactly cap and cap + 1 long
+        std::vector<cg_rt_camera> seq(9);
+        for (size_t f = 0; f < seq.size(); ++f) {
+            cg_rt_camera &c = seq[f];
+            c = cg_rt_camera{};
+            c.width = 1920; c.height = 1080; c.focal = 1080.0f + 10.0f * (float)f;
+            c.camera = cg_vec4{0, 0, -3, 1};
+            for (int k = 0; k < 16; ++k) c.R[k] = (k % 5 == 0) ? 1.0f : 0.0f;
+            if (f % 3 == 1) { c.R[0] = 0.98f; c.R[2] = -0.17f; c.R[8] = 0.17f; c.R[10] = 0.98f; }
+            if (f == 5) c.R[5] = 0.9f;
+            c.indirect = 0.5f;
+        }
+        for (int nt : {28, 1000000})
+            for (int cap = 0; cap <= 10; ++cap) {
+                std::vector<int> start((size_t)cap + 1), route((size_t)cap);
+                const int runs = cg_rt_sequence_runs(seq.data(), (int)seq.size(), nt, 1, 1, nullptr, start.data(),
+                                                     cap ? route.data() : nullptr, cap);
+                if (runs < 1 || runs > (int)seq.size()) fail("cg_rt_sequence_runs", runs);
+            }
+        if (cg_rt_sequence_runs(seq.data(), -1, 28, 1, 1, nullptr, nullptr, nullptr, 0) != CG_E_INVALID)
+            fail("cg_rt_sequence_runs accepted n_frames < 0", -1);
+    }
     cg_light centre{{0, -0.5f, -0.7f, 1}, {14, 14, 14}}, area[64];
     if (int rc = cg_rt_area_lights(&centre, 0.1f, 8, area, 64); rc < 0) fail("cg_rt_area_lights", rc);
     std::vector<int32_t> r(4096);

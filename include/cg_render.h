@@ -214,6 +214,34 @@ enum {
     CG_RT_ROUTE_BIG_LATTICE_YAW = 7
 };
 int cg_rt_route(const cg_rt_camera *cam, int n_tris, int n_spheres, int n_lights, const cg_rt_shard *shard);
+/* n_frames successive Draw()s as the main loop makes them after any keys of Update()
+ * (skeleton.cpp:192-256): frame f with camera cams[f] and lights
+ * lights[f * n_lights .. f * n_lights + n_lights - 1]; n_lights is common
+ * (0 <= n_lights <= 4096; lights may be NULL when it is 0), width/height common.
+ * Frame f equals cg_rt_render_device(ctx, lights + f * n_lights, n_lights, &cams[f], shard, ...).
+ * Output, shard, frame_stride, pix_format, stream as cg_rt_render_frames_device.
+ * The lights and a per-frame table (cameraPos, focal, indirect, R, the light-set
+ * summary) are uploaded once per call; consecutive frames on the same lattice route
+ * (cg_rt_sequence_runs) share launches of up to 32 frames whatever they differ in.
+ * Calls may be queued back to back without a synchronise between them: two calls in flight keep
+ * their own lights and tables.  A third call issued while the first call's upload has not yet run
+ * (it is the first thing that call enqueues) blocks the host until it has; apart from that, and
+ * after the first call of a size, a call neither allocates nor waits for the device. */
+int cg_rt_render_sequence_device(cg_ctx *ctx, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
+                                 int n_frames, const cg_rt_shard *shard, void *d_out, size_t frame_stride,
+                                 int pix_format, void *stream);
+/* Host-memory form, pipelined like cg_rt_render_frames (chunks render while the previous chunk downloads). */
+int cg_rt_render_sequence(cg_ctx *ctx, const cg_light *lights, int n_lights, const cg_rt_camera *cams, int n_frames,
+                          uint32_t *argb, size_t frame_stride, int chunk, cg_stats *stats);
+/* Host-only (no device work): how a sequence is launched.  Consecutive frames on the same route
+ * (CG_RT_ROUTE_*; size, shard and light count are the call's) form a run; run r covers frames
+ * run_start[r] .. run_start[r+1]-1 and takes run_route[r].  Writes min(runs, cap) runs: run_route
+ * holds cap entries, run_start cap + 1 (the entry after the last written run closes it).  Frames
+ * of a lattice run may differ in cameraPos, focal, indirect, the yaw angle and every light; a
+ * change of route (unrotated <-> yawed, lattice <-> per-pixel) ends the run.  Returns the number
+ * of runs (may exceed cap: the caller re-sizes) or CG_E_INVALID. */
+int cg_rt_sequence_runs(const cg_rt_camera *cams, int n_frames, int n_tris, int n_spheres, int n_lights,
+                        const cg_rt_shard *shard, int *run_start, int *run_route, int cap);
 /* Reassemble a frame from gathered shards: d_gathered holds nranks blocks of
  * cg_rt_shard_rows() rows each, in rank order. */
 int cg_rt_unstripe_device(cg_ctx *ctx, const uint32_t *d_gathered, int width, int height,
