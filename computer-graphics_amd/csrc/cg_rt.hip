@@ -10,6 +10,7 @@
 #include <float.h>
 #include <stdlib.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "cg_rt_dev.h"
@@ -986,7 +987,6 @@ constexpr int kLatWY = 3 * kLatTileW;   // per-pixel columns (a yawed camera): 4
 #ifndef CG_LAT_SOA
 #define CG_LAT_SOA 1   // per-pixel-column lattice: point values and hit indices in separate LDS arrays (A/B: 0)
 #endif
-constexpr int kLatSoaNoHit = -128;   // int8 hit index of a miss (hits: -kLatMaxSph .. 62)
 
 // Shared pieces of the two lattice kernels.
 //
@@ -1026,6 +1026,114 @@ __device__ __forceinline__ vec3 lat_normal(const LatObj *s_obj, int bi, vec3 pos
     if (bi >= 0) return v3(o.x, o.y, o.z);
     return normalize(pos - v3(o.x, o.y, o.z));
 }
+// The one-light lattice kernel's table: per slot the normal (sphere: centre) and the two
+// products every hit on the object uses -- colour * lc, the left factor of :412 as
+// direct_light_lit writes it ((objColor * lc) * a), and colour * indirect, the term of :156.
+// Each is the float multiply of the same operands the per-point code did, formed once per
+// object and workgroup, so every product is bit-identical.  Slot kLatZeroSlot is "no hit":
+// ambient product (+0, +0, +0).  A lattice point carries its slot through LDS as `enc`, the
+// byte offset of the slot's entry (shared columns, in .w of the point's float4: the table
+// reads need no address arithmetic) or the slot number (per-pixel columns, the int8 array;
+// normal and lit product in 12 bytes each so that seven workgroups still fit a CU's LDS).
+// Beside it the frame's light position: pass 2 reads it with a broadcast LDS read instead of
+// a global load per chunk.
+#ifndef CG_LAT_LIGHT_LDS
+#define CG_LAT_LIGHT_LDS 1   // pass 2 reads the light's position from the table (A/B: 0, from global memory)
+#endif
+constexpr int kLatZeroSlot = kLatSphSlot + kLatMaxSph, kLatSlots = kLatZeroSlot + 1;
+struct LatVec3 {
+    float x, y, z;
+};
+template <bool PACKED>
+struct LatTab {
+    using V = std::conditional_t<PACKED, LatVec3, float4>;
+    static constexpr int kEnc = PACKED ? 1 : (int)sizeof(V);   // enc = slot * kEnc
+    float4 amb[kLatSlots];   // 16 bytes in both forms: one aligned read per sample of the pixel sums
+    // nrm and lit are read in pass 2 only; the RGB24 staging of lat_store, written after the
+    // barrier that ends pass 2, lies over them
+    union {
+        struct {
+            V nrm[kLatSlots], lit[kLatSlots];
+        };
+        uint32_t px[kLatTileH * kLatTileW];
+    };
+    float lpos[3];
+    template <class E>
+    __device__ __forceinline__ static vec3 at(const E *a, int enc)
+    {
+        const E v = PACKED ? a[enc] : *(const E *)((const char *)a + enc);
+        return v3(v.x, v.y, v.z);
+    }
+    __device__ __forceinline__ static V mk(float x, float y, float z)
+    {
+        if constexpr (PACKED) return V{x, y, z};
+        else return make_float4(x, y, z, 0.0f);
+    }
+    // by every thread of the workgroup, before a barrier; F: the frame's own record installed
+    __device__ __forceinline__ void load(const RtFrame &F, const RtShade *__restrict__ shade,
+                                         const RtSphere *__restrict__ sph)
+    {
+        const int t = threadIdx.x;
+        const RtLight Lt = F.lights[0];
+        vec3 n, c;
+        bool have = false;
+        if (t < F.n_tris) {
+            const RtShade h = shade[t];
+            n = v3(h.nx, h.ny, h.nz);
+            c = v3(h.cr, h.cg, h.cb);
+            have = true;
+        } else if (t >= kLatSphSlot && t < kLatSphSlot + F.n_sph) {
+            const RtSphere S = sph[t - kLatSphSlot];
+            n = v3(S.cx, S.cy, S.cz);
+            c = v3(S.cr, S.cg, S.cb);
+            have = true;
+        }
+        if (have) {
+            const vec3 l = c * v3(Lt.r, Lt.g, Lt.b);                        // :412's objColor * lc
+            const vec3 a = c * v3(F.indirect, F.indirect, F.indirect);      // :156
+            nrm[t] = mk(n.x, n.y, n.z);
+            lit[t] = mk(l.x, l.y, l.z);
+            amb[t] = make_float4(a.x, a.y, a.z, 0.0f);
+        } else if (t == kLatZeroSlot) {
+            amb[t] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            lpos[0] = Lt.x;
+            lpos[1] = Lt.y;
+            lpos[2] = Lt.z;
+        }
+    }
+};
+// closest_primary_n's hits named by enc (the values are workgroup-uniform: no per-ray arithmetic);
+// a ray that hit nothing gets the zero slot and t = 0
+template <int KENC>
+struct HitSlot {
+    static constexpr int none = kLatZeroSlot * KENC;
+    static constexpr bool zero_t = true;
+    __device__ __forceinline__ static int tri(int k) { return k * KENC; }
+    __device__ __forceinline__ static int sph(int q) { return (kLatSphSlot + q) * KENC; }
+};
+// DirectLight (skeleton.cpp:366-415) of the frame's one light for a hit at pos on the object of
+// enc, from the table; otherwise lat_direct_light below
+template <bool PACKED>
+__device__ __forceinline__ vec3 lat_direct_light_tab(const RtFrame &Fs, const RtTri *__restrict__ tc,
+                                                     const RtSphere *__restrict__ sph, const LatTab<PACKED> &T,
+                                                     int enc, vec3 pos, unsigned long long smask)
+{
+    using Tab = LatTab<PACKED>;
+    cg_work(W_DL);
+#if CG_LAT_LIGHT_LDS
+    const vec3 lp = v3(T.lpos[0], T.lpos[1], T.lpos[2]);
+#else
+    const vec3 lp = v3(Fs.lights[0].x, Fs.lights[0].y, Fs.lights[0].z);
+#endif
+    const vec3 r = lp - pos;                                            // :370
+    const float rmag = light_rmag(r);                                   // :371
+    const vec3 o = Tab::at(T.nrm, enc);                                 // :377-387
+    const vec3 normal = enc < kLatSphSlot * Tab::kEnc ? o : normalize(pos - o);
+    const vec3 origin = pos + normal * 0.00001f;                        // :394
+    if (shadowed<true>(Fs, tc, sph, origin, r, rmag, smask)) return v3(0.0f, 0.0f, 0.0f);   // :394-398
+    return direct_light_lit_pre<false>(r, rmag, normal, Tab::at(T.lit, enc));
+}
+
 // DirectLight (skeleton.cpp:366-415) of light Lt for a hit on bi at pos, the
 // shadow ray walking the candidates of smask (as direct_light<true>)
 template <bool SHARED = false>
@@ -1101,7 +1209,8 @@ __device__ __forceinline__ void lat_store(const RtFrame &F, const LatTile &G, co
 // ray (rt_tile_cert_kernel: t > 0, u, v inside, nothing else can be hit), so
 // the reference's closest hit is k with t = detT / det (:306), formed with
 // closest_primary_n's float ops; the u, v tests and the distance are not needed.
-template <int PITCH, class Store, int NP = 2>
+// Code: the hits' names given to store (closest_primary_n).
+template <int PITCH, class Store, int NP = 2, class Code = HitIndex>
 __device__ __forceinline__ void lat_closest(const RtFrame &Fp, const RtTri *__restrict__ tc,
                                             const RtSphere *__restrict__ sph, unsigned long long mask, bool covered,
                                             const LatTile &G, int p_lo, int p_hi, int lane, Store store,
@@ -1136,10 +1245,10 @@ __device__ __forceinline__ void lat_closest(const RtFrame &Fp, const RtTri *__re
                 const float Q1 = nd.y * c.e1z - c.e1y * nd.z;
                 const float det = (nd.x * c.K1 - c.e1x * Q2) + c.e2x * Q1;   // :289
                 t[n] = c.detT / det;                                         // :306
-                bi[n] = k;
+                bi[n] = Code::tri(k);
             }
         } else {
-            closest_primary_n<NP>(Fp, tc, sph, X, Y, live, mask, bi, t, wc);   // :140
+            closest_primary_n<NP, Code>(Fp, tc, sph, X, Y, live, mask, bi, t, wc);   // :140
         }
 #pragma unroll
         for (int n = 0; n < NP; ++n)
@@ -1324,18 +1433,21 @@ __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__r
     G.yaw = PITCH != kLatW;   // the launch's choice (lat_yaw), a constant here
     lat_store_outside(F, G, o, S.bx);
     const int ay0 = G.ay0, cols = G.cols, rows = G.rows;
-    // per lattice point: .w = hit index bits (INT_MIN: no hit); .x = t after
-    // pass 1, .xyz = DirectLight after pass 2 (one ds_read_b128 per sample).
-    // Per-pixel columns (PITCH 48, CG_LAT_SOA): the three values and the hit
-    // index (int8, kLatSoaNoHit: none) in separate arrays, 13 bytes a point
-    // instead of 16, so that seven workgroups fit a CU's LDS instead of five.
+    // per lattice point: .w = the hit object's table slot (enc; the zero slot: no hit);
+    // .x = t after pass 1 (0: no hit), .xyz = DirectLight after pass 2 (one
+    // ds_read_b128 per sample).
+    // Per-pixel columns (PITCH 48, CG_LAT_SOA): (x, y), z and the slot (int8) in
+    // separate arrays, 13 bytes a point instead of 16, so that seven workgroups
+    // fit a CU's LDS instead of five.
     constexpr bool kSoA = CG_LAT_SOA && PITCH == kLatWY;
+    using Tab = LatTab<kSoA>;
+    constexpr int kNoHit = kLatZeroSlot * Tab::kEnc;
     __shared__ float4 s_pt[kSoA ? 1 : PITCH * kLatH];
-    __shared__ float s_v[kSoA ? 3 : 1][kSoA ? PITCH * kLatH : 1];
+    __shared__ float2 s_xy[kSoA ? PITCH * kLatH : 1];
+    __shared__ alignas(16) float s_z[kSoA ? PITCH * kLatH : 1];
     __shared__ int8_t s_h[kSoA ? PITCH * kLatH : 1];
-    __shared__ LatObj s_obj[kLatSphSlot + kLatMaxSph];
-    __shared__ uint32_t s_px[kLatTileH * kLatTileW];
-    lat_load_objs(s_obj, shade, sph, F.n_tris, F.n_sph);
+    __shared__ Tab s_tab;
+    s_tab.load(F, shade, sph);
     // the needed points, walked row-major at the full pitch; wave w takes the
     // w-th quarter
     const int npts = PITCH * rows;
@@ -1416,19 +1528,27 @@ __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__r
         lat_store_black(F, G, o);
         return;                            // the whole workgroup (m0 is uniform)
     }
-    __syncthreads();                       // s_obj
-    auto stt = [&](int p, float t, int bi) {
+    // a point that missed keeps the value (0, 0, 0) and the zero slot to the end: pass 1 stores
+    // (t, 0) = (0, 0) for it; the separate z array is zeroed here, 16 bytes a store
+    if constexpr (kSoA) {
+        static_assert((PITCH * kLatH) % 4 == 0, "whole 16-byte units");
+        float4 *z = (float4 *)s_z;
+        for (int i = threadIdx.x; i < PITCH * kLatH / 4; i += kRtThreads) z[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    __syncthreads();                       // s_tab, the zeroed values
+    using Hit = HitSlot<Tab::kEnc>;
+    auto stt = [&](int p, float t, int enc) {
         if constexpr (kSoA) {
-            s_v[0][p] = t;
-            s_h[p] = (int8_t)(bi == INT_MIN ? kLatSoaNoHit : bi);
+            s_xy[p] = make_float2(t, 0.0f);
+            s_h[p] = (int8_t)enc;
         } else {
-            s_pt[p] = make_float4(t, 0.0f, 0.0f, __int_as_float(bi));
+            s_pt[p] = make_float4(t, 0.0f, 0.0f, __int_as_float(enc));
         }
     };
     if constexpr (kNP4)
-        lat_closest<PITCH, decltype(stt), 4>(Fp, tc, sph, mask, covered, G, p_lo, p_hi, lane, stt, step1, 256);
+        lat_closest<PITCH, decltype(stt), 4, Hit>(Fp, tc, sph, mask, covered, G, p_lo, p_hi, lane, stt, step1, 256);
     else
-        lat_closest<PITCH>(Fp, tc, sph, mask, covered, G, p_lo, p_hi, lane, stt, step1);
+        lat_closest<PITCH, decltype(stt), 2, Hit>(Fp, tc, sph, mask, covered, G, p_lo, p_hi, lane, stt, step1);
     // Pass 2: DirectLight of each lattice ray that hit (:151-153); shading
     // attributes from the LDS table
     for (int pc = 0; p_lo + pc < p_hi; pc += 64) {
@@ -1438,15 +1558,14 @@ __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__r
         const int p = p0 + lane;
         const int cy = p / PITCH, cx = p - cy * PITCH, idx = p;
         float t = 0.0f;
-        int bi = INT_MIN;
+        int enc = kNoHit;
         if (p < p_hi && cx < cols) {
             if constexpr (kSoA) {
-                const int h = s_h[idx];
-                bi = h == kLatSoaNoHit ? INT_MIN : h;
-                t = s_v[0][idx];
+                enc = s_h[idx];
+                t = s_xy[idx].x;
             } else {
                 const float4 q = s_pt[idx];
-                bi = __float_as_int(q.w);
+                enc = __float_as_int(q.w);
                 t = q.x;
             }
         }
@@ -1455,62 +1574,73 @@ __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__r
         unsigned long long cmask = smask;
         if (objt) {
             unsigned long long cm = 0ull;
-            for (unsigned long long pend = __ballot(bi != INT_MIN); pend;) {
-                const int b = __builtin_amdgcn_readlane(bi, __builtin_ctzll(pend));
-                int sl = b < 0 ? kObjTri : __popcll(mask & ((1ull << b) - 1ull));
-                if (b >= 0 && sl >= kObjTri) sl = kObjSlots;   // a lane that holds the tile's mask
+            for (unsigned long long pend = __ballot(enc != kNoHit); pend;) {
+                const int e = __builtin_amdgcn_readlane(enc, __builtin_ctzll(pend));
+                const int b = e / Tab::kEnc;   // slot b < kLatSphSlot: triangle b
+                const bool tri = b < kLatSphSlot;
+                int sl = !tri ? kObjTri : __popcll(mask & ((1ull << b) - 1ull));
+                if (tri && sl >= kObjTri) sl = kObjSlots;   // a lane that holds the tile's mask
                 const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(vobj >> 32), sl);
                 const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)vobj, sl);
                 cm |= ((unsigned long long)hi << 32) | lo;
-                pend &= ~__ballot(bi == b);
+                pend &= ~__ballot(enc == e);
             }
             cmask = cm & ~(1ull << 63);
             Fs.n_sph = (cm >> 63) ? F.n_sph : 0;
         }
-        if (bi != INT_MIN) {
+        if (enc != kNoHit) {
             const float X = lat_x(F, G, cx), Y = 0.5f * (float)(ay0 + cy);
             const vec3 pos = v3(F.cam[0] + t * X, F.cam[1] + t * Y, F.cam[2] + t * F.focal);
-            const vec3 dl = lat_direct_light(Fs, tc, sph, s_obj, F.lights[0], bi, pos, cmask);
+            const vec3 dl = lat_direct_light_tab(Fs, tc, sph, s_tab, enc, pos, cmask);
             if constexpr (kSoA) {
-                s_v[0][idx] = dl.x;
-                s_v[1][idx] = dl.y;
-                s_v[2][idx] = dl.z;
+                s_xy[idx] = make_float2(dl.x, dl.y);
+                s_z[idx] = dl.z;
             } else {
-                s_pt[idx] = make_float4(dl.x, dl.y, dl.z, __int_as_float(bi));
+                s_pt[idx] = make_float4(dl.x, dl.y, dl.z, __int_as_float(enc));
             }
         }
     }
     __syncthreads();
-    // Pixels: the nine contributions in the reference's order (:134-166)
+    // Pixels: the nine contributions in the reference's order (:134-166).  Every point a pixel
+    // reads holds (DirectLight, slot) -- a miss (0, 0, 0) and the zero slot -- so the sums test
+    // nothing.  The reference adds nothing for a sub-ray that missed; here +0 is added twice,
+    // which is an identity: x + (+0) = x for every float x but -0 (infinities and NaN
+    // included), pc starts at +0, and a sum is -0 only when both operands are -0, so by
+    // induction pc is never -0.  A pixel none of whose sub-rays hit ends at pc = +0,
+    // div_const(+0, 9, 1/9) is +0 (residual zero keeps q0), and put_pixel of it is the
+    // reference's PutPixelSDL(0, 0, 0) (:160-166), so no `valid` flag is kept either.
     const int tx = threadIdx.x % kLatTileW, ty = threadIdx.x / kLatTileW;
     uint32_t px = 0u;
     if (tx < G.nu && ty < G.nv) {
-        vec3 pc = v3(0.0f, 0.0f, 0.0f);
-        bool valid = false;
-        const vec3 ind = v3(F.indirect, F.indirect, F.indirect);
+        // (x, y) as one packed add: the pair is the aligned low half of each LDS read's registers
+        typedef float f2 __attribute__((ext_vector_type(2)));
+        f2 pxy = {0.0f, 0.0f};
+        float pz = 0.0f;
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
             const int i = k / 3 - 1, j = k % 3 - 1;
             const int idx = (2 * ty + 1 + j) * PITCH + ((G.yaw ? 3 : 2) * tx + 1 + i);
-            int bi;
+            int enc;
             vec3 dl;
             if constexpr (kSoA) {
-                const int h = s_h[idx];
-                bi = h == kLatSoaNoHit ? INT_MIN : h;
-                dl = v3(s_v[0][idx], s_v[1][idx], s_v[2][idx]);
+                enc = s_h[idx];
+                const float2 xy = s_xy[idx];
+                dl = v3(xy.x, xy.y, s_z[idx]);
             } else {
                 const float4 q = s_pt[idx];
-                bi = __float_as_int(q.w);
+                enc = __float_as_int(q.w);
                 dl = v3(q.x, q.y, q.z);
             }
-            if (bi == INT_MIN) continue;
-            valid = true;
-            pc = pc + dl;                                                                 // :151-153
-            pc = pc + (lat_colour(s_obj, bi) * ind);                                      // :156
+            const vec3 am = Tab::at(s_tab.amb, enc);
+            pxy = pxy + f2{dl.x, dl.y};                                                   // :151-153
+            pz = pz + dl.z;
+            pxy = pxy + f2{am.x, am.y};                                                   // :156
+            pz = pz + am.z;
         }
-        px = valid ? put_pixel(div_const(pc, 9.0f, 1.0f / 9.0f)) : put_pixel(v3(0.0f, 0.0f, 0.0f));   // :160-166
+        const vec3 pc = v3(pxy.x, pxy.y, pz);
+        px = put_pixel(div_const(pc, 9.0f, 1.0f / 9.0f));                                 // :160-166
     }
-    lat_store(F, G, o, px, tx, ty, s_px);
+    lat_store(F, G, o, px, tx, ty, s_tab.px);
 }
 
 // ---------------------------------------------------------------------------

@@ -809,7 +809,16 @@ __device__ __forceinline__ int closest_primary(const RtFrame &F, const RtTri *__
 // (X[n], Y[n], focal), traced iff live[n]), triangle-outer: each triangle's
 // constants are loaded once for the N rays and their divides are
 // independent.  Each ray's result equals closest_primary's for it.
-template <int N>
+// Code: how a hit is named in bi -- HitIndex: triangle k as k, sphere q as -1 - q, INT_MIN for
+// none; a caller's own (cg_rt.hip HitSlot) names its table slots, and with zero_t a ray that
+// hit nothing also gets t = 0 (bt of such a ray is otherwise whatever the search left).
+struct HitIndex {
+    static constexpr int none = INT_MIN;
+    static constexpr bool zero_t = false;
+    __device__ __forceinline__ static int tri(int k) { return k; }
+    __device__ __forceinline__ static int sph(int q) { return -1 - q; }
+};
+template <int N, class Code = HitIndex>
 __device__ __forceinline__ void closest_primary_n(const RtFrame &F, const RtTri *__restrict__ tc,
                                                   const RtSphere *__restrict__ sph, const float (&X)[N],
                                                   const float (&Y)[N], const bool (&live)[N],
@@ -825,7 +834,7 @@ __device__ __forceinline__ void closest_primary_n(const RtFrame &F, const RtTri 
         len[n] = length(v3(X[n], Y[n], fz));                  // :307
         best[n] = bound;
         bt[n] = 0.f;
-        bi[n] = INT_MIN;
+        bi[n] = Code::none;
     }
     while (mask != 0ull) {
         const int k = __builtin_ctzll(mask);
@@ -847,7 +856,7 @@ __device__ __forceinline__ void closest_primary_n(const RtFrame &F, const RtTri 
             if (tri_accept(c.detT, det, len[n], best[n], uvf, t, distance, wc)) {
                 best[n] = distance;
                 bt[n] = t;
-                bi[n] = k;
+                bi[n] = Code::tri(k);
             }
         }
     }
@@ -863,13 +872,16 @@ __device__ __forceinline__ void closest_primary_n(const RtFrame &F, const RtTri 
             if (live[n] && sphere_intersect_pre(L, cq, v3(X[n], Y[n], fz), t) && t < best[n]) {
                 best[n] = t;
                 bt[n] = t;
-                bi[n] = -1 - q;
+                bi[n] = Code::sph(q);
             }
         }
     }
 #pragma unroll
     for (int n = 0; n < N; ++n)
-        if (!(best[n] < bound)) bi[n] = INT_MIN;                  // :357
+        if (!(best[n] < bound)) {                                 // :357
+            bi[n] = Code::none;
+            if (Code::zero_t) bt[n] = 0.f;
+        }
 }
 
 // ClosestIntersection for a group of NI x NJ camera sub-rays of one pixel
@@ -1050,6 +1062,18 @@ __device__ __forceinline__ vec3 div3_by(vec3 x, float d)
 
 // DirectLight's lit branch (skeleton.cpp:400-412): r = light - pos, rmag its
 // FP64 magnitude (:370-371), normal at the hit (:377-387).
+// direct_light_lit_pre: with litColour = objColor * lc, :412's left factor, given (a caller
+// with one light forms it once per object).
+template <bool SHARED = false>
+__device__ __forceinline__ vec3 direct_light_lit_pre(vec3 r, float rmag, vec3 normal, vec3 litColour)
+{
+    vec3 nd = normalize(r);                                              // :400
+    float a = dot(nd, normal);                                           // :403
+    const float b = (float)(4 * M_PI);                                   // :404
+    float area = (float)((double)b * ((double)rmag * (double)rmag));     // :406
+    if (a <= 0) a = 0.f;                                                 // :409
+    return div3_by<SHARED>(litColour * a, area);                         // :412
+}
 template <bool SHARED = false>
 __device__ __forceinline__ vec3 direct_light_lit(const RtLight &Lt, vec3 r, float rmag, vec3 normal,
                                                  vec3 objColor)
