@@ -866,7 +866,9 @@ __global__ __launch_bounds__(256, CG_CERT_WAVES) void rt_tile_cert_seq_kernel(co
 #ifndef CG_LAT_WAVES
 #define CG_LAT_WAVES 6    // A/B: -DCG_LAT_WAVES=n
 #endif
-constexpr int kRtMinWaves = CG_LAT_WAVES;   // waves per SIMD of rt_lattice_kernel (68 VGPRs: 7 fit)
+// waves per SIMD of rt_lattice_kernel, at least (60 and 50 VGPRs: 8 fit; by LDS 8 workgroups
+// per CU at pitch 33, 7 at pitch 48)
+constexpr int kRtMinWaves = CG_LAT_WAVES;
 // The pixel kernel (rotations other than a yaw; no bench configuration) at 5
 // waves per SIMD: 96 VGPRs and no scratch -- 6 spilled 52 B per lane for ~1 %.
 constexpr int kRtPixelWaves = 5;
@@ -1131,7 +1133,7 @@ __device__ __forceinline__ vec3 lat_direct_light_tab(const RtFrame &Fs, const Rt
     const vec3 normal = enc < kLatSphSlot * Tab::kEnc ? o : normalize(pos - o);
     const vec3 origin = pos + normal * 0.00001f;                        // :394
     if (shadowed<true>(Fs, tc, sph, origin, r, rmag, smask)) return v3(0.0f, 0.0f, 0.0f);   // :394-398
-    return direct_light_lit_pre<false>(r, rmag, normal, Tab::at(T.lit, enc));
+    return direct_light_lit_chan(r, rmag, normal, Tab::at(T.lit, enc));
 }
 
 // DirectLight (skeleton.cpp:366-415) of light Lt for a hit on bi at pos, the

@@ -1087,6 +1087,65 @@ __device__ __forceinline__ vec3 direct_light_lit(const RtLight &Lt, vec3 r, floa
     return div3_by<SHARED>((objColor * lc) * a, area);                   // :412
 }
 
+// :412 with one divide per distinct channel (the one-light lattice kernels; the light-set sweep's
+// shared-reciprocal quotients are cheaper than the tests that would skip them: C4 lost 2 %,
+// DESIGN §4 round 9).  The scene's colours have two or three equal channels and the default
+// light is grey, so litColour = objColor * lc mostly holds the same bits in two or all three
+// channels.  The IEEE f32 division
+// (v_div_scale, v_rcp, the FMAs, v_div_fmas, v_div_fixup) is a deterministic function of
+// (numerator bits, denominator bits), and litColour_c * a is a deterministic function of
+// litColour_c's bits (a is one value per lane), so channels whose litColour bits are equal
+// get bit-identical quotients for EVERY input -- zeros of either sign, denormals, infinities
+// and NaN included.  The comparison is on the integer bits, never a float ==, so +0 and
+// -0 stay distinct and a NaN equals only its own bits.  A divide is skipped only when no
+// active lane of the wave needs it (the branches are wave-uniform: no per-lane select); when
+// some lane does, the lanes whose channels are equal compute the identical bits anyway.
+struct ChanShare {
+    bool need_y, z_is_x, z_is_y;
+};
+__device__ __forceinline__ ChanShare chan_share(vec3 litColour)
+{
+    const uint32_t xb = __float_as_uint(litColour.x), yb = __float_as_uint(litColour.y),
+                   zb = __float_as_uint(litColour.z);
+    ChanShare s;
+    s.need_y = __ballot(yb != xb) != 0ull;
+    s.z_is_x = __ballot(zb != xb) == 0ull;
+    s.z_is_y = __ballot(zb != yb) == 0ull;
+    return s;
+}
+// v, pinned to the branch it is written in: to the optimiser a division is one cheap
+// operation, which it would hoist out of a uniform branch and select afterwards (it did, for
+// the y channel); the empty statement cannot be executed speculatively and costs nothing
+__device__ __forceinline__ float kept_branch(float v)
+{
+    asm volatile("" : "+v"(v));
+    return v;
+}
+// x / d per channel, the quotients shared as s says
+__device__ __forceinline__ vec3 div3_by_shared(vec3 x, float d, ChanShare s)
+{
+    vec3 o;
+    o.x = x.x / d;
+    o.y = o.x;
+    if (s.need_y) o.y = kept_branch(x.y) / d;
+    o.z = o.x;
+    if (!s.z_is_x) {
+        o.z = o.y;
+        if (!s.z_is_y) o.z = kept_branch(x.z) / d;
+    }
+    return o;
+}
+// direct_light_lit_pre with the shared quotients; litColour as the lane holds it
+__device__ __forceinline__ vec3 direct_light_lit_chan(vec3 r, float rmag, vec3 normal, vec3 litColour)
+{
+    vec3 nd = normalize(r);                                              // :400
+    float a = dot(nd, normal);                                           // :403
+    const float b = (float)(4 * M_PI);                                   // :404
+    float area = (float)((double)b * ((double)rmag * (double)rmag));     // :406
+    if (a <= 0) a = 0.f;                                                 // :409
+    return div3_by_shared(litColour * a, area, chan_share(litColour));   // :412
+}
+
 // r_magnitude (skeleton.cpp:371): the norm in FP64, rounded to float.
 __device__ __forceinline__ float light_rmag(vec3 r)
 {
