@@ -1037,10 +1037,10 @@ __device__ __forceinline__ vec3 lat_normal(const LatObj *s_obj, int bi, vec3 pos
 // byte offset of the slot's entry (shared columns, in .w of the point's float4: the table
 // reads need no address arithmetic) or the slot number (per-pixel columns, the int8 array;
 // normal and lit product in 12 bytes each so that seven workgroups still fit a CU's LDS).
-// Beside it the frame's light position: pass 2 reads it with a broadcast LDS read instead of
+// Beside it the frame's light position: the shading reads it with a broadcast LDS read instead of
 // a global load per chunk.
 #ifndef CG_LAT_LIGHT_LDS
-#define CG_LAT_LIGHT_LDS 1   // pass 2 reads the light's position from the table (A/B: 0, from global memory)
+#define CG_LAT_LIGHT_LDS 1   // the shading reads the light's position from the table (A/B: 0, from global memory)
 #endif
 constexpr int kLatZeroSlot = kLatSphSlot + kLatMaxSph, kLatSlots = kLatZeroSlot + 1;
 struct LatVec3 {
@@ -1051,8 +1051,8 @@ struct LatTab {
     using V = std::conditional_t<PACKED, LatVec3, float4>;
     static constexpr int kEnc = PACKED ? 1 : (int)sizeof(V);   // enc = slot * kEnc
     float4 amb[kLatSlots];   // 16 bytes in both forms: one aligned read per sample of the pixel sums
-    // nrm and lit are read in pass 2 only; the RGB24 staging of lat_store, written after the
-    // barrier that ends pass 2, lies over them
+    // nrm and lit are read by the shading only; the RGB24 staging of lat_store, written after the
+    // barrier that ends it, lies over them
     union {
         struct {
             V nrm[kLatSlots], lit[kLatSlots];
@@ -1258,6 +1258,47 @@ __device__ __forceinline__ void lat_closest(const RtFrame &Fp, const RtTri *__re
     }
 }
 
+// One step of lat_closest with its results left in registers (rt_lattice_kernel shades them
+// from there): the step's points p0 + ray_stride * n + lane -- pp, live, the ray (X, Y, focal)
+// -- and their closest hits (t, bi), by the same statements; t and bi of a point that is not
+// live mean nothing.
+template <int PITCH, int NP, class Code>
+__device__ __forceinline__ void lat_closest_step(const RtFrame &Fp, const RtTri *__restrict__ tc,
+                                                 const RtSphere *__restrict__ sph, unsigned long long mask,
+                                                 bool covered, const LatTile &G, int p0, int p_hi, int lane,
+                                                 int ray_stride, bool wc, int (&pp)[NP], bool (&live)[NP],
+                                                 float (&X)[NP], float (&Y)[NP], float (&t)[NP], int (&bi)[NP])
+{
+#pragma unroll
+    for (int n = 0; n < NP; ++n) {
+        const int p = p0 + ray_stride * n + lane;
+        const int cy = p / PITCH, cx = p - cy * PITCH;
+        pp[n] = p;
+        live[n] = p < p_hi && cx < G.cols;
+        X[n] = lat_x(Fp, G, cx);
+        Y[n] = 0.5f * (float)(G.ay0 + cy);
+    }
+    if (covered) {
+        const int k = __builtin_ctzll(mask);
+        const RtTri c = tc[k];
+#pragma unroll
+        for (int n = 0; n < NP; ++n) {
+            if (wc && live[n]) {   // the t stage of the ray's one candidate
+                cg_work(W_RAY_PRI);
+                cg_work(W_T_PRI);
+            }
+            const vec3 nd = -v3(X[n], Y[n], Fp.focal);
+            const float Q2 = nd.y * c.e2z - c.e2y * nd.z;
+            const float Q1 = nd.y * c.e1z - c.e1y * nd.z;
+            const float det = (nd.x * c.K1 - c.e1x * Q2) + c.e2x * Q1;   // :289
+            t[n] = c.detT / det;                                         // :306
+            bi[n] = Code::tri(k);
+        }
+    } else {
+        closest_primary_n<NP, Code>(Fp, tc, sph, X, Y, live, mask, bi, t, wc);   // :140
+    }
+}
+
 // A tile no ray of which can hit anything (certified): every pixel is
 // PutPixelSDL(0, 0, 0) = 0x80000000 (:160-166).
 __device__ __forceinline__ void lat_store_black(const RtFrame &F, const LatTile &G, const LatOut &o)
@@ -1434,10 +1475,9 @@ __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__r
     LatTile G = lat_tile(F, bx, by);
     G.yaw = PITCH != kLatW;   // the launch's choice (lat_yaw), a constant here
     lat_store_outside(F, G, o, S.bx);
-    const int ay0 = G.ay0, cols = G.cols, rows = G.rows;
+    const int rows = G.rows;
     // per lattice point: .w = the hit object's table slot (enc; the zero slot: no hit);
-    // .x = t after pass 1 (0: no hit), .xyz = DirectLight after pass 2 (one
-    // ds_read_b128 per sample).
+    // .xyz = DirectLight (one ds_read_b128 per sample).
     // Per-pixel columns (PITCH 48, CG_LAT_SOA): (x, y), z and the slot (int8) in
     // separate arrays, 13 bytes a point instead of 16, so that seven workgroups
     // fit a CU's LDS instead of five.
@@ -1454,10 +1494,9 @@ __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__r
     // w-th quarter
     const int npts = PITCH * rows;
 #if CG_LAT_INTERLEAVE
-    // 64-point chunks dealt round-robin to the four waves (pass 1: pairs of
+    // 64-point chunks dealt round-robin to the four waves (per-pixel columns: pairs of
     // chunks): hits and shadow tests are spatially clustered, so contiguous
-    // quarters leave some waves idle at the barrier.  Pass 2 walks the same
-    // points as the wave's pass 1 (no barrier between them).
+    // quarters leave some waves idle at the barrier.
     // shared columns: four points per lane per step, 256 apart -- the wave's 64-point chunks w,
     // w + 4, w + 8, .. -- each walked triangle's constants loaded once for four rays (lattice
     // kernel 0.930 -> 0.913 ms per 20-frame launch, 66 VGPRs, 90 SGPRs); the per-pixel-column
@@ -1516,61 +1555,39 @@ __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__r
     const unsigned long long s0 = certified ? uniform_u64(lat_masks[2 * tix + 1]) : all;
     const unsigned long long mask = m0 & ~(3ull << 62), smask = s0 & ~(1ull << 63);
     const bool covered = (m0 >> 62) & 1ull;
-    RtFrame Fp = F;                        // pass 1: spheres only where one may be hit
+    RtFrame Fp = F;                        // closest hit: spheres only where one may be hit
     if (!(m0 >> 63)) Fp.n_sph = 0;
-    RtFrame Fs = F;                        // pass 2: spheres only where one may block a shadow ray
+    RtFrame Fs = F;                        // shading: spheres only where one may block a shadow ray
     if (!(s0 >> 63)) Fs.n_sph = 0;
     // per-object shadow masks (rt_tile_cert_kernel's phase 3; obj_tile(): the same condition)
     const unsigned long long *objt =
         (obj_masks && certified && obj_tile(true, m0, s0)) ? obj_masks + tix * kObjSlots : nullptr;
     // lane j < kObjSlots holds slot j, every other lane the tile's mask (candidates past the last
-    // slot): one vector load ahead of pass 1 instead of dependent scalar loads inside pass 2
+    // slot): one vector load ahead of the steps instead of dependent scalar loads inside the shading
     const unsigned long long vobj = (objt && lane < kObjSlots) ? objt[lane] : s0;
     if (m0 == 0ull) {
         lat_store_black(F, G, o);
         return;                            // the whole workgroup (m0 is uniform)
     }
-    // a point that missed keeps the value (0, 0, 0) and the zero slot to the end: pass 1 stores
-    // (t, 0) = (0, 0) for it; the separate z array is zeroed here, 16 bytes a store
-    if constexpr (kSoA) {
-        static_assert((PITCH * kLatH) % 4 == 0, "whole 16-byte units");
-        float4 *z = (float4 *)s_z;
-        for (int i = threadIdx.x; i < PITCH * kLatH / 4; i += kRtThreads) z[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-    __syncthreads();                       // s_tab, the zeroed values
+    __syncthreads();                       // s_tab
     using Hit = HitSlot<Tab::kEnc>;
-    auto stt = [&](int p, float t, int enc) {
-        if constexpr (kSoA) {
-            s_xy[p] = make_float2(t, 0.0f);
-            s_h[p] = (int8_t)enc;
-        } else {
-            s_pt[p] = make_float4(t, 0.0f, 0.0f, __int_as_float(enc));
-        }
-    };
-    if constexpr (kNP4)
-        lat_closest<PITCH, decltype(stt), 4, Hit>(Fp, tc, sph, mask, covered, G, p_lo, p_hi, lane, stt, step1, 256);
-    else
-        lat_closest<PITCH, decltype(stt), 2, Hit>(Fp, tc, sph, mask, covered, G, p_lo, p_hi, lane, stt, step1);
-    // Pass 2: DirectLight of each lattice ray that hit (:151-153); shading
-    // attributes from the LDS table
-    for (int pc = 0; p_lo + pc < p_hi; pc += 64) {
-        // the chunks of this wave's pass 1
-        const int p0 = kNP4 ? p_lo + 4 * pc : p_lo + (pc / 128) * step1 + (pc % 128);
-        if (p0 >= p_hi) break;
-        const int p = p0 + lane;
-        const int cy = p / PITCH, cx = p - cy * PITCH, idx = p;
-        float t = 0.0f;
-        int enc = kNoHit;
-        if (p < p_hi && cx < cols) {
-            if constexpr (kSoA) {
-                enc = s_h[idx];
-                t = s_xy[idx].x;
-            } else {
-                const float4 q = s_pt[idx];
-                enc = __float_as_int(q.w);
-                t = q.x;
-            }
-        }
+    // One pass per point.  A step of the wave finds the closest hits (:140) of its NP chunks of
+    // 64 points as lat_closest does, then shades the chunks in ascending order (:151-153) from
+    // the registers that hold t, the slot and the ray's X, Y, and stores each live point once
+    // as (DirectLight, slot): a miss (0, 0, 0) and the zero slot, a shadowed hit (0, 0, 0) and
+    // its own slot.  The lane that finds a point's hit was already the lane that shaded it; the
+    // point no longer goes through LDS in between, as (t, 0, 0, slot), to be read back and its
+    // column, row, X and Y derived a second time.  Every float operation, its operands and its
+    // order are those of the two passes: t, X and Y are the same values, only kept in registers;
+    // a chunk's ballots run over the same 64 lanes with the same slots (a lane whose point is not
+    // live offers the zero slot, as the read-back left it), so its shadow candidates are the
+    // same, and the chunks of a wave are shaded in the order the second pass took them.  Frames
+    // are bit-identical for every input.  Every live point is stored, with all three components,
+    // so nothing is zeroed beforehand.
+    constexpr int kNP = kNP4 ? 4 : 2, kStride = kNP4 ? 256 : 64;
+    // shading attributes from the LDS table
+    auto shade_pt = [&](int p, bool live, float X, float Y, float t, int hit) {
+        const int enc = live ? hit : kNoHit;
         // the chunk's shadow candidates: the masks of the objects its points hit, ORed (a point
         // needs its own object's; the any-hit walk of a superset gives the same answer)
         unsigned long long cmask = smask;
@@ -1590,17 +1607,31 @@ __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__r
             cmask = cm & ~(1ull << 63);
             Fs.n_sph = (cm >> 63) ? F.n_sph : 0;
         }
+        vec3 dl = v3(0.0f, 0.0f, 0.0f);
         if (enc != kNoHit) {
-            const float X = lat_x(F, G, cx), Y = 0.5f * (float)(ay0 + cy);
             const vec3 pos = v3(F.cam[0] + t * X, F.cam[1] + t * Y, F.cam[2] + t * F.focal);
-            const vec3 dl = lat_direct_light_tab(Fs, tc, sph, s_tab, enc, pos, cmask);
+            dl = lat_direct_light_tab(Fs, tc, sph, s_tab, enc, pos, cmask);
+        }
+        if (live) {
             if constexpr (kSoA) {
-                s_xy[idx] = make_float2(dl.x, dl.y);
-                s_z[idx] = dl.z;
+                s_xy[p] = make_float2(dl.x, dl.y);
+                s_z[p] = dl.z;
+                s_h[p] = (int8_t)enc;
             } else {
-                s_pt[idx] = make_float4(dl.x, dl.y, dl.z, __int_as_float(enc));
+                s_pt[p] = make_float4(dl.x, dl.y, dl.z, __int_as_float(enc));
             }
         }
+    };
+    for (int p0 = p_lo; p0 < p_hi; p0 += step1) {
+        float X[kNP], Y[kNP], t[kNP];
+        bool live[kNP];
+        int pp[kNP], hit[kNP];
+        lat_closest_step<PITCH, kNP, Hit>(Fp, tc, sph, mask, covered, G, p0, p_hi, lane, kStride, true, pp, live, X, Y,
+                                          t, hit);
+#pragma unroll
+        for (int n = 0; n < kNP; ++n)
+            if (p0 + kStride * n < p_hi)   // a chunk past the tile's points has no live lane
+                shade_pt(pp[n], live[n], X[n], Y[n], t[n], hit[n]);
     }
     __syncthreads();
     // Pixels: the nine contributions in the reference's order (:134-166).  Every point a pixel
