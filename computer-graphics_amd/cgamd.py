@@ -104,6 +104,13 @@ _SIGS = {
     "cg_starfield_init": (C.c_int, [P, C.c_int]),
     "cg_starfield_update": (C.c_int, [P, C.c_int, C.c_float]),
     "cg_starfield_draw": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, P]),
+    "cg_starfield_set": (C.c_int, [P, P, C.c_int]),
+    "cg_starfield_get": (C.c_int, [P, P, C.c_int]),
+    "cg_starfield_run_device": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, C.c_int, P, C.c_size_t, P]),
+    "cg_starfield_advance_device": (C.c_int, [P, P, C.c_int, P]),
+    "cg_starfield_run": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, C.c_int, P, C.c_size_t, C.c_int,
+                                   C.POINTER(Stats)]),
+    "cg_starfield_plan": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "cg_rt_area_lights": (C.c_int, [C.POINTER(Light), C.c_float, C.c_int, C.POINTER(Light), C.c_int]),
     "cg_rt_random_scene": (C.c_int, [C.c_uint64, C.c_int, C.POINTER(Tri)]),
     "cg_rt_set_scene": (C.c_int, [P, C.POINTER(Tri), C.c_int, C.POINTER(Sphere), C.c_int]),
@@ -322,6 +329,20 @@ def starfield_update(stars, dt):
     rc = load().cg_starfield_update(stars.ctypes.data_as(C.c_void_p), len(stars), dt)
     if rc:
         raise RuntimeError(f"cg_starfield_update failed: {rc}")
+
+
+def starfield_plan(n_stars, n_frames):
+    """cg_starfield_plan: how a run of n_frames frames is cut (host-only; no GPU needed), as
+    (launches, frames_per_launch, frames_per_block)."""
+    L, B = C.c_int(), C.c_int()
+    n = load().cg_starfield_plan(n_stars, n_frames, C.byref(L), C.byref(B))
+    if n < 0:
+        raise ValueError(f"cg_starfield_plan: {n}")
+    return n, L.value, B.value
+
+
+def _dts(dts):
+    return np.ascontiguousarray(dts, np.float32).reshape(-1)
 
 
 def random_scene(n, seed=0x5EED):
@@ -761,6 +782,66 @@ class Context:
         self._check(self.lib.cg_starfield_draw(self.h, stars.ctypes.data_as(P), len(stars), width, height,
                                                out.ctypes.data_as(P)), "cg_starfield_draw")
         return out
+
+    def starfield_set(self, stars):
+        """cg_starfield_set: (n, 3) float32 stars become the context's resident stars."""
+        st = np.ascontiguousarray(stars, np.float32).reshape(-1, 3)
+        self._check(self.lib.cg_starfield_set(self.h, st.ctypes.data_as(P), len(st)), "cg_starfield_set")
+        self._star_n = len(st)
+
+    def starfield_get(self, cap=None):
+        """cg_starfield_get: the resident stars as (n, 3) float32, after the context's starfield
+        work (cap: capacity offered in stars; None = the count of the latest starfield_set)."""
+        cap = getattr(self, "_star_n", 0) if cap is None else cap
+        out = np.zeros((max(cap, 1), 3), np.float32)
+        n = self.lib.cg_starfield_get(self.h, out.ctypes.data_as(P), cap)
+        if n < 0:
+            self._check(n, "cg_starfield_get")
+        return out[:n].copy()
+
+    def starfield_run_device(self, dts, n_frames, width, height, d_argb, n_updates=None, frame_stride=0,
+                             stream=None):
+        """cg_starfield_run_device: n_frames frames into d_argb + f * frame_stride pixels, frame f
+        after f updates, update f with frame time dts[f] (n_updates: n_frames, the default, or
+        n_frames - 1).  Enqueues only."""
+        n_updates = n_frames if n_updates is None else n_updates
+        d = _dts(dts)
+        if len(d) < n_updates:
+            raise ValueError(f"{n_updates} updates need {n_updates} frame times, got {len(d)}")
+        self._check(self.lib.cg_starfield_run_device(self.h, d.ctypes.data_as(P) if len(d) else None, n_updates,
+                                                     n_frames, width, height, P(d_argb), frame_stride,
+                                                     P(stream) if stream else None), "cg_starfield_run_device")
+
+    def starfield_advance_device(self, dts, stream=None):
+        """cg_starfield_advance_device: one Update per entry of dts, no drawing.  Enqueues only."""
+        d = _dts(dts)
+        self._check(self.lib.cg_starfield_advance_device(self.h, d.ctypes.data_as(P) if len(d) else None, len(d),
+                                                         P(stream) if stream else None),
+                    "cg_starfield_advance_device")
+
+    def starfield_run(self, dts, n_frames, width=320, height=256, n_updates=None, out=None, chunk=0,
+                      frame_stride=0):
+        """cg_starfield_run: the frames of starfield_run_device into host memory `out` (as
+        rt_render_frames: uint32, pageable or pinned, allocated pageable when None)."""
+        n_updates = n_frames if n_updates is None else n_updates
+        d = _dts(dts)
+        if len(d) < n_updates:
+            raise ValueError(f"{n_updates} updates need {n_updates} frame times, got {len(d)}")
+        npx = width * height
+        stride = frame_stride or npx
+        if stride < npx:
+            raise ValueError(f"frame_stride {stride} < W*H = {npx}")
+        if out is None:
+            out = np.zeros(n_frames * stride, np.uint32)
+        need = (n_frames - 1) * stride + npx if n_frames else 0
+        have = (out.nbytes if isinstance(out, np.ndarray) else out.numel() * out.element_size()) // 4
+        if have < need:
+            raise ValueError(f"out holds {have} pixels, {n_frames} frames at stride {stride} need {need}")
+        ptr = out.ctypes.data if isinstance(out, np.ndarray) else out.data_ptr()
+        st = Stats()
+        self._check(self.lib.cg_starfield_run(self.h, d.ctypes.data_as(P) if len(d) else None, n_updates, n_frames,
+                                              width, height, P(ptr), stride, chunk, C.byref(st)), "cg_starfield_run")
+        return out, st
 
     def rast_render(self, tris, n, params, light, want_depth=True, want_shadow=True):
         npx = params.width * params.height

@@ -217,6 +217,37 @@ struct RastTriHdr {
     int pad;
 };
 
+// ---- starfield (cg_starfield.hip) ---------------------------------------
+// Resident stars and frame runs (cg_starfield_set / _run_device / _run).  One launch of
+// star_run_kernel covers up to kStarLaunchFrames frames; a thread draws kStarBlockFrames
+// consecutive frames of one star after replaying the updates before them in registers.
+constexpr int kStarLaunchFrames = 256;
+constexpr int kStarBlockFrames = 8;
+// 0.0005 * (double)dt of each update of a launch (Update :96's right operand, the host's
+// IEEE product), by value: kernarg, read with scalar loads at a launch-uniform index.
+struct StarSteps {
+    double d[kStarLaunchFrames];
+};
+// The context's starfield state, owned by cg_starfield.hip (star_release frees it).  x and y
+// never change; z alternates between two buffers, because a launch's blocks replay from the
+// state before it while its last block stores the state after it.
+struct StarState {
+    int n = -1;                  // resident stars; -1: none set
+    int cap = 0;                 // stars the buffers hold
+    int cur = 0;                 // z[cur] is the resident state once everything enqueued has run
+    float2 *xy = nullptr;
+    float *z[2] = {nullptr, nullptr};
+    hipEvent_t last = nullptr;   // after the latest enqueued starfield work
+    bool pending = false;        // `last` has been recorded
+    // cg_starfield_run (host output): chunks render into two device slots and download on
+    // `xfer` while the next chunk renders
+    hipStream_t xfer = nullptr;
+    hipEvent_t rdone[2] = {nullptr, nullptr}, cdone[2] = {nullptr, nullptr};
+    uint32_t *slot[2] = {nullptr, nullptr};
+    size_t slot_px = 0;
+};
+void star_release(StarState *s);
+
 // ---- live kernel timing (cg_ktime.hip, cg_kernel_timing) ---------------
 enum KtId {
     KT_RT_PREPARE, KT_RT_TILE_CERT, KT_RT_LATTICE_UNITS, KT_RT_LATTICE, KT_RT_LATTICE_LIGHTS, KT_RT_PIXEL,

@@ -278,6 +278,7 @@ struct cg_ctx {
     DevBuf rseq;
     long long rseq_chunks = 0, rand_cap = 0;
     DevBuf sstars, sframe;               // starfield (cg_starfield.hip)
+    StarState star;                      // resident stars and frame runs (cg_starfield.hip)
     DevBuf iscratch;                     // JPEG decode (cg_image.hip)
     int n_room = -1, n_boxes = 0;
     int scene_tex = 0;                   // bit k: the uploaded room/boxes carry texture k
@@ -337,6 +338,7 @@ void *ctx_buf(cg_ctx *c, int which, size_t bytes, hipError_t *e)
     return *e == hipSuccess ? b->p : nullptr;
 }
 hipStream_t ctx_stream(cg_ctx *c) { return c->stream; }
+StarState *ctx_star(cg_ctx *c) { return &c->star; }
 int ctx_device(cg_ctx *c) { return c->device; }
 int ctx_invalid(cg_ctx *c, const char *what)
 {
@@ -469,6 +471,7 @@ extern "C" void cg_destroy(cg_ctx *c)
         if (q.done) (void)hipEventDestroy(q.done);
     }
     rast_release(c);
+    star_release(&c->star);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);

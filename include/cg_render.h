@@ -535,6 +535,36 @@ int cg_starfield_update(float *stars, int n, float dt);
 /* Draw() (:66-79): clear, project each star, PutPixelSDL white; W*H ARGB
  * into the caller-owned host buffer. */
 int cg_starfield_draw(cg_ctx *ctx, const float *stars, int n, int width, int height, uint32_t *argb);
+/* Resident stars: the main loop (:53-57) on the device.  cg_starfield_set uploads n (x, y, z)
+ * triples as the context's stars (n == 0: an empty field), replacing an earlier set after
+ * waiting for the starfield work that still reads it.  cg_starfield_get waits for the
+ * context's starfield work, copies the resident state out and returns n (CG_E_CAPACITY if
+ * cap < n, CG_E_NOSCENE before the first set).  They share nothing with cg_starfield_draw,
+ * which may be interleaved freely. */
+int cg_starfield_set(cg_ctx *ctx, const float *stars, int n);
+int cg_starfield_get(cg_ctx *ctx, float *stars, int cap);
+/* n_frames frames into device memory: frame f is Draw() of the stars after f updates, at
+ * d_argb + f * frame_stride pixels (0 = W * H; pixels between frames are not written), and
+ * update f is Update() with frame time dts[f] (host memory, consumed before the call
+ * returns).  n_updates is n_frames, or n_frames - 1 to draw the last frame without advancing
+ * past it (n_frames 1, n_updates 0: a plain Draw of the resident stars).  Afterwards the
+ * resident stars are the state after n_updates updates.  Enqueues on `stream` (NULL: the
+ * context's) and does not synchronise; calls may be queued back to back on one stream.
+ * Every pixel and every z is bit-identical to cg_starfield_draw / cg_starfield_update run
+ * frame by frame.  CG_E_NOSCENE before cg_starfield_set. */
+int cg_starfield_run_device(cg_ctx *ctx, const float *dts, int n_updates, int n_frames, int width, int height,
+                            uint32_t *d_argb, size_t frame_stride, void *stream);
+/* Update() x n_updates on the resident stars, no drawing; enqueues like the call above. */
+int cg_starfield_advance_device(cg_ctx *ctx, const float *dts, int n_updates, void *stream);
+/* The same frames into caller-owned host memory (pageable or pinned), rendered `chunk` frames
+ * at a time (0 = 8; at most 64): chunk j + 1 renders while chunk j downloads on a second
+ * stream.  Returns once every frame is in host memory. */
+int cg_starfield_run(cg_ctx *ctx, const float *dts, int n_updates, int n_frames, int width, int height,
+                     uint32_t *argb, size_t frame_stride, int chunk, cg_stats *stats);
+/* Host-only: how a run of n_frames frames is cut.  *frames_per_launch: the most frames one
+ * kernel launch covers; *frames_per_block: the consecutive frames one thread draws (either
+ * may be NULL).  Returns the number of launches, or CG_E_INVALID for negative arguments. */
+int cg_starfield_plan(int n_stars, int n_frames, int *frames_per_launch, int *frames_per_block);
 
 #ifdef __cplusplus
 }
