@@ -163,6 +163,11 @@ _SIGS = {
     "cg_rast_draw_frames_device": (C.c_int, [P, C.POINTER(RastParams), C.c_int, P, P, P, C.c_size_t, P]),
     "cg_rast_draw_sequence_device": (C.c_int, [P, C.POINTER(RastParams), C.c_int, P, P, P, C.c_size_t, P, P]),
     "cg_rast_set_rand_capacity": (C.c_int, [P, C.c_longlong]),
+    "cg_rast_route": (C.c_int, [C.c_longlong]),
+    "cg_rast_set_route": (C.c_int, [P, C.c_int]),
+    "cg_rast_scratch_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
+    "cg_rast_row_blocks": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "cg_rast_random_scene": (C.c_int, [C.c_uint64, C.c_int, C.c_float, C.POINTER(RTri)]),
     "cg_glibc_rand_device": (C.c_int, [P, P, C.c_int, P, P]),
     "cg_dist_unique_id": (C.c_int, [P]),
     "cg_dist_create": (C.c_int, [P, C.c_int, C.c_int, P, C.POINTER(P)]),
@@ -352,6 +357,31 @@ def random_scene(n, seed=0x5EED):
     k = lib.cg_rt_random_scene(seed, n, tris)
     if k != n:
         raise RuntimeError(f"cg_rt_random_scene failed: {k}")
+    return tris
+
+
+RAST_ROUTE_DENSE, RAST_ROUTE_COMPACT = 0, 1   # cg_render.h CG_RAST_ROUTE_*
+
+
+def rast_route(list_capacity):
+    """cg_rast_route (host-only): the route a frame of this list capacity takes automatically."""
+    return load().cg_rast_route(list_capacity)
+
+
+def rast_row_blocks():
+    """cg_rast_row_blocks (host-only): (batch, chunk), the block sizes of the compact route's row-list passes."""
+    b, c = C.c_int(), C.c_int()
+    if load().cg_rast_row_blocks(C.byref(b), C.byref(c)) != CG_OK:
+        raise RuntimeError("cg_rast_row_blocks failed")
+    return b.value, c.value
+
+
+def rast_random_scene(n, extent=0.02, seed=0x5EED):
+    """cg_rast_random_scene (host-only): ctypes RTri array of n random triangles."""
+    tris = (RTri * max(n, 1))()
+    k = load().cg_rast_random_scene(seed, n, extent, tris)
+    if k != n:
+        raise RuntimeError(f"cg_rast_random_scene failed: {k}")
     return tris
 
 
@@ -934,6 +964,16 @@ class Context:
             self.h, arr, len(params_list), P(d_argb), P(d_depth) if d_depth else None,
             P(d_shadow) if d_shadow else None, frame_stride, P(d_info) if d_info else None,
             P(stream) if stream else None), "cg_rast_draw_sequence_device")
+
+    def rast_set_route(self, route):
+        """Test and A/B hook: -1 automatic, RAST_ROUTE_DENSE / RAST_ROUTE_COMPACT forced."""
+        self._check(self.lib.cg_rast_set_route(self.h, route), "cg_rast_set_route")
+
+    def rast_scratch_info(self):
+        """Rasteriser scratch after the latest frame (waits for it): dict(bytes, route, tris, spans, recs)."""
+        out = (C.c_uint64 * 5)()
+        self._check(self.lib.cg_rast_scratch_info(self.h, out), "cg_rast_scratch_info")
+        return dict(bytes=out[0], route=out[1], tris=out[2], spans=out[3], recs=out[4])
 
     def rast_set_rand_capacity(self, n):
         """Test hook: fragments the sequence's materialised rand() stream holds (0 = 4 * W * H)."""

@@ -251,7 +251,9 @@ void star_release(StarState *s);
 // ---- live kernel timing (cg_ktime.hip, cg_kernel_timing) ---------------
 enum KtId {
     KT_RT_PREPARE, KT_RT_TILE_CERT, KT_RT_LATTICE_UNITS, KT_RT_LATTICE, KT_RT_LATTICE_LIGHTS, KT_RT_PIXEL,
-    KT_RT_BIG_PRIMARY, KT_RT_SHADOW_HINTS, KT_RT_BIG_FRAME, KT_RAST_FILL, KT_RAST_POST, KT_COUNT
+    KT_RT_BIG_PRIMARY, KT_RT_SHADOW_HINTS, KT_RT_BIG_FRAME, KT_RAST_FILL, KT_RAST_POST,
+    // the compact rasteriser route's phases (cg_rast_big.hip), each a scope over its launches
+    KT_RAST_BIG_CLIP, KT_RAST_BIG_SETUP, KT_RAST_BIG_ROWS, KT_RAST_BIG_FILL, KT_RAST_BIG_POST, KT_COUNT
 };
 // HIP events on `st` around the scope's launches while timing is on (id
 // outside [0, KT_COUNT): nothing).

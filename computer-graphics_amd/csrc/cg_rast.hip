@@ -35,99 +35,7 @@ int ctx_fail(cg_ctx *c, hipError_t e, const char *what);
 int ctx_invalid(cg_ctx *c, const char *what);
 void ctx_events(cg_ctx *c, hipEvent_t *a, hipEvent_t *b);
 
-constexpr int kSetupThreads = 256;
 constexpr int kSetupPreChunks = 16;  // input triangles counted in one round trip: < 64 * 16
-constexpr int kRastMaxRows = 4096;   // LDS rows per triangle in span setup (H <= 4096)
-
-// Workgroups are dispatched round-robin over the 8 XCDs, each with its own L2.
-// The row-ordered kernels renumber them so that each group of kXcdRows rows
-// is handled by one XCD (a row's records are then fetched into one L2, not
-// all eight), with the groups dealt round-robin to keep the XCDs balanced
-// (row cost varies a lot over the frame).  A kernel whose row group is
-// `per_group` workgroups wide launches xcd_grid(H, per_group) of them.
-constexpr int kXcds = 8, kXcdRows = 8;
-__host__ __device__ constexpr int xcd_grid(int H, int per_group)
-{
-    return kXcds * ((((H + kXcdRows - 1) / kXcdRows) + kXcds - 1) / kXcds) * per_group;
-}
-// -> row group of this workgroup (-1: idle padding) and its index m within the group
-__device__ __forceinline__ int xcd_group(int H, int per_group, int &m)
-{
-    const int k = (int)(blockIdx.x % kXcds), l = (int)(blockIdx.x / kXcds);
-    m = l % per_group;
-    const int g = k + kXcds * (l / per_group);
-    return g < (H + kXcdRows - 1) / kXcdRows ? g : -1;
-}
-
-struct Pix {                // rasteriser Pixel (:88-94) minus w
-    int x, y;
-    float zinv, X, Y;
-};
-
-__device__ __forceinline__ Pix vertex_shader(const RastArgs &A, cg_vec4 v)
-{
-    // :512-521
-    float x = (A.focal * (v.x / v.z)) + (float)(A.W / 2);
-    float y = (A.focal * (v.y / v.z)) + (float)(A.H / 2);
-    Pix p;
-    p.x = f2i_x86(x);
-    p.y = f2i_x86(y);
-    p.zinv = 1 / v.z;
-    p.X = v.x;
-    p.Y = v.y;
-    return p;
-}
-
-// Interpolate (:524-551) prepared for one edge a -> b with N samples.
-struct Edge {
-    float ax, ay, az, aX, aY;     // a.x, a.y as float; a.zinv; a.pos3d.xy * a.zinv
-    float stx, sty, stz, sX, sY;
-    int n;
-};
-
-__device__ __forceinline__ Edge make_edge(Pix a, Pix b)
-{
-    Edge e;
-    float aX = a.X * a.zinv, aY = a.Y * a.zinv;   // :526-527
-    float bX = b.X * b.zinv, bY = b.Y * b.zinv;   // :529-530
-    int dx = a.x - b.x, dy = a.y - b.y;
-    dx = dx < 0 ? -dx : dx;
-    dy = dy < 0 ? -dy : dy;
-    e.n = (dx > dy ? dx : dy) + 1;                // :473-475
-    float den = (float)(e.n - 1 > 1 ? e.n - 1 : 1);
-    e.ax = (float)a.x;
-    e.ay = (float)a.y;
-    e.az = a.zinv;
-    e.aX = aX;
-    e.aY = aY;
-    e.stx = (float)(b.x - a.x) / den;             // :533-538
-    e.sty = (float)(b.y - a.y) / den;
-    e.stz = (b.zinv - a.zinv) / den;
-    e.sX = (bX - aX) / den;
-    e.sY = (bY - aY) / den;
-    return e;
-}
-
-__device__ __forceinline__ int edge_x(const Edge &e, int j) { return f2i_x86(floorf(e.ax + (e.stx * (float)j))); }
-__device__ __forceinline__ int edge_y(const Edge &e, int j) { return f2i_x86(floorf(e.ay + (e.sty * (float)j))); }
-
-// sample j's zinv and pos3d.xy (:543-548)
-__device__ __forceinline__ void edge_attr(const Edge &e, int j, float &zinv, float &X, float &Y)
-{
-    float fj = (float)j;
-    zinv = e.az + (e.stz * fj);
-    X = (e.aX + (e.sX * fj)) / zinv;
-    Y = (e.aY + (e.sY * fj)) / zinv;
-}
-
-__device__ __forceinline__ unsigned long long key_left(int x, unsigned seq)
-{
-    return ((unsigned long long)((unsigned)x ^ 0x80000000u) << 32) | (unsigned long long)(~seq);
-}
-__device__ __forceinline__ unsigned long long key_right(int x, unsigned seq)
-{
-    return ((unsigned long long)((unsigned)x ^ 0x80000000u) << 32) | (unsigned long long)seq;
-}
 
 __device__ void rast_setup_one(const cg_rtri &T, const RastArgs &A, RastSpan *__restrict__ spans,
                                RastHdr *__restrict__ hdr, int *__restrict__ first_tri, int t,
@@ -423,20 +331,6 @@ __global__ __launch_bounds__(256) void rast_rows_kernel(const cg_rtri *__restric
     if (lane == 0) count[y] = c;
 }
 
-// Colour mode 0: fill -> post state, 4 bytes per pixel: 1 + the row record of
-// the last shading fragment (0 none) | the shadow mark << 31; 2 bytes (the
-// mark in bit 15) when a row holds fewer than 32768 records (A.state16).  The post-pass
-// rebuilds that fragment from the record -- zinv = lz + sz * i (:543) and the
-// pos3d numerators with the same float ops, the normal, the texels -- and
-// evaluates calculateIllumination there, so the fill keeps only what its
-// ordered walk decides.
-constexpr uint32_t kStShadow = 0x80000000u;
-
-// One wave per kFillPx-pixel row segment, one pixel per lane, state in
-// registers; records walked in triangle order (the reference's ordered
-// z-buffer), one uniform overlap test per record.
-constexpr int kFillPx = 64;   // pixels per wave; 128 / 256 measured 3 % / 10 % slower (C3, round 1)
-
 // TEX: texture modes 1-3 possible (A.textured): a fragment of texture 2/3
 // that passes the depth test but hits a transparent texel sets the depth to 0
 // and shades nothing (:619, :643, :665) -- decided in the ordered walk.
@@ -528,65 +422,6 @@ __global__ __launch_bounds__(256) void rast_fill_kernel(RastArgs A, const RowRec
     }
 }
 
-// shade buffers of one pixel as they stand after the fill (:580-585), from its
-// state and its triangle's colour
-__device__ __forceinline__ void shade3c(const RastArgs &A, float4 st, cg_vec3 col, vec3 &sc, vec3 &lo, vec3 &hi,
-                                        int tex = 0, uint32_t texel = 0u)
-{
-    const int tb = __float_as_int(st.x);
-    if (tb < 0) {
-        sc = lo = hi = v3(0.f, 0.f, 0.f);
-        return;
-    }
-    if (tb & kStateDirect) {                               // colour modes 1-2 (:652, :660)
-        sc = v3(st.y, st.z, st.w);
-        lo = hi = v3(0.f, 0.f, 0.f);                       // cleared buffers (:250-257)
-        return;
-    }
-    const float ind = (tb & (1 << 30)) ? A.ind_first : 0.2f * 1;
-    const vec3 D = v3(st.y, st.z, st.w);
-    if (tex != 0) {
-        // textureColour (:590, :611, :636) and, texture 3, the occlusion (:626-627)
-        const vec3 c = v3((float)((texel >> 16) & 255u) / 255.0f, (float)((texel >> 8) & 255u) / 255.0f,
-                          (float)(texel & 255u) / 255.0f);
-        if (tex == 3) {
-            float occ = (float)(texel >> 24);
-            occ /= 255.0f;
-            sc = c * ((D + v3(ind, ind, ind)) * occ);                                // :638
-            lo = c * ((D + v3(0.0f * 1, 0.0f * 1, 0.0f * 1)) * occ);                 // :640
-            hi = c * ((D + v3(0.4f * 1, 0.4f * 1, 0.4f * 1)) * occ);                 // :642
-        } else {
-            sc = c * (D + v3(ind, ind, ind));
-            lo = c * (D + v3(0.0f * 1, 0.0f * 1, 0.0f * 1));
-            hi = c * (D + v3(0.4f * 1, 0.4f * 1, 0.4f * 1));
-        }
-        return;
-    }
-    const vec3 c = v3(col.x, col.y, col.z);
-    sc = c * (D + v3(ind, ind, ind));                      // :580
-    lo = c * (D + v3(0.0f * 1, 0.0f * 1, 0.0f * 1));       // :582
-    hi = c * (D + v3(0.4f * 1, 0.4f * 1, 0.4f * 1));       // :584
-}
-
-// soft-shadow darkening amount of a pixel whose 3x3 shadow neighbourhood is
-// sh[cy-1..cy+1][cx-1..cx+1] (row stride ld), 0 if not shadowed
-// (:286-303, :1725-1733; [y+1][x-1] counted twice, [y+1][x+1] omitted)
-// (sh: the marks as ints, or the post state words with the mark in bit 31)
-template <class T>
-__device__ __forceinline__ float darken_at(const T *sh, int ld, int cy, int cx)
-{
-    const T *p = sh + cy * ld + cx;
-    auto c = [&](int o) { return sizeof(T) == 4 && (T)-1 > (T)0 ? (int)((uint32_t)p[o] >> 31) : (int)p[o]; };
-    if (c(0) != 1) return 0.0f;
-    int k = c(0) + c(-ld) + c(-ld - 1) + c(-ld + 1) + c(ld - 1) + c(ld) + c(ld - 1) + c(-1) + c(1);
-    float val = div_const((float)k, 9.0f, 1.0f / 9.0f);                 // val /= 9.0f
-    if ((double)val < 0.6) return 0.05f;
-    if ((double)val < 0.7) return 0.08f;
-    if ((double)val < 0.8) return 0.1f;
-    if ((double)val < 0.9) return 0.12f;
-    return 0.3f;
-}
-
 // Post-pass (:283-307) on a 64x8 tile: the shadow marks (halo 2) go to LDS,
 // then every pixel of the tile and its 1-pixel halo gets its three shade
 // buffers and its darkening computed once, then each interior pixel runs
@@ -596,10 +431,6 @@ __device__ __forceinline__ float darken_at(const T *sh, int ld, int cy, int cx)
 // state is the colour fill's float4 (cg_rast_colour.hip) instead of the fill's
 // record word, and the shadow marks come from the shadow plane; skip (may be
 // null): a sequence frame's status word, non-zero = the frame is not drawn.
-constexpr int kPostTW = 64, kPostTH = 8;
-constexpr int kPostHW = kPostTW + 2, kPostHH = kPostTH + 2;      // shade halo 1
-constexpr int kPostSW = kPostTW + 4, kPostSH = kPostTH + 4;      // shadow halo 2
-
 template <bool DIRECT, bool TEX>
 __global__ __launch_bounds__(256) void rast_post_kernel(const cg_rtri *__restrict__ tris, RastArgs A0,
                                                        const void *__restrict__ state_v,
@@ -807,6 +638,8 @@ static int rast_pipeline(cg_ctx *c, cg_rtri *d_tris, int n, int *n_dev, const cg
                          int32_t *d_shadow, hipStream_t st, cg_stats *stats, bool events_open, int tex_mask,
                          RastStage sg, const RastSeq *seq = nullptr);
 int rast_tex_maps(cg_ctx *c, RastTexMaps *m);
+int rast_make_args(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *p, cg_vec4 light,
+                   const cg_vec4 *d_light, int tex_mask, RastArgs *out);
 
 // glm::inverse for mat4 (glm/detail/type_mat4x4.inl:37-90), column-major
 // m[4c + r] = m[c][r]: findU / findV's inverse(R) (skeleton.cpp:1762).
@@ -844,10 +677,45 @@ static void mat4_inverse_glm(const float *m, float *out)
         for (int r = 0; r < 4; ++r) out[4 * c + r] = inv[c][r] * one_over;
 }
 
+// The kernels' frame arguments from the caller's parameters (both routes); state16 is the
+// route's own decision.  Fails for a texture the frame cannot render.
+int rast_make_args(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *p, cg_vec4 light,
+                   const cg_vec4 *d_light, int tex_mask, RastArgs *out)
+{
+    const int W = p->width, H = p->height;
+    RastArgs A;
+    A.W = W;
+    A.H = H;
+    A.n = n;
+    A.focal = p->focal;
+    A.light[0] = light.x; A.light[1] = light.y; A.light[2] = light.z;
+    A.lp[0] = p->light_power.x; A.lp[1] = p->light_power.y; A.lp[2] = p->light_power.z;
+    A.ind_first = p->indirect_first;
+    A.want_first = p->colour_mode == 0 && p->indirect_first != 0.2f * 1;   // the :585 rewrite is mode 0 only
+    A.d_light = d_light;
+    // texture modes 1-3: the maps, cameraPos and, when yaw != 0, inverse(R)
+    const int loaded = rast_tex_maps(c, &A.tx);
+    if (tex_mask & 16) return ctx_invalid(c, "texture selector outside 0-3 (TestModelH.h:21)");
+    if (tex_mask & ~loaded & 0xe)
+        return ctx_invalid(c, "a triangle carries a texture whose maps are not loaded (cg_rast_set_textures)");
+    if ((tex_mask & 2) && (size_t)(H - 1) * kMarbleN + (W - 1) >= (size_t)kMarbleN * kMarbleN)
+        return ctx_invalid(c, "marble: normalMap_marble[y * 2000 + x] would index past the map");
+    A.textured = (tex_mask & 0xe) != 0;
+    A.use_inv = p->yaw != 0.0f;
+    A.state16 = 0;
+    A.tris = d_tris;
+    A.cam[0] = p->camera.x; A.cam[1] = p->camera.y; A.cam[2] = p->camera.z; A.cam[3] = p->camera.w;
+    mat4_inverse_glm(p->R, A.Rinv);
+    *out = A;
+    return CG_OK;
+}
+
 int rast_render_device(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *p, cg_vec4 light,
                        uint32_t *d_argb, float *d_depth, int32_t *d_shadow, hipStream_t st,
                        cg_stats *stats, int tex_mask)
 {
+    if (ctx_rast_route(c, n) == CG_RAST_ROUTE_COMPACT)
+        return rast_big_render(c, d_tris, n, p, light, d_argb, d_depth, d_shadow, st, stats, tex_mask);
     return rast_pipeline(c, const_cast<cg_rtri *>(d_tris), n, nullptr, p, light, nullptr, d_argb, d_depth, d_shadow,
                          st, stats, false, tex_mask, RastStage{nullptr, nullptr, 0});
 }
@@ -860,7 +728,14 @@ int rast_draw_device(cg_ctx *c, const cg_rtri *d_room, int n_room, const cg_rtri
                      hipStream_t st, cg_stats *stats, int **n_out, int tex_mask, const RastSeq *seq)
 {
     if (p->width <= 2 || p->height <= 2 || p->height > kRastMaxRows || p->focal == 0.0f) return CG_E_INVALID;
-    const int n_in = n_room + 7 * n_boxes;
+    const long long n_in_ll = (long long)n_room + 7ll * n_boxes;
+    if (ctx_rast_route(c, kGeomMaxLeaves * n_in_ll) == CG_RAST_ROUTE_COMPACT)
+        return rast_big_draw(c, d_room, n_room, d_boxes, n_boxes, p, d_argb, d_depth, d_shadow, st, stats, n_out,
+                             tex_mask, seq);
+    if (n_in_ll > kRastDenseInputs)
+        return ctx_invalid(c, "dense route: more than 4096 input triangles (the setup's LDS prefix); "
+                              "use the compact route (cg_rast_set_route)");
+    const int n_in = (int)n_in_ll;
     // planes 1-4 and 6 can each split a triangle in two; plane 5 never does
     const int cap = n_in > 0 ? 32 * n_in : 1;
     hipError_t e;
@@ -910,28 +785,8 @@ static int rast_pipeline(cg_ctx *c, cg_rtri *d_tris, int n, int *n_dev, const cg
         if (!shadow) return ctx_fail(c, e, "alloc shadow");
     }
     RastArgs A;
-    A.W = W;
-    A.H = H;
-    A.n = n;
-    A.focal = p->focal;
-    A.light[0] = light.x; A.light[1] = light.y; A.light[2] = light.z;
-    A.lp[0] = p->light_power.x; A.lp[1] = p->light_power.y; A.lp[2] = p->light_power.z;
-    A.ind_first = p->indirect_first;
-    A.want_first = p->colour_mode == 0 && p->indirect_first != 0.2f * 1;   // the :585 rewrite is mode 0 only
-    A.d_light = d_light;
-    // texture modes 1-3: the maps, cameraPos and, when yaw != 0, inverse(R)
-    const int loaded = rast_tex_maps(c, &A.tx);
-    if (tex_mask & 16) return ctx_invalid(c, "texture selector outside 0-3 (TestModelH.h:21)");
-    if (tex_mask & ~loaded & 0xe)
-        return ctx_invalid(c, "a triangle carries a texture whose maps are not loaded (cg_rast_set_textures)");
-    if ((tex_mask & 2) && (size_t)(H - 1) * kMarbleN + (W - 1) >= (size_t)kMarbleN * kMarbleN)
-        return ctx_invalid(c, "marble: normalMap_marble[y * 2000 + x] would index past the map");
-    A.textured = (tex_mask & 0xe) != 0;
-    A.use_inv = p->yaw != 0.0f;
+    if (const int rc = rast_make_args(c, d_tris, n, p, light, d_light, tex_mask, &A)) return rc;
     A.state16 = p->colour_mode == 0 && nn < 32768;
-    A.tris = d_tris;
-    A.cam[0] = p->camera.x; A.cam[1] = p->camera.y; A.cam[2] = p->camera.z; A.cam[3] = p->camera.w;
-    mat4_inverse_glm(p->R, A.Rinv);
     hipEvent_t e0, e1;
     ctx_events(c, &e0, &e1);
     if (stats && !events_open && (e = hipEventRecord(e0, st)) != hipSuccess) return ctx_fail(c, e, "event");
@@ -992,6 +847,7 @@ static int rast_pipeline(cg_ctx *c, cg_rtri *d_tris, int n, int *n_dev, const cg
         stats->n_tris = n_dev ? -1 : n;
         stats->n_spans = 0;
     }
+    *ctx_rast_last(c) = RastLast{CG_RAST_ROUTE_DENSE, n_dev ? -1ll : (long long)n, 0, -1, n_dev, count, H, st};
     return CG_OK;
 }
 

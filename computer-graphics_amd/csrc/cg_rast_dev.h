@@ -1,5 +1,6 @@
 // cg_rast_dev.h -- rasteriser structures and device helpers shared by the
-// colour-mode-0 pipeline (cg_rast.hip) and colour modes 1-2 (cg_rast_colour.hip).
+// colour-mode-0 pipeline (cg_rast.hip), colour modes 1-2 (cg_rast_colour.hip)
+// and the compact route for large scenes (cg_rast_big.hip).
 // Reference: rasteriser/Source/skeleton.cpp.
 #pragma once
 
@@ -62,6 +63,30 @@ struct RastSeq {
     // null for the first) and announces itself (done_ev); null on one stream
     hipEvent_t wait_ev, done_ev;
 };
+
+// ---- routes (cg_rast_route): the dense pipeline of cg_rast.hip, the compact one of cg_rast_big.hip ----
+constexpr int kRastDenseInputs = 4096;                                  // input triangles the dense Draw accepts
+constexpr long long kRastDenseList = (long long)kGeomMaxLeaves * kRastDenseInputs;   // 131072: its list capacity
+constexpr long long kRastMaxInputs = 4194304;                           // cg_rast_set_scene's limit
+// The route a frame of list capacity `cap` takes on this context (its forced route, else cg_rast_route).
+int ctx_rast_route(cg_ctx *c, long long cap);
+// What cg_rast_scratch_info reports of the latest frame.  The dense route leaves its counts on
+// the device (n_dev, count[H]); the compact route knows them on the host.
+struct RastLast {
+    int route = -1;                 // -1: no frame yet
+    long long n = -1;               // clipped triangles (-1: read *n_dev)
+    long long spans = 0;            // spans the setup stored (dense: not counted)
+    long long recs = -1;            // row records (-1: sum of count[0 .. H))
+    const int *n_dev = nullptr, *count = nullptr;
+    int H = 0;
+    hipStream_t st = nullptr;
+};
+RastLast *ctx_rast_last(cg_ctx *c);
+int rast_big_render(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *p, cg_vec4 light, uint32_t *d_argb,
+                    float *d_depth, int32_t *d_shadow, hipStream_t st, cg_stats *stats, int tex_mask);
+int rast_big_draw(cg_ctx *c, const cg_rtri *d_room, int n_room, const cg_rtri *d_boxes, int n_boxes,
+                  const cg_rast_params *p, uint32_t *d_argb, float *d_depth, int32_t *d_shadow, hipStream_t st,
+                  cg_stats *stats, int **n_out, int tex_mask, const RastSeq *seq);
 
 // Ordered per-row records (one wave per screen row): for every triangle in
 // order whose span on this row has a fragment on screen, a 48-byte record
@@ -193,5 +218,177 @@ __device__ __forceinline__ vec3 rast_tex_normal(const RastArgs &A, int tex, int 
 // (colour modes 1-2; low/high buffers stay cleared), instead of a triangle
 // index whose colour the post-pass multiplies by (D + k).
 constexpr int kStateDirect = 1 << 29;
+
+// ---- shared by the dense pipeline (cg_rast.hip) and the compact route (cg_rast_big.hip) ----
+constexpr int kSetupThreads = 256;
+constexpr int kRastMaxRows = 4096;   // LDS rows per triangle in span setup (H <= 4096)
+
+// Workgroups are dispatched round-robin over the 8 XCDs, each with its own L2.
+// The row-ordered kernels renumber them so that each group of kXcdRows rows
+// is handled by one XCD (a row's records are then fetched into one L2, not
+// all eight), with the groups dealt round-robin to keep the XCDs balanced
+// (row cost varies a lot over the frame).  A kernel whose row group is
+// `per_group` workgroups wide launches xcd_grid(H, per_group) of them.
+constexpr int kXcds = 8, kXcdRows = 8;
+__host__ __device__ constexpr int xcd_grid(int H, int per_group)
+{
+    return kXcds * ((((H + kXcdRows - 1) / kXcdRows) + kXcds - 1) / kXcds) * per_group;
+}
+// -> row group of this workgroup (-1: idle padding) and its index m within the group
+__device__ __forceinline__ int xcd_group(int H, int per_group, int &m)
+{
+    const int k = (int)(blockIdx.x % kXcds), l = (int)(blockIdx.x / kXcds);
+    m = l % per_group;
+    const int g = k + kXcds * (l / per_group);
+    return g < (H + kXcdRows - 1) / kXcdRows ? g : -1;
+}
+
+struct Pix {                // rasteriser Pixel (:88-94) minus w
+    int x, y;
+    float zinv, X, Y;
+};
+
+__device__ __forceinline__ Pix vertex_shader(const RastArgs &A, cg_vec4 v)
+{
+    // :512-521
+    float x = (A.focal * (v.x / v.z)) + (float)(A.W / 2);
+    float y = (A.focal * (v.y / v.z)) + (float)(A.H / 2);
+    Pix p;
+    p.x = f2i_x86(x);
+    p.y = f2i_x86(y);
+    p.zinv = 1 / v.z;
+    p.X = v.x;
+    p.Y = v.y;
+    return p;
+}
+
+// Interpolate (:524-551) prepared for one edge a -> b with N samples.
+struct Edge {
+    float ax, ay, az, aX, aY;     // a.x, a.y as float; a.zinv; a.pos3d.xy * a.zinv
+    float stx, sty, stz, sX, sY;
+    int n;
+};
+
+__device__ __forceinline__ Edge make_edge(Pix a, Pix b)
+{
+    Edge e;
+    float aX = a.X * a.zinv, aY = a.Y * a.zinv;   // :526-527
+    float bX = b.X * b.zinv, bY = b.Y * b.zinv;   // :529-530
+    int dx = a.x - b.x, dy = a.y - b.y;
+    dx = dx < 0 ? -dx : dx;
+    dy = dy < 0 ? -dy : dy;
+    e.n = (dx > dy ? dx : dy) + 1;                // :473-475
+    float den = (float)(e.n - 1 > 1 ? e.n - 1 : 1);
+    e.ax = (float)a.x;
+    e.ay = (float)a.y;
+    e.az = a.zinv;
+    e.aX = aX;
+    e.aY = aY;
+    e.stx = (float)(b.x - a.x) / den;             // :533-538
+    e.sty = (float)(b.y - a.y) / den;
+    e.stz = (b.zinv - a.zinv) / den;
+    e.sX = (bX - aX) / den;
+    e.sY = (bY - aY) / den;
+    return e;
+}
+
+__device__ __forceinline__ int edge_x(const Edge &e, int j) { return f2i_x86(floorf(e.ax + (e.stx * (float)j))); }
+__device__ __forceinline__ int edge_y(const Edge &e, int j) { return f2i_x86(floorf(e.ay + (e.sty * (float)j))); }
+
+// sample j's zinv and pos3d.xy (:543-548)
+__device__ __forceinline__ void edge_attr(const Edge &e, int j, float &zinv, float &X, float &Y)
+{
+    float fj = (float)j;
+    zinv = e.az + (e.stz * fj);
+    X = (e.aX + (e.sX * fj)) / zinv;
+    Y = (e.aY + (e.sY * fj)) / zinv;
+}
+
+__device__ __forceinline__ unsigned long long key_left(int x, unsigned seq)
+{
+    return ((unsigned long long)((unsigned)x ^ 0x80000000u) << 32) | (unsigned long long)(~seq);
+}
+__device__ __forceinline__ unsigned long long key_right(int x, unsigned seq)
+{
+    return ((unsigned long long)((unsigned)x ^ 0x80000000u) << 32) | (unsigned long long)seq;
+}
+
+// Colour mode 0: fill -> post state, 4 bytes per pixel: 1 + the row record of
+// the last shading fragment (0 none) | the shadow mark << 31; 2 bytes (the
+// mark in bit 15) when a row holds fewer than 32768 records (A.state16).  The post-pass
+// rebuilds that fragment from the record -- zinv = lz + sz * i (:543) and the
+// pos3d numerators with the same float ops, the normal, the texels -- and
+// evaluates calculateIllumination there, so the fill keeps only what its
+// ordered walk decides.
+constexpr uint32_t kStShadow = 0x80000000u;
+
+// One wave per kFillPx-pixel row segment, one pixel per lane, state in
+// registers; records walked in triangle order (the reference's ordered
+// z-buffer), one uniform overlap test per record.
+constexpr int kFillPx = 64;   // pixels per wave; 128 / 256 measured 3 % / 10 % slower (C3, round 1)
+
+// shade buffers of one pixel as they stand after the fill (:580-585), from its
+// state and its triangle's colour
+__device__ __forceinline__ void shade3c(const RastArgs &A, float4 st, cg_vec3 col, vec3 &sc, vec3 &lo, vec3 &hi,
+                                        int tex = 0, uint32_t texel = 0u)
+{
+    const int tb = __float_as_int(st.x);
+    if (tb < 0) {
+        sc = lo = hi = v3(0.f, 0.f, 0.f);
+        return;
+    }
+    if (tb & kStateDirect) {                               // colour modes 1-2 (:652, :660)
+        sc = v3(st.y, st.z, st.w);
+        lo = hi = v3(0.f, 0.f, 0.f);                       // cleared buffers (:250-257)
+        return;
+    }
+    const float ind = (tb & (1 << 30)) ? A.ind_first : 0.2f * 1;
+    const vec3 D = v3(st.y, st.z, st.w);
+    if (tex != 0) {
+        // textureColour (:590, :611, :636) and, texture 3, the occlusion (:626-627)
+        const vec3 c = v3((float)((texel >> 16) & 255u) / 255.0f, (float)((texel >> 8) & 255u) / 255.0f,
+                          (float)(texel & 255u) / 255.0f);
+        if (tex == 3) {
+            float occ = (float)(texel >> 24);
+            occ /= 255.0f;
+            sc = c * ((D + v3(ind, ind, ind)) * occ);                                // :638
+            lo = c * ((D + v3(0.0f * 1, 0.0f * 1, 0.0f * 1)) * occ);                 // :640
+            hi = c * ((D + v3(0.4f * 1, 0.4f * 1, 0.4f * 1)) * occ);                 // :642
+        } else {
+            sc = c * (D + v3(ind, ind, ind));
+            lo = c * (D + v3(0.0f * 1, 0.0f * 1, 0.0f * 1));
+            hi = c * (D + v3(0.4f * 1, 0.4f * 1, 0.4f * 1));
+        }
+        return;
+    }
+    const vec3 c = v3(col.x, col.y, col.z);
+    sc = c * (D + v3(ind, ind, ind));                      // :580
+    lo = c * (D + v3(0.0f * 1, 0.0f * 1, 0.0f * 1));       // :582
+    hi = c * (D + v3(0.4f * 1, 0.4f * 1, 0.4f * 1));       // :584
+}
+
+// soft-shadow darkening amount of a pixel whose 3x3 shadow neighbourhood is
+// sh[cy-1..cy+1][cx-1..cx+1] (row stride ld), 0 if not shadowed
+// (:286-303, :1725-1733; [y+1][x-1] counted twice, [y+1][x+1] omitted)
+// (sh: the marks as ints, or the post state words with the mark in bit 31)
+template <class T>
+__device__ __forceinline__ float darken_at(const T *sh, int ld, int cy, int cx)
+{
+    const T *p = sh + cy * ld + cx;
+    auto c = [&](int o) { return sizeof(T) == 4 && (T)-1 > (T)0 ? (int)((uint32_t)p[o] >> 31) : (int)p[o]; };
+    if (c(0) != 1) return 0.0f;
+    int k = c(0) + c(-ld) + c(-ld - 1) + c(-ld + 1) + c(ld - 1) + c(ld) + c(ld - 1) + c(-1) + c(1);
+    float val = div_const((float)k, 9.0f, 1.0f / 9.0f);                 // val /= 9.0f
+    if ((double)val < 0.6) return 0.05f;
+    if ((double)val < 0.7) return 0.08f;
+    if ((double)val < 0.8) return 0.1f;
+    if ((double)val < 0.9) return 0.12f;
+    return 0.3f;
+}
+
+// Post-pass tile (rast_post_kernel): 64x8 pixels, shade halo 1, shadow halo 2.
+constexpr int kPostTW = 64, kPostTH = 8;
+constexpr int kPostHW = kPostTW + 2, kPostHH = kPostTH + 2;      // shade halo 1
+constexpr int kPostSW = kPostTW + 4, kPostSH = kPostTH + 4;      // shadow halo 2
 
 }  // namespace cg

@@ -213,6 +213,30 @@ extern "C" int cg_rt_random_scene(uint64_t seed, int n, cg_tri *out)
     return n;
 }
 
+// The same draws for the rasteriser's Triangle, with the vertex spread a
+// parameter: centroid, v0, v1, v2 = centroid + U[-extent,extent]^3, colour;
+// texture 0, index 0; normal by ComputeNormal.  Stream seq 54.
+extern "C" int cg_rast_random_scene(uint64_t seed, int n, float extent, cg_rtri *out)
+{
+    if (n < 0 || (n && !out) || !(extent >= 0.0f) || !(extent <= 1e30f)) return CG_E_INVALID;
+    Pcg32 g(seed, 54u);
+    for (int k = 0; k < n; ++k) {
+        cg_rtri &t = out[k];
+        float cx = g.uniform(-1.f, 1.f), cy = g.uniform(-1.f, 1.f), cz = g.uniform(-1.f, 1.f);
+        cg_vec4 *v[3] = {&t.v0, &t.v1, &t.v2};
+        for (cg_vec4 *p : v) {
+            float dx = g.uniform(-extent, extent), dy = g.uniform(-extent, extent), dz = g.uniform(-extent, extent);
+            *p = cg_vec4{cx + dx, cy + dy, cz + dz, 1.0f};
+        }
+        float r = g.uniform(0.15f, 0.75f), gg = g.uniform(0.15f, 0.75f), b = g.uniform(0.15f, 0.75f);
+        t.color = cg_vec3{r, gg, b};
+        t.texture = 0;
+        t.index = 0;
+        compute_normal(t);
+    }
+    return n;
+}
+
 namespace cg {
 // The scene's box for the column windows: every triangle vertex and every
 // sphere (radius widened by 1e-6), then widened by 0.02 (1 + max |coordinate|).

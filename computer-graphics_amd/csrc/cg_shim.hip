@@ -71,6 +71,7 @@ int rast_seq_tables(cg_ctx *c, long long nb, long long *have, uint32_t **tables)
 int rast_rand_probe(cg_ctx *c, uint32_t *tables, int nb, const uint64_t *d_off, int n, int32_t *d_out, hipStream_t st);
 long long rast_rand_chunks(long long nvals);
 void rast_release(cg_ctx *ctx);
+void rast_big_blocks(int *batch, int *chunk);
 }  // namespace cg
 
 using namespace cg;
@@ -273,6 +274,9 @@ struct cg_ctx {
     // RAST scratch (owned by cg_rast.hip)
     DevBuf rtris, rhdr, rspan, rpix, rargb, rdepth, rshadow, rcount, rrecs, rgeo, rroom, rboxes;
     DevBuf rpc, rtl, rrnd, rjt;          // colour modes 1-2 (cg_rast_colour.hip)
+    DevBuf rbig[8];                      // the compact route's own buffers (cg_rast_big.hip)
+    int rast_route = -1;                 // cg_rast_set_route: -1 automatic, else the forced route
+    RastLast rlast;                      // the latest rasteriser frame (cg_rast_scratch_info)
     // cg_rast_draw_sequence_device: the generator's tables (windows, seed words, J_b for
     // rseq_chunks chunks) and the stream's capacity in fragments (0: 4 * W * H)
     DevBuf rseq;
@@ -332,6 +336,7 @@ void *ctx_buf(cg_ctx *c, int which, size_t bytes, hipError_t *e)
     case 16: b = &c->rtexel; break;
     case 17: b = &c->iscratch; break;
     case 18: b = &c->rseq; break;
+    case 20: case 21: case 22: case 23: case 24: case 25: case 26: case 27: b = &c->rbig[which - 20]; break;
     default: *e = hipErrorInvalidValue; return nullptr;
     }
     *e = b->ensure(bytes);
@@ -362,11 +367,14 @@ void rast_release(cg_ctx *c)
     c->rrecs.release(); c->rgeo.release(); c->rroom.release(); c->rboxes.release();
     c->rpc.release(); c->rtl.release(); c->rrnd.release(); c->rjt.release();
     c->rseq.release();
+    for (DevBuf &b : c->rbig) b.release();
     c->sstars.release(); c->sframe.release();
     c->tmarble.release(); c->tnoise.release(); c->twoven.release(); c->twoven_ao.release();
     c->twoven_op.release(); c->twoven_nrm.release(); c->tgrill.release(); c->tgrill_op.release();
     c->tgrill_nrm.release(); c->rtexel.release();
 }
+int ctx_rast_route(cg_ctx *c, long long cap) { return c->rast_route >= 0 ? c->rast_route : cg_rast_route(cap); }
+RastLast *ctx_rast_last(cg_ctx *c) { return &c->rlast; }
 // the device texture maps and which textures are renderable (bit k: texture k)
 int rast_tex_maps(cg_ctx *c, RastTexMaps *m)
 {
@@ -2014,8 +2022,9 @@ extern "C" int cg_rast_render(cg_ctx *c, const cg_rtri *tris, int n, const cg_ra
 
 extern "C" int cg_rast_set_scene(cg_ctx *c, const cg_rtri *room, int n_room, const cg_rtri *boxes, int n_boxes)
 {
-    if (!c || n_room < 0 || n_boxes < 0 || (n_room && !room) || (n_boxes && !boxes) || n_room + 7 * n_boxes > 4096)
-        return CG_E_INVALID;
+    if (!c || n_room < 0 || n_boxes < 0 || (n_room && !room) || (n_boxes && !boxes)) return CG_E_INVALID;
+    if ((long long)n_room + 7ll * n_boxes > kRastMaxInputs)
+        return ctx_invalid(c, "cg_rast_set_scene: more than 4194304 input triangles (n_room + 7 * n_boxes)");
     CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
     CG_TRY(c, c->rroom.ensure((size_t)(n_room > 0 ? n_room : 1) * sizeof(cg_rtri)), "alloc room");
     CG_TRY(c, c->rboxes.ensure((size_t)(n_boxes > 0 ? n_boxes : 1) * sizeof(cg_rtri)), "alloc boxes");
@@ -2028,6 +2037,62 @@ extern "C" int cg_rast_set_scene(cg_ctx *c, const cg_rtri *room, int n_room, con
     c->n_boxes = n_boxes;
     c->scene_tex = rast_tex_mask(room, n_room) | rast_tex_mask(boxes, n_boxes);
     ++c->scene_gen;
+    return CG_OK;
+}
+
+extern "C" int cg_rast_route(long long list_capacity)
+{
+    return list_capacity <= kRastDenseList ? CG_RAST_ROUTE_DENSE : CG_RAST_ROUTE_COMPACT;
+}
+
+extern "C" int cg_rast_set_route(cg_ctx *c, int route)
+{
+    if (!c) return CG_E_INVALID;
+    if (route < -1 || route > CG_RAST_ROUTE_COMPACT) return ctx_invalid(c, "cg_rast_set_route: -1, 0 or 1");
+    c->rast_route = route;
+    return CG_OK;
+}
+
+extern "C" int cg_rast_row_blocks(int *batch, int *chunk)
+{
+    if (!batch || !chunk) return CG_E_INVALID;
+    rast_big_blocks(batch, chunk);
+    return CG_OK;
+}
+
+extern "C" int cg_rast_scratch_info(cg_ctx *c, uint64_t out[5])
+{
+    if (!c || !out) return CG_E_INVALID;
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    const RastLast &L = c->rlast;
+    if (L.route >= 0) CG_TRY(c, hipStreamSynchronize(L.st ? L.st : c->stream), "rast frame");
+    auto held = [](const cg_ctx *x) {
+        size_t b = x->rtris.bytes + x->rhdr.bytes + x->rspan.bytes + x->rpix.bytes + x->rcount.bytes + x->rrecs.bytes +
+                   x->rgeo.bytes;
+        for (const DevBuf &d : x->rbig) b += d.bytes;
+        return b;
+    };
+    out[0] = held(c);
+    for (const cg_ctx *l : c->lanes)
+        if (l) out[0] += held(l);
+    out[1] = out[2] = out[3] = out[4] = 0;
+    if (L.route < 0) return CG_OK;
+    out[1] = (uint64_t)L.route;
+    long long n = L.n, recs = L.recs;
+    if (n < 0 && L.n_dev) {
+        int v = 0;
+        CG_TRY(c, hipMemcpy(&v, L.n_dev, sizeof(int), hipMemcpyDeviceToHost), "d2h count");
+        n = v;
+    }
+    if (recs < 0 && L.count && L.H > 0) {
+        std::vector<int> cnt((size_t)L.H);
+        CG_TRY(c, hipMemcpy(cnt.data(), L.count, cnt.size() * sizeof(int), hipMemcpyDeviceToHost), "d2h counts");
+        recs = 0;
+        for (int v : cnt) recs += v;
+    }
+    out[2] = (uint64_t)std::max(n, 0ll);
+    out[3] = (uint64_t)L.spans;
+    out[4] = (uint64_t)std::max(recs, 0ll);
     return CG_OK;
 }
 
@@ -2049,6 +2114,17 @@ extern "C" int cg_rast_draw_frames_device(cg_ctx *c, const cg_rast_params *ps, i
             return ctx_invalid(c, "draw_frames: colour mode 0 frames of one size (modes 1-2 chain rand offsets)");
     CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    if (ctx_rast_route(c, kGeomMaxLeaves * ((long long)c->n_room + 7ll * c->n_boxes)) == CG_RAST_ROUTE_COMPACT) {
+        // compact-route frames follow each other on `stream`: a lane would hold its own copy of the scratch
+        for (int f = 0; f < n_frames; ++f) {
+            const size_t o = (size_t)f * stride;
+            const int rc = rast_draw_device(c, (const cg_rtri *)c->rroom.p, c->n_room, (const cg_rtri *)c->rboxes.p,
+                                            c->n_boxes, &ps[f], d_argb + o, d_depth ? d_depth + o : nullptr,
+                                            d_shadow ? d_shadow + o : nullptr, st, nullptr, nullptr, c->scene_tex);
+            if (rc) return rc;
+        }
+        return CG_OK;
+    }
     // lanes in flight (CG_RAST_LANES for A/B runs): 6 -- C3 1080p, 64 frames per call, round 6:
     // 2 lanes 21.3-21.4k frames/s, 3 18.0k, 4 21.2k, 5 22.6-22.7k, 6 23.1-23.3k, 7 20.7-20.9k,
     // 8 21.3-22.4k (profiles/r06_ab_session2.json; round 1 had found 2 best).  The lanes' streams
@@ -2079,6 +2155,8 @@ extern "C" int cg_rast_draw_frames_device(cg_ctx *c, const cg_rast_params *ps, i
         CG_TRY(c, hipEventRecord(c->lane_ev[k], c->lanes[k]->stream), "event");
         CG_TRY(c, hipStreamWaitEvent(st, c->lane_ev[k], 0), "lane join");
     }
+    c->rlast = c->lanes[(n_frames - 1) % L]->rlast;   // the latest frame's counts live in its lane
+    c->rlast.st = st;
     return CG_OK;
 }
 
@@ -2096,6 +2174,7 @@ static int rast_lanes_ready(cg_ctx *c, int L)
             c->lane_gen[k] = c->scene_gen - 1;
         }
         cg_ctx *l = c->lanes[k];
+        l->rast_route = c->rast_route;          // the lanes follow their parent
         if (c->lane_gen[k] != c->scene_gen) {   // the parent's scene, device to device
             CG_TRY(c, l->rroom.ensure(c->rroom.bytes), "alloc lane room");
             CG_TRY(c, l->rboxes.ensure(c->rboxes.bytes), "alloc lane boxes");
@@ -2164,7 +2243,10 @@ extern "C" int cg_rast_draw_sequence_device(cg_ctx *c, const cg_rast_params *ps,
         const int v = e ? std::atoi(e) : 6;
         return std::max(1, std::min(v, (int)cg_ctx::kRastLanes));
     }();
-    const int L = std::min(lanes, n_frames);
+    // compact-route frames follow each other on `stream` (a lane would hold its own copy of the scratch)
+    const bool compact =
+        ctx_rast_route(c, kGeomMaxLeaves * ((long long)c->n_room + 7ll * c->n_boxes)) == CG_RAST_ROUTE_COMPACT;
+    const int L = compact ? 1 : std::min(lanes, n_frames);
     if (L > 1) {
         const int rc = rast_lanes_ready(c, L);
         if (rc) return rc;
@@ -2212,6 +2294,10 @@ extern "C" int cg_rast_draw_sequence_device(cg_ctx *c, const cg_rast_params *ps,
     for (int k = 0; L > 1 && k < L; ++k) {
         CG_TRY(c, hipEventRecord(c->lane_ev[k], c->lanes[k]->stream), "event");
         CG_TRY(c, hipStreamWaitEvent(st, c->lane_ev[k], 0), "lane join");
+    }
+    if (L > 1) {
+        c->rlast = c->lanes[(n_frames - 1) % L]->rlast;
+        c->rlast.st = st;
     }
     return CG_OK;
 }

@@ -419,12 +419,59 @@ int cg_rast_render_device(cg_ctx *ctx, const cg_rtri *d_tris, int n, const cg_ra
 /* Whole rasteriser Draw on the device (skeleton.cpp:203-308): upload the
  * LoadTestModel room/boxes once, then each frame runs the geometry
  * (shadow volumes, rotation, clip) AND the fill + post-pass on the GPU --
- * the same lists cg_rast_prepare builds on the host. */
+ * the same lists cg_rast_prepare builds on the host.
+ * n_room + 7 * n_boxes (a box triangle brings its 6 shadow-volume triangles)
+ * may be up to 4194304; above that CG_E_INVALID with a message.
+ *
+ * cg_rast_draw_device on the dense route (below) only enqueues and never
+ * waits.  On the compact route it waits on the host, on `stream`, for the
+ * frame's own counts -- the clipped triangle count, then the span total, then
+ * the record total and the longest row -- and allocates exactly what the frame
+ * needs, grow-only: no pool can overflow and there is no fallback path.  (So a
+ * compact-route frame cannot be captured into a graph.)  cg_rast_render_device
+ * on the compact route waits likewise for the last two. */
 int cg_rast_set_scene(cg_ctx *ctx, const cg_rtri *room, int n_room, const cg_rtri *boxes, int n_boxes);
 int cg_rast_draw(cg_ctx *ctx, const cg_rast_params *p, uint32_t *argb, float *depth, int32_t *shadow,
                  cg_stats *stats);
 int cg_rast_draw_device(cg_ctx *ctx, const cg_rast_params *p, uint32_t *d_argb, float *d_depth,
                         int32_t *d_shadow, void *stream);
+
+/* Two routes render the same Draw, every plane bit for bit the same.  DENSE:
+ * spans and row records sized at list capacity x H, the kernels of the
+ * coursework scene.  COMPACT (large scenes): scratch and work follow what the
+ * frame covers -- spans packed per triangle, a row's records packed in
+ * triangle order by a stable counting sort of the spans.  cg_rast_route
+ * (host-only) is the automatic choice: DENSE for list_capacity <= 131072,
+ * else COMPACT; list_capacity is 32 * (n_room + 7 * n_boxes) for the
+ * cg_rast_draw* entries and n for cg_rast_render*.
+ * The compact route serves cg_rast_draw, cg_rast_draw_device, cg_rast_render
+ * and cg_rast_render_device in colour mode 0 with texture modes 0-3 and the
+ * indirect_first rule; cg_rast_draw_frames_device and
+ * cg_rast_draw_sequence_device run its frames one after another on `stream`
+ * (no lanes: each would hold its own copy of the scratch).  Colour modes 1-2
+ * on the compact route return CG_E_INVALID with a message: their count, scan,
+ * generator and chain kernels are built for the dense layout only. */
+enum { CG_RAST_ROUTE_DENSE = 0, CG_RAST_ROUTE_COMPACT = 1 };
+int cg_rast_route(long long list_capacity);
+/* Test and A/B hook: -1 automatic (the default), 0 forces DENSE, 1 forces
+ * COMPACT for this context's frames (its lanes follow).  A forced dense
+ * cg_rast_draw* of more than 4096 input triangles fails with CG_E_INVALID. */
+int cg_rast_set_route(cg_ctx *ctx, int route);
+/* Rasteriser scratch after the latest rasteriser frame (waits for it, on the
+ * stream it ran on): out[0] device bytes held for rasteriser scratch (lanes
+ * included), out[1] the route the frame took, out[2] its clipped triangles,
+ * out[3] its spans (the dense route does not count them: 0), out[4] its row
+ * records.  All 0 before the first frame. */
+int cg_rast_scratch_info(cg_ctx *ctx, uint64_t out[5]);
+/* Host-only: the block sizes of the compact route's row-list passes -- the
+ * spans a wave ranks per round (*batch) and the consecutive spans a wave owns
+ * (*chunk); record order must hold across both boundaries. */
+int cg_rast_row_blocks(int *batch, int *chunk);
+/* Host-only, no device work: n random triangles from PCG32 (seed, stream 54)
+ * as cg_rt_random_scene draws them: centroid ~ U[-1,1]^3, each vertex =
+ * centroid + U[-extent,extent]^3 with w = 1, colour ~ U[0.15,0.75]^3, texture 0,
+ * index 0, normal by ComputeNormal (rasteriser TestModelH.h:32-41).  Returns n. */
+int cg_rast_random_scene(uint64_t seed, int n, float extent, cg_rtri *out);
 /* n_frames whole Draws (colour mode 0, one size; each frame its own params --
  * camera, light, R, first-frame indirect) into frame f at d_argb + f *
  * frame_stride pixels (0: W*H), likewise d_depth / d_shadow (may be NULL).
