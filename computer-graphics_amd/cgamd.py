@@ -114,6 +114,14 @@ _SIGS = {
     "cg_rt_area_lights": (C.c_int, [C.POINTER(Light), C.c_float, C.c_int, C.POINTER(Light), C.c_int]),
     "cg_rt_random_scene": (C.c_int, [C.c_uint64, C.c_int, C.POINTER(Tri)]),
     "cg_rt_set_scene": (C.c_int, [P, C.POINTER(Tri), C.c_int, C.POINTER(Sphere), C.c_int]),
+    "cg_rt_set_scene_device": (C.c_int, [P, P, C.c_int, C.POINTER(Sphere), C.c_int, P]),
+    "cg_rt_set_grid_caps": (C.c_int, [P, C.c_longlong, C.c_longlong]),
+    "cg_rt_grid_dims": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float),
+                                  C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    "cg_rt_grid_get": (C.c_int, [P, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float), P, C.c_size_t, P,
+                                 C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "cg_rt_grid_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
+    "cg_rt_grid_phase_ms": (C.c_int, [P, C.POINTER(C.c_double)]),
     "cg_rt_set_pending_cap": (C.c_int, [P, C.c_int]),
     "cg_rt_scratch_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
     "cg_rt_pool_demand": (C.c_int, [P, C.POINTER(C.c_uint64)]),
@@ -361,6 +369,22 @@ def random_scene(n, seed=0x5EED):
 
 
 RAST_ROUTE_DENSE, RAST_ROUTE_COMPACT = 0, 1   # cg_render.h CG_RAST_ROUTE_*
+
+
+def rt_grid_dims(vmin, vmax, n_tris):
+    """cg_rt_grid_dims (host only): the scene grid's frame from the float vertex minimum / maximum
+    per axis and the triangle count, as dict(lo float32[3], h, inv_h float32, res int[3]), or None
+    for "no grid"."""
+    lib = load()
+    lo, res = (C.c_float * 3)(), (C.c_int * 3)()
+    h, inv_h = C.c_float(), C.c_float()
+    rc = lib.cg_rt_grid_dims((C.c_float * 3)(*vmin), (C.c_float * 3)(*vmax), n_tris, lo, C.byref(h), C.byref(inv_h), res)
+    if rc < 0:
+        raise RuntimeError(f"cg_rt_grid_dims failed: {rc}")
+    if rc == 0:
+        return None
+    return dict(lo=np.array(lo[:], np.float32), h=np.float32(h.value), inv_h=np.float32(inv_h.value),
+                res=np.array(res[:], np.int32))
 
 
 def rast_route(list_capacity):
@@ -643,6 +667,51 @@ class Context:
         sp = C.byref(sph) if sph is not None else None
         self._check(self.lib.cg_rt_set_scene(self.h, tris, n, sp, n_sph if sph is not None else 0),
                     "cg_rt_set_scene")
+
+    def rt_set_scene_device(self, d_tris_ptr, n, sph=None, n_sph=0, stream=None):
+        """cg_rt_set_scene_device: n triangles (cg_tri, 76 B each) at the device address d_tris_ptr;
+        sph is a host Sphere (n_sph of them), stream a HIP stream handle (None: the context's).
+        Raises on any failure, as rt_set_scene does."""
+        sp = C.byref(sph) if sph is not None else None
+        self._check(self.lib.cg_rt_set_scene_device(self.h, P(d_tris_ptr) if d_tris_ptr else None, n, sp,
+                                                    n_sph if sph is not None else 0, P(stream) if stream else None),
+                    "cg_rt_set_scene_device")
+
+    def rt_set_grid_caps(self, entries=0, candidates=0):
+        """cg_rt_set_grid_caps: caps of the scene grid for later scene changes (0 = default)."""
+        self._check(self.lib.cg_rt_set_grid_caps(self.h, entries, candidates), "cg_rt_set_grid_caps")
+
+    def rt_grid(self):
+        """cg_rt_grid_get: the installed scene grid as dict(res int32[3], lo float32[3], h float32,
+        start int32[cells + 1], tris int32[entries]), or None when the scene has none."""
+        res, lo, h = (C.c_int * 3)(), (C.c_float * 3)(), C.c_float()
+        ns, ne = C.c_size_t(), C.c_size_t()
+        rc = self.lib.cg_rt_grid_get(self.h, res, lo, C.byref(h), None, 0, None, 0, C.byref(ns), C.byref(ne))
+        if rc == 0:
+            return None
+        if rc != 1:
+            self._check(rc, "cg_rt_grid_get")
+        start = np.zeros(ns.value, np.int32)
+        tris = np.zeros(max(ne.value, 1), np.int32)
+        rc = self.lib.cg_rt_grid_get(self.h, res, lo, C.byref(h), start.ctypes.data_as(P), start.size,
+                                     tris.ctypes.data_as(P), tris.size, C.byref(ns), C.byref(ne))
+        if rc != 1:
+            self._check(rc if rc < 0 else CG_E_INVALID, "cg_rt_grid_get")
+        return dict(res=np.array(res[:], np.int32), lo=np.array(lo[:], np.float32), h=np.float32(h.value),
+                    start=start, tris=tris[:ne.value])
+
+    def rt_grid_info(self):
+        """cg_rt_grid_info: dict(cells, entries, candidates, bytes) of the latest scene change
+        (candidates: pairs the device build tested, 0 after a host build)."""
+        out = (C.c_uint64 * 4)()
+        self._check(self.lib.cg_rt_grid_info(self.h, out), "cg_rt_grid_info")
+        return dict(cells=out[0], entries=out[1], candidates=out[2], bytes=out[3])
+
+    def rt_grid_phase_ms(self):
+        """cg_rt_grid_phase_ms: device ms of the latest device build's phases, -1 where one did not run."""
+        out = (C.c_double * 5)()
+        self._check(self.lib.cg_rt_grid_phase_ms(self.h, out), "cg_rt_grid_phase_ms")
+        return dict(zip(("bounds", "ranges", "count", "offsets", "fill_order"), out[:]))
 
     def rt_set_pending_cap(self, cap):
         """Test hook: capacity of the large-scene pending shadow-ray queue (0 = default)."""

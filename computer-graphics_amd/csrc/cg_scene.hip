@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "cg_internal.h"
+#include "cg_rt_grid.h"
 
 using namespace cg;
 
@@ -238,12 +239,33 @@ extern "C" int cg_rast_random_scene(uint64_t seed, int n, float extent, cg_rtri 
 }
 
 namespace cg {
+// What the triangles contribute to the scene's bounds (SceneBounds, cg_rt_grid.h), on the host.
+// rt_grid_bounds_device computes the same seven floats from device triangles.
+SceneBounds rt_scene_bounds(const cg_tri *tris, int n_tris)
+{
+    SceneBounds b;
+    for (int i = 0; i < n_tris; ++i) {
+        const cg_vec4 *v[3] = {&tris[i].v0, &tris[i].v1, &tris[i].v2};
+        for (const cg_vec4 *q : v) {
+            const float p[3] = {q->x, q->y, q->z};
+            for (int k = 0; k < 3; ++k) {
+                b.vmin[k] = std::min(b.vmin[k], p[k]);
+                b.vmax[k] = std::max(b.vmax[k], p[k]);
+            }
+        }
+        const float q[3] = {tris[i].normal.x, tris[i].normal.y, tris[i].normal.z};
+        for (float x : q) b.nmax = std::isfinite(x) ? std::max(b.nmax, std::fabs(x)) : INFINITY;
+    }
+    return b;
+}
+
 // The scene's box for the column windows: every triangle vertex and every
 // sphere (radius widened by 1e-6), then widened by 0.02 (1 + max |coordinate|).
 // A scene property: computed once per uploaded scene (cg_rt_set_scene), so
 // the per-frame window below is O(1) for any camera.  Empty scene: lo > hi.
-void rt_scene_box(const cg_tri *tris, int n_tris, const cg_sphere *spheres, int n_spheres, double lo[3],
-                  double hi[3])
+// The vertices enter through their float minimum / maximum per axis (b).
+void rt_scene_box_from(const SceneBounds &b, int n_tris, const cg_sphere *spheres, int n_spheres, double lo[3],
+                       double hi[3])
 {
     for (int k = 0; k < 3; ++k) {
         lo[k] = 1e300;
@@ -257,10 +279,11 @@ void rt_scene_box(const cg_tri *tris, int n_tris, const cg_sphere *spheres, int 
             hi[k] = std::max(hi[k], p[k] + r);
         }
     };
-    for (int i = 0; i < n_tris; ++i) {
-        const cg_vec4 *v[3] = {&tris[i].v0, &tris[i].v1, &tris[i].v2};
-        for (const cg_vec4 *q : v) add(q->x, q->y, q->z, 0.0);
-    }
+    if (n_tris > 0)
+        for (int k = 0; k < 3; ++k) {
+            lo[k] = std::min(lo[k], (double)b.vmin[k]);
+            hi[k] = std::max(hi[k], (double)b.vmax[k]);
+        }
     for (int i = 0; i < n_spheres; ++i)
         add(spheres[i].centre.x, spheres[i].centre.y, spheres[i].centre.z,
             std::sqrt((double)spheres[i].radiusSquared) * (1.0 + 1e-6));
@@ -270,6 +293,45 @@ void rt_scene_box(const cg_tri *tris, int n_tris, const cg_sphere *spheres, int 
         lo[k] -= m;
         hi[k] += m;
     }
+}
+
+void rt_scene_box(const cg_tri *tris, int n_tris, const cg_sphere *spheres, int n_spheres, double lo[3],
+                  double hi[3])
+{
+    rt_scene_box_from(rt_scene_bounds(tris, n_tris), n_tris, spheres, n_spheres, lo, hi);
+}
+
+// The box of every possible hit position (RtGrid::blo / bhi): the triangles' vertices and the
+// spheres (radius from radiusSquared, rounded up), widened because float hit positions stray by
+// rounding.
+void rt_hit_box_from(const SceneBounds &b, const cg_sphere *spheres, int n_spheres, float blo[3], float bhi[3])
+{
+    for (int k = 0; k < 3; ++k) {
+        blo[k] = std::min(FLT_MAX, b.vmin[k]);
+        bhi[k] = std::max(-FLT_MAX, b.vmax[k]);
+    }
+    auto grow = [&](int k, float lo, float hi) {
+        blo[k] = std::min(blo[k], lo);
+        bhi[k] = std::max(bhi[k], hi);
+    };
+    for (int i = 0; i < n_spheres; ++i) {
+        const float r = (float)(std::sqrt((double)spheres[i].radiusSquared) * (1.0 + 1e-6));
+        grow(0, spheres[i].centre.x - r, spheres[i].centre.x + r);
+        grow(1, spheres[i].centre.y - r, spheres[i].centre.y + r);
+        grow(2, spheres[i].centre.z - r, spheres[i].centre.z + r);
+    }
+    for (int k = 0; k < 3; ++k) {
+        blo[k] -= 1e-4f + 1e-5f * std::fabs(blo[k]);
+        bhi[k] += 1e-4f + 1e-5f * std::fabs(bhi[k]);
+    }
+}
+
+// Bound of every hit normal's components: the triangles' own (skeleton.cpp:378) and
+// normalize(pos - centre) for spheres (:385), whose components are <= 1 up to rounding.
+float rt_normal_bound(const SceneBounds &b, int n_spheres)
+{
+    const float nb = n_spheres > 0 ? 1.00000095367431640625f : 0.f;   // 1 + 2^-20
+    return std::max(nb, b.nmax);
 }
 
 // Columns an unrotated camera can see anything in, from the scene's box

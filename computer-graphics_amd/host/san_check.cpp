@@ -203,6 +203,35 @@ int main(int argc, char **argv)
         if (cg_rt_sequence_runs(seq.data(), -1, 28, 1, 1, nullptr, nullptr, nullptr, 0) != CG_E_INVALID)
             fail("cg_rt_sequence_runs accepted n_frames < 0", -1);
     }
+    {
+        // the scene grid's sizing rule (host-only): ordinary, flat in one axis, a single point (near
+        // the origin and far from it, where the +-1e-4f widening rounds away), infinite, lo > hi
+        const float inf = __builtin_inff(), nan = __builtin_nanf("");
+        const float bounds[][6] = {{-1.02f, -1.02f, -1.02f, 1.02f, 1.02f, 1.02f},
+                                   {-1, -1, 0.5f, 1, 1, 0.5f},
+                                   {0.25f, 0.25f, 0.25f, 0.25f, 0.25f, 0.25f},
+                                   {1e9f, 1e9f, 1e9f, 1e9f, 1e9f, 1e9f},
+                                   {-inf, -1, -1, 1, 1, inf},
+                                   {inf, inf, inf, -inf, -inf, -inf},
+                                   {nan, 0, 0, 1, 1, 1},
+                                   {1, 1, 1, -1, -1, -1},
+                                   {3.4e38f, -3.4e38f, 0, 3.4e38f, 3.4e38f, 1},
+                                   {0, 0, 0, 1000, 1e-3f, 1e-3f}};
+        for (const auto &b : bounds)
+            for (int n : {0, 1, 4194304}) {
+                float lo[3], h, inv_h;
+                int res[3];
+                const int rc = cg_rt_grid_dims(b, b + 3, n, lo, &h, &inv_h, res);
+                if (rc != 0 && rc != 1) fail("cg_rt_grid_dims", rc);
+                if (n == 0 && rc != 0) fail("cg_rt_grid_dims built a grid of no triangles", rc);
+                if (rc == 1)
+                    for (int k = 0; k < 3; ++k)
+                        if (res[k] < 1 || res[k] > 512) fail("cg_rt_grid_dims resolution", res[k]);
+            }
+        float lo[3], h, inv_h;
+        if (cg_rt_grid_dims(nullptr, bounds[0], 1, lo, &h, &inv_h, nullptr) != CG_E_INVALID)
+            fail("cg_rt_grid_dims accepted null arguments", -1);
+    }
     cg_light centre{{0, -0.5f, -0.7f, 1}, {14, 14, 14}}, area[64];
     if (int rc = cg_rt_area_lights(&centre, 0.1f, 8, area, 64); rc < 0) fail("cg_rt_area_lights", rc);
     std::vector<int32_t> r(4096);

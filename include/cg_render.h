@@ -138,6 +138,42 @@ int cg_rt_random_scene(uint64_t seed, int n, cg_tri *out);
  * the reference rebuilds in Draw (skeleton.cpp:113-116). */
 int cg_rt_set_scene(cg_ctx *ctx, const cg_tri *tris, int n_tris,
                     const cg_sphere *spheres, int n_spheres);
+/* cg_rt_set_scene for triangles that live in device memory (cg_tri, 76 B each); the spheres are
+ * host memory.  d_tris is read after the work already queued on `stream` (NULL: the context's own),
+ * so a producer kernel on that stream is ordered before it; the triangles are copied into the
+ * context's buffer and on return the caller's buffer is no longer read.  Frames of the previous
+ * scene still in flight on this context are waited for.  The context is left as cg_rt_set_scene
+ * leaves it for the same bytes -- the scene bounds and, for n_tris > 64, the grid are computed on
+ * the device (cg_rt_grid.hip) and equal the host's bit for bit -- so every later call works
+ * unchanged.  Host waits, each a hipStreamSynchronize on `stream` after a small copy: one for the
+ * reduced bounds, two for the grid's totals (candidate pairs, entries), and a closing one after
+ * which frames may follow on any stream.  The grid is declined (frames then take the no-grid path,
+ * as when the host builder gives up) when it would hold more entries than the entries cap or when
+ * more candidate (triangle, cell) pairs would have to be tested than the candidates cap
+ * (cg_rt_set_grid_caps); the host form has no candidates cap and, for scenes of many large thin
+ * triangles, builds a grid this form declines. */
+int cg_rt_set_scene_device(cg_ctx *ctx, const cg_tri *d_tris, int n_tris,
+                           const cg_sphere *spheres /* host */, int n_spheres, void *stream);
+/* Caps of the scene grid, 0 = default: `entries` (both forms; default 64 << 20) and `candidates`
+ * (device form only; default 16 x the entries cap).  They apply to later scene changes. */
+int cg_rt_set_grid_caps(cg_ctx *ctx, long long entries, long long candidates);
+/* Host-only (no device work): the grid's sizing rule.  From the float minimum / maximum of the
+ * vertices per axis and the triangle count: lo[3], h, inv_h, res[3].  Returns 1, or 0 for "no
+ * grid" (n_tris <= 0 or bounds that are not finite; the outputs are then 0). */
+int cg_rt_grid_dims(const float vmin[3], const float vmax[3], int n_tris, float lo[3], float *h,
+                    float *inv_h, int res[3]);
+/* Diagnostic: the installed grid.  Returns 1 and res / lo / h (each may be NULL), *n_start =
+ * cells + 1 and *n_entries; with buffers, also start[cells + 1] and tris[entries] (CG_E_CAPACITY if
+ * a given buffer is smaller).  Returns 0 when the scene has no grid (small scene, or declined). */
+int cg_rt_grid_get(cg_ctx *ctx, int res[3], float lo[3], float *h, int *start, size_t start_cap,
+                   int *tris, size_t tris_cap, size_t *n_start, size_t *n_entries);
+/* Diagnostic: out = cells, entries, candidate pairs the device build tested (0 after a host
+ * build), device bytes the device builder holds.  After a declined device build cells, candidates
+ * and (when the entries cap declined it) entries are the declined grid's. */
+int cg_rt_grid_info(cg_ctx *ctx, uint64_t out[4]);
+/* Diagnostic: device time in ms of the latest device build's phases (bounds, ranges, count,
+ * offsets, fill / order), -1 for a phase that did not run. */
+int cg_rt_grid_phase_ms(cg_ctx *ctx, double out[5]);
 /* One frame of raytracer Draw (skeleton.cpp:104-169): per pixel 3x3
  * sub-rays, ClosestIntersection (:263-363) and DirectLight (:366-415),
  * PutPixelSDL packing (SDLauxiliary.h:149-161).  Writes W*H ARGB into the
