@@ -170,6 +170,8 @@ _SIGS = {
     "cg_rast_draw_device": (C.c_int, [P, C.POINTER(RastParams), P, P, P, P]),
     "cg_rast_draw_frames_device": (C.c_int, [P, C.POINTER(RastParams), C.c_int, P, P, P, C.c_size_t, P]),
     "cg_rast_draw_sequence_device": (C.c_int, [P, C.POINTER(RastParams), C.c_int, P, P, P, C.c_size_t, P, P]),
+    "cg_rast_draw_sequence": (C.c_int, [P, C.POINTER(RastParams), C.c_int, P, P, P, C.c_size_t, C.c_int,
+                                        C.POINTER(RastSeqFrame), C.POINTER(Stats)]),
     "cg_rast_set_rand_capacity": (C.c_int, [P, C.c_longlong]),
     "cg_rast_route": (C.c_int, [C.c_longlong]),
     "cg_rast_set_route": (C.c_int, [P, C.c_int]),
@@ -423,6 +425,46 @@ def rast_params(width, height, focal=512.0, cam=(0.0, 0.0, -3.001, 1.0), R=None,
     p.rand_offset = rand_offset
     p.yaw = yaw
     return p
+
+
+# cg_rast_seq_frame as a numpy record (rast_draw_sequence's info)
+RAST_SEQ_DTYPE = np.dtype([("rand_offset", "<u8"), ("n_shaded", "<i8"), ("status", "<i4"), ("pad", "<i4")])
+
+
+def rast_sequence_planes(params_list, out=None, want_depth=False, want_shadow=False, chunk=0, frame_stride=0):
+    """Argument checks and host planes of Context.rast_draw_sequence (no device work):
+    -> (stride, argb, depth, shadow), None for a plane not asked for.  out / want_depth /
+    want_shadow may each be a destination of 4-byte elements (numpy array or torch CPU tensor,
+    pageable or pinned); True allocates one.  The C entry has no capacity argument, so a
+    destination shorter than (n - 1) * stride + W * H pixels is refused here."""
+    n = len(params_list)
+    if not 0 <= chunk <= 64:
+        raise ValueError(f"chunk {chunk}: 0 (= 8) to 64")
+    npx = params_list[0].width * params_list[0].height if n else 0
+    stride = frame_stride or npx
+    if stride < npx:
+        raise ValueError(f"frame_stride {stride} < W*H = {npx}")
+    if any((p.width, p.height) != (params_list[0].width, params_list[0].height) for p in params_list):
+        raise ValueError("frames of one size")
+    need = (n - 1) * stride + npx if n else 0
+
+    def plane(want, dtype, what):
+        if want is None or want is False:
+            return None
+        if want is True:
+            return np.zeros(n * stride, dtype)
+        isnp = isinstance(want, np.ndarray)
+        if (want.itemsize if isnp else want.element_size()) != 4:
+            raise ValueError(f"{what}: 4-byte elements")
+        if not (want.flags["C_CONTIGUOUS"] if isnp else want.is_contiguous()):
+            raise ValueError(f"{what}: contiguous memory")
+        have = want.size if isnp else want.numel()
+        if have < need:
+            raise ValueError(f"{what} holds {have} pixels, {n} frames at stride {stride} need {need}")
+        return want
+
+    return (stride, plane(True if out is None else out, np.uint32, "out"), plane(want_depth, np.float32, "depth"),
+            plane(want_shadow, np.int32, "shadow"))
 
 
 def opacity_map(bgr):
@@ -1033,6 +1075,25 @@ class Context:
             self.h, arr, len(params_list), P(d_argb), P(d_depth) if d_depth else None,
             P(d_shadow) if d_shadow else None, frame_stride, P(d_info) if d_info else None,
             P(stream) if stream else None), "cg_rast_draw_sequence_device")
+
+    def rast_draw_sequence(self, params_list, out=None, want_depth=False, want_shadow=False, chunk=0,
+                           frame_stride=0):
+        """cg_rast_draw_sequence: the frames of rast_draw_sequence_device into host memory, frame f
+        at f * frame_stride pixels (0 = W * H), chunks downloading while the next renders.
+        -> (argb, depth, shadow, info, stats): info the len(params_list) + 1 records
+        (RAST_SEQ_DTYPE), planes not asked for None.  out (and want_depth / want_shadow in place
+        of True) may supply a destination, e.g. a pinned tensor (rast_sequence_planes)."""
+        n = len(params_list)
+        stride, argb, depth, shadow = rast_sequence_planes(params_list, out, want_depth, want_shadow, chunk,
+                                                           frame_stride)
+        ptr = lambda a: None if a is None else P(a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr())  # noqa: E731
+        arr = (RastParams * max(n, 1))(*params_list)
+        info = np.zeros(n + 1, RAST_SEQ_DTYPE)
+        st = Stats()
+        self._check(self.lib.cg_rast_draw_sequence(
+            self.h, arr, n, ptr(argb), ptr(depth), ptr(shadow), stride, chunk,
+            C.cast(info.ctypes.data, C.POINTER(RastSeqFrame)), C.byref(st)), "cg_rast_draw_sequence")
+        return argb, depth, shadow, info, st
 
     def rast_set_route(self, route):
         """Test and A/B hook: -1 automatic, RAST_ROUTE_DENSE / RAST_ROUTE_COMPACT forced."""

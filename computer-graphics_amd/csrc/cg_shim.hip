@@ -290,6 +290,14 @@ struct cg_ctx {
     // rseq_chunks chunks) and the stream's capacity in fragments (0: 4 * W * H)
     DevBuf rseq;
     long long rseq_chunks = 0, rand_cap = 0;
+    // cg_rast_draw_sequence (host output): two sets of plane slots of `chunk` frames (downloaded on
+    // `xfer` as hslot is, with events of their own), the call's n_frames + 1 device records, and their
+    // pinned host copy followed by one int for the last frame's clipped count
+    static constexpr int kRastHostSlots = 2;
+    DevBuf rs_argb[kRastHostSlots], rs_depth[kRastHostSlots], rs_shadow[kRastHostSlots], rs_info;
+    hipEvent_t rs_rdone[kRastHostSlots] = {}, rs_cdone[kRastHostSlots] = {};
+    void *rs_host = nullptr;
+    size_t rs_host_bytes = 0;
     DevBuf sstars, sframe;               // starfield (cg_starfield.hip)
     StarState star;                      // resident stars and frame runs (cg_starfield.hip)
     DevBuf iscratch;                     // JPEG decode (cg_image.hip)
@@ -481,6 +489,13 @@ extern "C" void cg_destroy(cg_ctx *c)
         if (c->ev_cdone[k]) (void)hipEventDestroy(c->ev_cdone[k]);
     }
     if (c->xfer) (void)hipStreamDestroy(c->xfer);
+    c->rs_info.release();
+    for (int k = 0; k < cg_ctx::kRastHostSlots; ++k) {
+        c->rs_argb[k].release(); c->rs_depth[k].release(); c->rs_shadow[k].release();
+        if (c->rs_rdone[k]) (void)hipEventDestroy(c->rs_rdone[k]);
+        if (c->rs_cdone[k]) (void)hipEventDestroy(c->rs_cdone[k]);
+    }
+    if (c->rs_host) (void)hipHostFree(c->rs_host);
     for (auto &q : c->seq) {
         q.dev.release();
         if (q.host) (void)hipHostFree(q.host);
@@ -2342,9 +2357,24 @@ extern "C" int cg_rast_set_rand_capacity(cg_ctx *c, long long fragments)
     return CG_OK;
 }
 
+static int rast_sequence_device(cg_ctx *c, const cg_rast_params *ps, int n_frames, uint32_t *d_argb, float *d_depth,
+                                int32_t *d_shadow, size_t frame_stride, cg_rast_seq_frame *d_info, void *stream,
+                                bool resume, int lane_cap);
+
 extern "C" int cg_rast_draw_sequence_device(cg_ctx *c, const cg_rast_params *ps, int n_frames, uint32_t *d_argb,
                                             float *d_depth, int32_t *d_shadow, size_t frame_stride,
                                             cg_rast_seq_frame *d_info, void *stream)
+{
+    return rast_sequence_device(c, ps, n_frames, d_argb, d_depth, d_shadow, frame_stride, d_info, stream, false, 0);
+}
+
+// cg_rast_draw_sequence_device, and a chunk of cg_rast_draw_sequence.  resume: the first frame
+// starts at the index an earlier call on the same stream left in d_info[0] (its closing record),
+// as every later frame does; ps[0].rand_offset is then ignored too.  lane_cap > 0: at most so
+// many lanes.
+static int rast_sequence_device(cg_ctx *c, const cg_rast_params *ps, int n_frames, uint32_t *d_argb, float *d_depth,
+                                int32_t *d_shadow, size_t frame_stride, cg_rast_seq_frame *d_info, void *stream,
+                                bool resume, int lane_cap)
 {
     if (!c || n_frames < 0 || (n_frames && (!ps || !d_argb))) return CG_E_INVALID;
     if (c->n_room < 0) {
@@ -2385,7 +2415,7 @@ extern "C" int cg_rast_draw_sequence_device(cg_ctx *c, const cg_rast_params *ps,
     // compact-route frames follow each other on `stream` (a lane would hold its own copy of the scratch)
     const bool compact =
         ctx_rast_route(c, kGeomMaxLeaves * ((long long)c->n_room + 7ll * c->n_boxes)) == CG_RAST_ROUTE_COMPACT;
-    const int L = compact ? 1 : std::min(lanes, n_frames);
+    const int L = compact ? 1 : std::min(lane_cap > 0 ? std::min(lanes, lane_cap) : lanes, n_frames);
     if (L > 1) {
         const int rc = rast_lanes_ready(c, L);
         if (rc) return rc;
@@ -2417,7 +2447,7 @@ extern "C" int cg_rast_draw_sequence_device(cg_ctx *c, const cg_rast_params *ps,
         const size_t o = (size_t)f * stride;
         cg_ctx *l = L > 1 ? c->lanes[f % L] : c;
         q.info = d_info + f;
-        q.first = f == 0;
+        q.first = f == 0 && !resume;
         q.win = win[f % L];
         q.wait_ev = L > 1 && f > 0 ? c->seq_ev[(f - 1) % L] : nullptr;
         q.done_ev = L > 1 ? c->seq_ev[f % L] : nullptr;
@@ -2560,4 +2590,182 @@ extern "C" int cg_rast_draw(cg_ctx *c, const cg_rast_params *p, uint32_t *argb, 
         stats->n_tris = n;
     }
     return CG_OK;
+}
+
+// The latest frame's counts on the host (what cg_rast_scratch_info would read), so that they
+// outlive other frames run through the same scratch.
+static int rast_last_resolve(cg_ctx *c)
+{
+    RastLast &L = c->rlast;
+    if (L.route < 0) return CG_OK;
+    CG_TRY(c, hipStreamSynchronize(L.st ? L.st : c->stream), "rast frame");
+    if (L.n < 0 && L.n_dev) {
+        int v = 0;
+        CG_TRY(c, hipMemcpy(&v, L.n_dev, sizeof(int), hipMemcpyDeviceToHost), "d2h count");
+        L.n = v;
+    }
+    if (L.recs < 0 && L.count && L.H > 0) {
+        std::vector<int> cnt((size_t)L.H);
+        CG_TRY(c, hipMemcpy(cnt.data(), L.count, cnt.size() * sizeof(int), hipMemcpyDeviceToHost), "d2h counts");
+        L.recs = 0;
+        for (int v : cnt) L.recs += v;
+    }
+    L.n_dev = L.count = nullptr;
+    return CG_OK;
+}
+
+// n_frames frames into host memory: chunks of `chunk` frames render through the device sequence
+// into two sets of device slots; each chunk's download runs on `xfer` while the next chunk renders
+// (rt_render_frames_host's scheme: chunk j's download is issued after chunk j + 1's render is
+// enqueued).  The call's records are one device array: chunk j + 1 resumes at the record chunk j
+// closed, so the rand() call index never visits the host between chunks.
+extern "C" int cg_rast_draw_sequence(cg_ctx *c, const cg_rast_params *ps, int n_frames, uint32_t *argb, float *depth,
+                                     int32_t *shadow, size_t frame_stride, int chunk, cg_rast_seq_frame *info,
+                                     cg_stats *stats)
+{
+    if (!c || n_frames < 0 || (n_frames && (!ps || !argb))) return CG_E_INVALID;
+    if (chunk < 0 || chunk > 64) return ctx_invalid(c, "draw_sequence: chunk 0 .. 64");
+    if (c->n_room < 0) {
+        c->err = "draw before cg_rast_set_scene";
+        return CG_E_NOSCENE;
+    }
+    if (n_frames == 0) return CG_OK;
+    if (ps[0].width <= 2 || ps[0].height <= 2) return ctx_invalid(c, "draw_sequence: frame size");
+    const size_t px = (size_t)ps[0].width * ps[0].height;
+    const size_t stride = frame_stride ? frame_stride : px;
+    for (int f = 0; f < n_frames; ++f)
+        if (ps[f].colour_mode < 0 || ps[f].colour_mode > 2 || ps[f].width != ps[0].width ||
+            ps[f].height != ps[0].height || stride < px)
+            return ctx_invalid(c, "draw_sequence: colour modes 0-2, frames of one size, frame_stride >= W * H");
+    auto t0 = std::chrono::steady_clock::now();
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    const int ch = std::min(chunk ? chunk : 8, n_frames);
+    // Lanes of a chunk's render (CG_RAST_HOST_LANES for A/B runs): 2.  The process's streams share
+    // its 4 hardware queues, so with the device form's 6 lanes the transfer stream's copy sits in
+    // a queue behind a lane's kernels of the next chunk, which wait for the previous download:
+    // the link idles for a chunk's render time per chunk.  1080p, 64 frames a call into pinned
+    // memory, mode 0: 1 lane 6.26k frames/s, 2 6.35k, 3 6.29k, 4 6.27k, 6 5.0k (a third slot set
+    // 5.8k, 16 hardware queues 5.5k); mode 1: 2 lanes 3.6k, 3 3.2k, 4 3.4k, 6 3.15k.
+    static const int host_lanes = [] {
+        const char *e = std::getenv("CG_RAST_HOST_LANES");
+        return std::max(1, std::min(e ? std::atoi(e) : 2, (int)cg_ctx::kRastLanes));
+    }();
+    constexpr int NS = cg_ctx::kRastHostSlots;
+    if (!c->xfer) {
+        CG_TRY(c, hipStreamCreateWithFlags(&c->xfer, hipStreamNonBlocking), "copy stream");
+        for (int k = 0; k < 2; ++k) {
+            CG_TRY(c, hipEventCreateWithFlags(&c->ev_rdone[k], hipEventDisableTiming), "copy event");
+            CG_TRY(c, hipEventCreateWithFlags(&c->ev_cdone[k], hipEventDisableTiming), "copy event");
+        }
+    }
+    for (int k = 0; k < NS; ++k) {
+        if (c->rs_rdone[k]) continue;
+        CG_TRY(c, hipEventCreateWithFlags(&c->rs_rdone[k], hipEventDisableTiming), "copy event");
+        CG_TRY(c, hipEventCreateWithFlags(&c->rs_cdone[k], hipEventDisableTiming), "copy event");
+    }
+    // Every return below, error or not, leaves nothing of this call running (rt_render_frames_host).
+    struct Drain {
+        cg_ctx *c;
+        ~Drain()
+        {
+            (void)hipStreamSynchronize(c->xfer);
+            (void)hipStreamSynchronize(c->stream);
+        }
+    } drain_on_exit{c};
+    for (int k = 0; k < NS; ++k) {
+        CG_TRY(c, c->rs_argb[k].ensure((size_t)ch * px * sizeof(uint32_t)), "alloc frame slots");
+        if (depth) CG_TRY(c, c->rs_depth[k].ensure((size_t)ch * px * sizeof(float)), "alloc depth slots");
+        if (shadow) CG_TRY(c, c->rs_shadow[k].ensure((size_t)ch * px * sizeof(int32_t)), "alloc shadow slots");
+    }
+    const size_t rec_bytes = ((size_t)n_frames + 1) * sizeof(cg_rast_seq_frame);
+    CG_TRY(c, c->rs_info.ensure(rec_bytes), "alloc records");
+    if (c->rs_host_bytes < rec_bytes + sizeof(int)) {
+        if (c->rs_host) (void)hipHostFree(c->rs_host);
+        c->rs_host = nullptr;
+        c->rs_host_bytes = 0;
+        CG_TRY(c, hipHostMalloc(&c->rs_host, rec_bytes + sizeof(int), hipHostMallocDefault), "alloc host records");
+        c->rs_host_bytes = rec_bytes + sizeof(int);
+    }
+    cg_rast_seq_frame *d_info = (cg_rast_seq_frame *)c->rs_info.p, *rec = (cg_rast_seq_frame *)c->rs_host;
+    int *h_ntris = (int *)((char *)c->rs_host + rec_bytes);
+    const int nchunks = (n_frames + ch - 1) / ch;
+    auto plane = [&](void *dst, const void *src, int f0, int nf) -> hipError_t {   // 4-byte pixels
+        if (stride == px)
+            return hipMemcpyAsync((uint32_t *)dst + (size_t)f0 * px, src, (size_t)nf * px * 4, hipMemcpyDeviceToHost,
+                                  c->xfer);
+        for (int f = 0; f < nf; ++f) {
+            const hipError_t e = hipMemcpyAsync((uint32_t *)dst + (size_t)(f0 + f) * stride,
+                                                (const uint32_t *)src + (size_t)f * px, px * 4, hipMemcpyDeviceToHost,
+                                                c->xfer);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    };
+    auto download = [&](int j) -> int {
+        const int s = j % NS, f0 = j * ch, nf = std::min(ch, n_frames - f0);
+        CG_TRY(c, hipStreamWaitEvent(c->xfer, c->rs_rdone[s], 0), "copy wait");
+        CG_TRY(c, plane(argb, c->rs_argb[s].p, f0, nf), "download frames");
+        if (depth) CG_TRY(c, plane(depth, c->rs_depth[s].p, f0, nf), "download depth");
+        if (shadow) CG_TRY(c, plane(shadow, c->rs_shadow[s].p, f0, nf), "download shadow");
+        CG_TRY(c, hipEventRecord(c->rs_cdone[s], c->xfer), "copy event");
+        return CG_OK;
+    };
+    CG_TRY(c, hipEventRecord(c->ev0, c->stream), "event");
+    for (int j = 0; j < nchunks; ++j) {
+        const int s = j % NS, f0 = j * ch, nf = std::min(ch, n_frames - f0);
+        if (j >= NS) CG_TRY(c, hipStreamWaitEvent(c->stream, c->rs_cdone[s], 0), "slot wait");   // chunk j - NS downloaded
+        int rc = rast_sequence_device(c, ps + f0, nf, (uint32_t *)c->rs_argb[s].p,
+                                      depth ? (float *)c->rs_depth[s].p : nullptr,
+                                      shadow ? (int32_t *)c->rs_shadow[s].p : nullptr, px, d_info + f0, c->stream, j > 0,
+                                      host_lanes);
+        if (rc) return rc;
+        CG_TRY(c, hipEventRecord(c->rs_rdone[s], c->stream), "render event");
+        if (j >= 1 && (rc = download(j - 1))) return rc;
+    }
+    CG_TRY(c, hipEventRecord(c->ev1, c->stream), "event");
+    if (int rc = download(nchunks - 1)) return rc;
+    CG_TRY(c, hipMemcpyAsync(rec, d_info, rec_bytes, hipMemcpyDeviceToHost, c->stream), "d2h records");
+    *h_ntris = (int)std::max(c->rlast.n, 0ll);
+    if (stats && c->rlast.n < 0 && c->rlast.n_dev)
+        CG_TRY(c, hipMemcpyAsync(h_ntris, c->rlast.n_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream), "d2h count");
+    CG_TRY(c, hipStreamSynchronize(c->xfer), "download frames");
+    CG_TRY(c, hipStreamSynchronize(c->stream), "rast frames");
+    float kernel_ms = 0.f;
+    (void)hipEventElapsedTime(&kernel_ms, c->ev0, c->ev1);
+    // A frame the stream's capacity could not hold was flagged and left undrawn, the chain exact:
+    // it renders alone from its record through the single-frame path, straight into its host slot.
+    int rc_out = CG_OK;
+    long long shaded = -1;
+    bool kept = false;
+    const bool last_flagged = rec[n_frames - 1].status != 0;   // then the last repair is the last frame
+    RastLast last;
+    for (int f = 0; f < n_frames; ++f) {
+        if (ps[f].colour_mode != 0) shaded = std::max(shaded, 0ll) + rec[f].n_shaded;
+        if (rec[f].status == 0 || rc_out) continue;
+        if (rec[f].status == CG_E_CAPACITY) {
+            if (!kept && !last_flagged) {   // cg_rast_scratch_info reports the call's last frame
+                if (const int rc = rast_last_resolve(c)) return rc;
+                last = c->rlast;
+                kept = true;
+            }
+            cg_rast_params p = ps[f];
+            p.rand_offset = rec[f].rand_offset;
+            const int rc = cg_rast_draw(c, &p, argb + (size_t)f * stride, depth ? depth + (size_t)f * stride : nullptr,
+                                        shadow ? shadow + (size_t)f * stride : nullptr, nullptr);
+            if (rc == CG_OK) rec[f].status = 0;
+            else rc_out = rc;
+        } else {
+            rc_out = rec[f].status;
+        }
+    }
+    if (kept) c->rlast = last;
+    if (info) std::memcpy(info, rec, rec_bytes);
+    if (stats) {
+        stats->kernel_ms = kernel_ms;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->n_tris = *h_ntris;
+        stats->n_spans = 0;
+        stats->n_shaded = shaded;
+    }
+    return rc_out;
 }

@@ -16,7 +16,15 @@
 // reference tree); they are decoded like cv::imread does (cg_image_decode_jpeg).
 //
 //   rasteriser [--width W] [--height H] [--focal F] [--keys KEYS] [--out FILE]
-//              [--setting S] [--setting-boxes B] [--textures DIR]
+//              [--setting S] [--setting-boxes B] [--textures DIR] [--batch]
+//
+// --batch: Update() runs over the whole key script first, each frame's globals
+// are recorded as a cg_rast_params, and one cg_rast_draw_sequence call renders
+// every frame (the rand() call index chained on the device); the screenshot is
+// the last frame and randCalls the closing record, as without the flag.  What
+// Draw carries from frame to frame besides, indirectLightPowerPerArea, follows
+// Draw's own rule while recording, with the frame's clipped triangle count
+// from cg_rast_prepare.
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -54,8 +62,8 @@ static void die(int rc, const char *what)
     exit(1);
 }
 
-// skeleton.cpp:203-308
-void Draw(screen *screen)
+// the globals as Draw hands them to the library
+static cg_rast_params CurrentParams(const screen *screen)
 {
     cg_rast_params p;
     p.width = screen->width;
@@ -70,6 +78,13 @@ void Draw(screen *screen)
     p.colour_mode = randColourSelect;
     p.yaw = yaw;
     p.rand_offset = randCalls;
+    return p;
+}
+
+// skeleton.cpp:203-308
+void Draw(screen *screen)
+{
+    const cg_rast_params p = CurrentParams(screen);
     // geometry (shadow volumes + clip), fill and post-pass all on the GPU
     cg_stats st;
     int rc = cg_rast_draw(g_ctx, &p, screen->buffer, nullptr, nullptr, &st);
@@ -149,8 +164,15 @@ int main(int argc, char *argv[])
 {
     string out = "screenshot.bmp", tex_dir;
     int setting = 0, setting_boxes = 0;
-    for (int i = 1; i + 1 < argc; i += 2) {
+    bool batch = false;
+    for (int i = 1; i < argc; i += 2) {
         string a = argv[i];
+        if (a == "--batch") {
+            batch = true;
+            --i;
+            continue;
+        }
+        if (i + 1 >= argc) break;
         if (a == "--width") SCREEN_WIDTH = atoi(argv[i + 1]);
         else if (a == "--height") SCREEN_HEIGHT = atoi(argv[i + 1]);
         else if (a == "--focal") focalLength = (float)atof(argv[i + 1]);
@@ -182,9 +204,36 @@ int main(int argc, char *argv[])
     rc = cg_rast_set_scene(g_ctx, reinterpret_cast<const cg_rtri *>(originalroom.data()), (int)originalroom.size(),
                            reinterpret_cast<const cg_rtri *>(originalbox.data()), (int)originalbox.size());
     if (rc) die(rc, "cg_rast_set_scene");
-    while (Update()) {
-        Draw(screen);
-        SDL_Renderframe(screen);
+    if (batch) {
+        // the main loop's frames in one call: each Update()'s globals recorded, then every Draw()
+        vector<cg_rast_params> ps;
+        while (Update()) {
+            ps.push_back(CurrentParams(screen));
+            if (randColourSelect == 0) {   // Draw's rule (:585), the count without a buffer
+                const int n = cg_rast_prepare(&ps.back(), reinterpret_cast<const cg_rtri *>(originalroom.data()),
+                                              (int)originalroom.size(),
+                                              reinterpret_cast<const cg_rtri *>(originalbox.data()),
+                                              (int)originalbox.size(), nullptr, 0, nullptr);
+                if (n < 0) die(n, "cg_rast_prepare");
+                if (n > 0) indirectLightPowerPerArea = 0.2f * vec3(1, 1, 1);
+            }
+        }
+        if (!ps.empty()) {
+            const size_t px = (size_t)screen->width * screen->height;
+            vector<uint32_t> frames(ps.size() * px);
+            vector<cg_rast_seq_frame> info(ps.size() + 1);
+            rc = cg_rast_draw_sequence(g_ctx, ps.data(), (int)ps.size(), frames.data(), nullptr, nullptr, 0, 0,
+                                       info.data(), nullptr);
+            if (rc) die(rc, "cg_rast_draw_sequence");
+            randCalls = info.back().rand_offset;
+            memcpy(screen->buffer, frames.data() + (ps.size() - 1) * px, px * sizeof(uint32_t));
+            SDL_Renderframe(screen);
+        }
+    } else {
+        while (Update()) {
+            Draw(screen);
+            SDL_Renderframe(screen);
+        }
     }
     SDL_SaveImage(screen, out.c_str());
     KillSDL(screen);

@@ -541,6 +541,30 @@ typedef struct { uint64_t rand_offset; int64_t n_shaded; int32_t status; int32_t
 int cg_rast_draw_sequence_device(cg_ctx *ctx, const cg_rast_params *ps, int n_frames, uint32_t *d_argb,
                                  float *d_depth, int32_t *d_shadow, size_t frame_stride,
                                  cg_rast_seq_frame *d_info, void *stream);
+/* Host-memory form: the frames of cg_rast_draw_sequence_device (the same chain: it starts at
+ * ps[0].rand_offset, ps[f > 0].rand_offset is ignored, each frame takes ps[f].indirect_first as
+ * given) into caller-owned host memory, pageable or pinned: frame f at argb + f * frame_stride
+ * pixels (0: W * H; below W * H CG_E_INVALID), likewise depth / shadow (may be NULL); pixels
+ * between frames are not written.  Every plane equals what cg_rast_draw leaves for the same
+ * params at the chained index.  info (host, optional): n_frames + 1 records as d_info.
+ * The frames render `chunk` at a time (0: 8, at most 64) through the device sequence into two
+ * sets of context-owned device slots; chunk j downloads on the context's transfer stream while
+ * chunk j + 1 renders, like cg_rt_render_frames.  The records are one device array for the whole
+ * call and a chunk's first frame reads its start index from the record the previous chunk closed:
+ * the index is never read back between chunks.  A frame flagged CG_E_CAPACITY is then rendered
+ * alone with cg_rast_draw at its recorded index, straight into its host slot, and reports status
+ * 0; a status that is non-zero on return means that frame is not in host memory, and the call
+ * returns that code.  Both routes as the device form (compact-route frames in turn; modes 1-2
+ * refused there).  stats (optional): kernel_ms the device time spanning the renders, total_ms the
+ * call, n_tris the last frame's clipped count, n_shaded the sum over the mode 1-2 frames (-1: none).
+ * Returns when every frame, and info, is in host memory; the only host waits are those of the
+ * downloads and the closing synchronise.  Slots and records grow only: after the first call of a
+ * size the call allocates nothing.  cg_rast_scratch_info afterwards reports the last frame.
+ * CG_E_NOSCENE before cg_rast_set_scene; CG_E_INVALID for NULL ps / argb with n_frames > 0,
+ * frames of several sizes, a colour mode outside 0-2, chunk < 0 or > 64, a bad stride;
+ * n_frames == 0 returns CG_OK and touches nothing. */
+int cg_rast_draw_sequence(cg_ctx *ctx, const cg_rast_params *ps, int n_frames, uint32_t *argb, float *depth,
+                          int32_t *shadow, size_t frame_stride, int chunk, cg_rast_seq_frame *info, cg_stats *stats);
 /* Test hook: capacity of the materialised rand() stream in fragments (3 values each);
  * 0 = automatic, 4 * W * H. */
 int cg_rast_set_rand_capacity(cg_ctx *ctx, long long fragments);
