@@ -175,6 +175,8 @@ _SIGS = {
     "cg_rast_set_rand_capacity": (C.c_int, [P, C.c_longlong]),
     "cg_rast_route": (C.c_int, [C.c_longlong]),
     "cg_rast_set_route": (C.c_int, [P, C.c_int]),
+    "cg_rast_set_route_limit": (C.c_int, [P, C.c_longlong]),
+    "cg_rast_span_segments": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "cg_rast_scratch_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
     "cg_rast_row_blocks": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "cg_rast_random_scene": (C.c_int, [C.c_uint64, C.c_int, C.c_float, C.POINTER(RTri)]),
@@ -392,6 +394,13 @@ def rt_grid_dims(vmin, vmax, n_tris):
 def rast_route(list_capacity):
     """cg_rast_route (host-only): the route a frame of this list capacity takes automatically."""
     return load().cg_rast_route(list_capacity)
+
+
+def rast_span_segments(lx, rx, width):
+    """cg_rast_span_segments (host-only): (count, first) of the 64-pixel fill segments a span's visible extent overlaps."""
+    first = C.c_int(0)
+    n = load().cg_rast_span_segments(lx, rx, width, C.byref(first))
+    return n, first.value
 
 
 def rast_row_blocks():
@@ -1098,6 +1107,10 @@ class Context:
     def rast_set_route(self, route):
         """Test and A/B hook: -1 automatic, RAST_ROUTE_DENSE / RAST_ROUTE_COMPACT forced."""
         self._check(self.lib.cg_rast_set_route(self.h, route), "cg_rast_set_route")
+
+    def rast_set_route_limit(self, list_capacity):
+        """Test and A/B hook: the list capacity above which frames take the compact route automatically (0: 131072)."""
+        self._check(self.lib.cg_rast_set_route_limit(self.h, list_capacity), "cg_rast_set_route_limit")
 
     def rast_scratch_info(self):
         """Rasteriser scratch after the latest frame (waits for it): dict(bytes, route, tris, spans, recs)."""

@@ -253,7 +253,9 @@ enum KtId {
     KT_RT_PREPARE, KT_RT_TILE_CERT, KT_RT_LATTICE_UNITS, KT_RT_LATTICE, KT_RT_LATTICE_LIGHTS, KT_RT_PIXEL,
     KT_RT_BIG_PRIMARY, KT_RT_SHADOW_HINTS, KT_RT_BIG_FRAME, KT_RAST_FILL, KT_RAST_POST,
     // the compact rasteriser route's phases (cg_rast_big.hip), each a scope over its launches
-    KT_RAST_BIG_CLIP, KT_RAST_BIG_SETUP, KT_RAST_BIG_ROWS, KT_RAST_BIG_FILL, KT_RAST_BIG_POST, KT_COUNT
+    KT_RAST_BIG_CLIP, KT_RAST_BIG_SETUP, KT_RAST_BIG_ROWS, KT_RAST_BIG_FILL, KT_RAST_BIG_POST,
+    // its colour modes 1-2: segments + count + scans, the generator, number + shade
+    KT_RAST_BIG_COUNT, KT_RAST_BIG_RAND, KT_RAST_BIG_SHADE, KT_COUNT
 };
 // HIP events on `st` around the scope's launches while timing is on (id
 // outside [0, KT_COUNT): nothing).

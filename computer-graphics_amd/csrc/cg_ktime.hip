@@ -23,6 +23,7 @@ static const char *const kKtNames[KT_COUNT] = {
     "rt_lattice_lights_kernel", "rt_pixel_kernel",       "rt_big_primary_kernel",   "rt_shadow_hints_kernel",
     "rt_big_frame",             "rast_fill_kernel",      "rast_post_kernel",        "rast_big_clip",
     "rast_big_setup",           "rast_big_rows",         "rast_big_fill",           "rast_big_post",
+    "rast_big_count",           "rast_big_rand",         "rast_big_shade",
 };
 
 namespace {

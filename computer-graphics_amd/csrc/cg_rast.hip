@@ -612,6 +612,16 @@ __global__ __launch_bounds__(256) void rast_post_kernel(const cg_rtri *__restric
     }
 }
 
+// The colour modes' post-pass over a float4 state and a shadow plane, for the compact route's
+// modes 1-2 (cg_rast_big.hip): the launch below, without a status word.
+void launch_rast_post_direct(const RastArgs &A, const float4 *state, const int32_t *shadow, uint32_t *d_argb,
+                             hipStream_t st)
+{
+    hipLaunchKernelGGL((rast_post_kernel<true, false>), dim3(xcd_grid(A.H, (A.W + kPostTW - 1) / kPostTW)), dim3(256), 0,
+                       st, A.tris, A, (const void *)state, (const RowRec *)nullptr, shadow, d_argb,
+                       (const int32_t *)nullptr);
+}
+
 int rast_colour_fill(cg_ctx *c, const RastArgs &A, const cg_rast_params *p, const RowRec *recs, const int *count,
                      const RastHdr *hdr, const int *n_dev, int max_recs, float4 *state, float *d_depth,
                      int32_t *shadow, hipStream_t st, long long *n_shaded);

@@ -4,7 +4,7 @@
 // capacity x H and tests every header slot on every row.  This route renders
 // the same Draw with scratch and work that follow what the frame covers; every
 // plane is bit-identical to the dense route's (the arithmetic below is the
-// dense kernels', only the addressing differs).  Colour mode 0 only.
+// dense kernels', only the addressing differs).
 //
 // Launches per frame, all order-exact (no atomic decides an order):
 //   1. rast_clip_kernel (cg_geometry.hip, unchanged) stages each input
@@ -27,6 +27,25 @@
 //      at row_off[y] + base + rank.
 //   4. rast_big_fill_kernel / rast_big_post_kernel: rast_fill_kernel / the
 //      mode-0 rast_post_kernel reading recs + row_off[y].
+// Colour modes 1-2 (every shaded fragment draws three rand() values, in the
+// reference's fragment order: triangle by triangle, row by row, left to right)
+// replace 4 by an order the layout already holds -- the spans lie in (triangle,
+// row) order:
+//   5. rast_big_segs_kernel: the kFillPx-pixel fill segments each span's visible
+//      extent overlaps (cg_rast_span_segments; 0 for shadow volumes, which never
+//      shade); big_scan gives seg_off[span]; the host reads the total N, and the
+//      row-list write pass leaves seg_off[span] beside every record.
+//   6. rast_big_colour_kernel<false>: the fill's walk, one wave per (row,
+//      segment), with the ordered z-buffer alone; the fragments of each record
+//      that pass it go to c[seg_off[span] + segment - the span's first]: one
+//      writer an entry.  big_scan over c numbers them: entries lie in (triangle,
+//      row, x) order, so fbase[entry] is the frame-wide number of the entry's
+//      first shaded fragment and fbase[N] is S, which the host reads.
+//   7. the generator of cg_rast_colour.hip makes exactly 3 S values;
+//      rast_big_colour_kernel<true> repeats the walk, numbers a passing fragment
+//      fbase[entry] + the passing lanes below it, and shades each pixel's last
+//      winner as rast_fill_rand_kernel does; the dense rast_post_kernel<true,
+//      false> finishes the frame.
 // Every store is bounded by its buffer's capacity; no kernel waits on another.
 #include <algorithm>
 
@@ -44,6 +63,10 @@ hipError_t launch_rast_clip(const cg_rast_params &prm, const cg_rtri *d_room, in
 int rast_make_args(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *p, cg_vec4 light,
                    const cg_vec4 *d_light, int tex_mask, RastArgs *out);
 int rast_seq_chain_mode0(cg_ctx *c, hipStream_t st, const RastSeq &q);
+int rast_seq_chain_exact(cg_ctx *c, hipStream_t st, const RastSeq &q, const long long *total);
+int rast_rand_stream(cg_ctx *c, int rnd_buf, int jt_buf, uint64_t offset, long long S, hipStream_t st, int32_t **out);
+void launch_rast_post_direct(const RastArgs &A, const float4 *state, const int32_t *shadow, uint32_t *d_argb,
+                             hipStream_t st);
 
 typedef unsigned long long u64;
 
@@ -350,14 +373,16 @@ __device__ __forceinline__ bool batch_rank(const RastArgs &A, const RastSpan *__
 
 // One wave per chunk of kBigChunk spans.  WRITE = false: hist[chunk][y] = the
 // chunk's records of row y.  WRITE = true: hist holds the chunk's base in each
-// row (rast_big_colscan_kernel) and the records are stored.
-template <bool WRITE>
+// row (rast_big_colscan_kernel) and the records are stored; ENT (colour modes
+// 1-2): with seg_off[span], the record's first entry of c, beside each.
+template <bool WRITE, bool ENT>
 __global__ __launch_bounds__(64) void rast_big_rows_kernel(RastArgs A, const RastSpan *__restrict__ spans,
                                                           const uint2 *__restrict__ span_ty, u64 n_spans,
                                                           int *__restrict__ hist, const RastHdr *__restrict__ hdr,
                                                           const int *__restrict__ first_tri,
                                                           const u64 *__restrict__ row_off, RowRec *__restrict__ recs,
-                                                          u64 rec_cap)
+                                                          u64 rec_cap, const u64 *__restrict__ seg_off,
+                                                          u64 *__restrict__ rec_ent)
 {
     extern __shared__ int s_cnt[];                          // [H]
     const int lane = threadIdx.x;
@@ -386,6 +411,7 @@ __global__ __launch_bounds__(64) void rast_big_rows_kernel(RastArgs A, const Ras
                 r.tex = h.tex; r.index = h.index;
                 const u64 o = row_off[ty.y] + (u64)(unsigned)(base + rank);
                 if (o < rec_cap) recs[o] = r;
+                if (ENT && o < rec_cap) rec_ent[o] = seg_off[b + lane];
             }
         }
     }
@@ -671,11 +697,141 @@ __global__ __launch_bounds__(256) void rast_big_post_kernel(const cg_rtri *__res
     }
 }
 
+// ---- 5-7. colour modes 1-2 ----
+// nseg[s]: the entries of c that span s takes, one per fill segment its visible extent overlaps
+__global__ __launch_bounds__(256) void rast_big_segs_kernel(RastArgs A, const RastSpan *__restrict__ spans,
+                                                           const uint2 *__restrict__ span_ty, u64 n_spans,
+                                                           const RastHdr *__restrict__ hdr, int *__restrict__ nseg)
+{
+    const u64 s = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (s >= n_spans) return;
+    const uint2 ty = span_ty[s];
+    int k = 0, first;
+    if (ty.x < (unsigned)A.n && ty.y < (unsigned)A.H && (hdr[ty.x].t_sh >> 31) == 0u)   // as batch_rank keeps them
+        k = rast_span_segments(spans[s].lx, spans[s].rx, A.W, &first);
+    nseg[s] = k;
+}
+
+// rast_big_fill_kernel's walk with the ordered z-buffer of rast_count_kernel / rast_fill_rand_kernel.
+// SHADE = false: c[entry] = the fragments of the record that pass in this segment (lane q keeps
+// the count of record base + q and stores it after the batch).  SHADE = true: a passing fragment
+// takes the number fbase[entry] + the passing lanes below it, and each pixel's last winner is
+// shaded with its three values into the kStateDirect state.
+template <bool SHADE>
+__global__ __launch_bounds__(256) void rast_big_colour_kernel(RastArgs A0, const RowRec *__restrict__ recs,
+                                                             const u64 *__restrict__ row_off,
+                                                             const int *__restrict__ count, u64 rec_cap,
+                                                             const u64 *__restrict__ rec_ent, u64 n_ent,
+                                                             int *__restrict__ c, const u64 *__restrict__ fbase,
+                                                             const int32_t *__restrict__ rnd, long long n_shaded,
+                                                             int mode, float4 *__restrict__ state,
+                                                             float *__restrict__ depth_out,
+                                                             int32_t *__restrict__ shadow_out)
+{
+    const RastArgs A = SHADE ? with_device_light(A0) : A0;
+    const int segs = (A.W + kFillPx - 1) / kFillPx;
+    int m;
+    const int g = xcd_group(A.H, (segs * kXcdRows + 3) / 4, m);
+    if (g < 0) return;
+    const int unit = m * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (row, segment) in the group
+    const int lane = threadIdx.x & 63;
+    const int y = g * kXcdRows + unit / segs;
+    if (unit >= segs * kXcdRows || y >= A.H) return;
+    const int seg = unit % segs, x0 = seg * kFillPx;
+    const int x = x0 + lane;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    float depth = 0.0f;                                   // :247
+    int shadow = 0, win = -1;                             // :259; record of the last shading fragment
+    long long widx = 0;                                   // its number among the frame's shaded fragments
+    const u64 ro = min(row_off[y], rec_cap);
+    const int cnt = (int)min((u64)(unsigned)max(count[y], 0), rec_cap - ro);
+    const RowRec *rr = recs + ro;
+    for (int base = 0; base < cnt; base += 64) {
+        const int q = base + lane;
+        int mlx = 0, mrx = 0, msh = 0;
+        float mlz = 0.f, msz = 0.f;
+        u64 ment = 0;
+        if (q < cnt) {
+            const RowRec &mr = rr[q];
+            mlx = mr.lx; mrx = mr.rx; mlz = mr.lz; msz = mr.sz; msh = rec_shadow(mr);
+            ment = rec_ent[ro + q];
+        }
+        const bool ov = q < cnt && !(mrx - 1 < x0 || mlx > x0 + kFillPx - 1);
+        // the record's entry for this segment: seg_off[span] + (segment - the span's first)
+        int first;
+        const int ns = rast_span_segments(mlx, mrx, A.W, &first);
+        const u64 ent = ment + (u64)(unsigned)(seg - first);
+        const bool own = ov && !msh && seg >= first && seg - first < ns && ent < n_ent;
+        int mine = 0;                                     // SHADE = false: the passes of record base + lane
+        long long mfb = 0;
+        if (SHADE && own) mfb = (long long)fbase[ent];
+        unsigned long long mk = __ballot(SHADE ? ov : own);   // shadow triangles never shade
+        while (mk) {
+            const int b = __builtin_ctzll(mk);
+            mk &= mk - 1ull;
+            // every readlane sits here, where the whole wave is active (see rast_fill_kernel)
+            const int lx = __builtin_amdgcn_readlane(mlx, b);
+            const int rx = __builtin_amdgcn_readlane(mrx, b);
+            const float lz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mlz), b));
+            const float sz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(msz), b));
+            const int shd = SHADE ? __builtin_amdgcn_readlane(msh, b) : 0;
+            long long fb = 0;
+            if (SHADE)
+                fb = (long long)(((u64)(unsigned)__builtin_amdgcn_readlane((int)((u64)mfb >> 32), b) << 32) |
+                                 (u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)mfb, b));
+            const int i = x - lx;
+            const bool in = x < A.W && i >= 0 && x < rx;             // :504, :573
+            const float zinv = lz + (sz * (float)i);                 // :543
+            if (!shd) {
+                const bool pass = in && zinv >= depth;               // :574
+                const unsigned long long pm = __ballot(pass);
+                if (pass) {
+                    depth = zinv;                                    // :665
+                    win = base + b;
+                    widx = fb + __popcll(pm & below);
+                }
+                if (!SHADE && lane == b) mine = __popcll(pm);
+            } else if (in && zinv > depth) {                         // :668-669
+                shadow = 1;
+            }
+        }
+        if (!SHADE && own) c[ent] = mine;
+    }
+    if (!SHADE || x >= A.W) return;
+    float4 st = make_float4(__int_as_float(-1), 0.f, 0.f, 0.f);
+    if (win >= 0 && widx >= 0 && widx < n_shaded) {
+        const RowRec r = rr[win];
+        const int i = x - r.lx;
+        const float X = r.lX + (r.sX * (float)i);                    // :547-548 numerators
+        const float Y = r.lY + (r.sY * (float)i);
+        const cg_vec4 tn = A.tris[rec_t(r)].normal;
+        const vec3 D = illum_D(A, depth, X, Y, v3(tn.x, tn.y, tn.z));
+        const float r0 = rand_unit(rnd[3 * widx]), r1 = rand_unit(rnd[3 * widx + 1]), r2 = rand_unit(rnd[3 * widx + 2]);
+        const vec3 rc = mode == 1 ? v3(r0, r1, r2) : v3(r0 - 0.2f, 1.0f, r2 - 0.2f);   // :652 / :660
+        const float ind = A.ind_first;                               // modes 1-2 never rewrite it
+        const vec3 sc = rc * (D + v3(ind, ind, ind));
+        st = make_float4(__int_as_float(kStateDirect), sc.x, sc.y, sc.z);
+    }
+    const size_t o = (size_t)y * A.W + x;
+    state[o] = st;
+    if (depth_out) depth_out[o] = depth;
+    shadow_out[o] = shadow;
+}
+
 // ---- host ----
 namespace {
 
 // ctx_buf slots of this route's own buffers (cg_shim.hip: rbig[which - 20])
-enum { kBufTris = 20, kBufPre, kBufNrows, kBufSpanOff, kBufSpanTy, kBufHist, kBufRowOff, kBufScan };
+enum { kBufTris = 20, kBufPre, kBufNrows, kBufSpanOff, kBufSpanTy, kBufHist, kBufRowOff, kBufScan,
+       // colour modes 1-2 only: segments per span, their offsets, each record's first entry, the
+       // entries' fragment counts, their prefix, the rand() stream and its jump table
+       kBufNseg, kBufSegOff, kBufRecEnt, kBufEnt, kBufFbase, kBufRnd, kBufJt };
+
+// The refusal of a colour mode 1-2 frame that cg_rast_set_route(ctx, 1) forced here: the hook is a
+// colour-mode-0 A/B switch (modes 1-2 reach this route on the automatic choice only).
+const char *const kForcedColour =
+    "compact route: colour modes 1-2 are not built for it (their count, scan, generator "
+    "and chain kernels read the dense layout); colour mode 0 only";
 
 // a few bytes the host needs before it can size the next buffer: the documented waits
 int big_read(cg_ctx *c, hipStream_t st, void *dst, const void *src, size_t bytes, const char *what)
@@ -704,6 +860,64 @@ int big_scan(cg_ctx *c, hipStream_t st, const int *in, long long N, u64 *out)
     return e == hipSuccess ? CG_OK : ctx_fail(c, e, "rast_big_scan launch");
 }
 
+// Colour modes 1-2 from the row records on: count, scan, (host: in a sequence the call index,
+// then S), generator, number and shade, post.  seq: the frame's record is written too.
+int big_colour(cg_ctx *c, const RastArgs &A, const cg_rast_params *p, const RowRec *recs, const u64 *row_off,
+               const int *count, u64 n_recs, const u64 *rec_ent, u64 n_ent, float4 *state, uint32_t *d_argb,
+               float *d_depth, int32_t *d_shadow, hipStream_t st, const RastSeq *seq, long long *n_shaded)
+{
+    hipError_t e;
+    const size_t npx = (size_t)A.W * A.H, ne = n_ent > 0 ? (size_t)n_ent : 1;
+    int32_t *shadow = d_shadow;   // the post-pass reads the marks from the plane
+    if (!shadow && !(shadow = (int32_t *)ctx_buf(c, 6, npx * sizeof(int32_t), &e))) return ctx_fail(c, e, "alloc shadow");
+    int *ent = (int *)ctx_buf(c, kBufEnt, ne * sizeof(int), &e);
+    if (!ent) return ctx_fail(c, e, "alloc entry counts");
+    u64 *fbase = (u64 *)ctx_buf(c, kBufFbase, (ne + 1) * sizeof(u64), &e);
+    if (!fbase) return ctx_fail(c, e, "alloc fragment numbers");
+    const int fgrid = xcd_grid(A.H, ((A.W + kFillPx - 1) / kFillPx * kXcdRows + 3) / 4);
+    {
+        KtScope kt(KT_RAST_BIG_COUNT, st);
+        // every entry has one writer; cleared all the same: a hole would be a wrong count, not a stray one
+        if ((e = hipMemsetAsync(ent, 0, ne * sizeof(int), st)) != hipSuccess) return ctx_fail(c, e, "memset");
+        if (n_ent > 0)
+            hipLaunchKernelGGL(rast_big_colour_kernel<false>, dim3(fgrid), dim3(256), 0, st, A, recs, row_off, count,
+                               n_recs, rec_ent, n_ent, ent, (const u64 *)nullptr, (const int32_t *)nullptr, 0ll, 0,
+                               (float4 *)nullptr, (float *)nullptr, (int32_t *)nullptr);
+        if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "rast_big_count launch");
+        if (const int rc = big_scan(c, st, ent, (long long)n_ent, fbase)) return rc;
+    }
+    uint64_t offset = seq ? seq->start : p->rand_offset;
+    if (seq && !seq->first)   // what the previous frame's step left in this frame's record
+        if (const int rc = big_read(c, st, &offset, &seq->info->rand_offset, sizeof(offset), "call index")) return rc;
+    u64 S = 0;
+    if (const int rc = big_read(c, st, &S, fbase + n_ent, sizeof(u64), "shaded-fragment count")) return rc;
+    *n_shaded = (long long)S;
+    int32_t *rnd = nullptr;
+    {
+        KtScope kt(KT_RAST_BIG_RAND, st);
+        if (const int rc = rast_rand_stream(c, kBufRnd, kBufJt, offset, (long long)S, st, &rnd)) return rc;
+    }
+    {
+        KtScope kt(KT_RAST_BIG_SHADE, st);
+        hipLaunchKernelGGL(rast_big_colour_kernel<true>, dim3(fgrid), dim3(256), 0, st, A, recs, row_off, count, n_recs,
+                           rec_ent, n_ent, (int *)nullptr, (const u64 *)fbase, (const int32_t *)rnd, (long long)S,
+                           p->colour_mode, state, d_depth, shadow);
+        if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "rast_big_shade launch");
+    }
+    {
+        KtScope kt(KT_RAST_BIG_POST, st);
+        launch_rast_post_direct(A, state, shadow, d_argb, st);
+        if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "rast_post launch");
+    }
+    if (seq) {
+        const int rc = rast_seq_chain_exact(c, st, *seq, (const long long *)(fbase + n_ent));
+        if (rc) return rc;
+    }
+    // the generator's jump table was uploaded from host memory that a later frame may grow
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return ctx_fail(c, e, "colour frame");
+    return CG_OK;
+}
+
 // Span setup, row lists, fill and post over a clipped list whose length the host knows.
 // clip_ran: rast_clip_kernel initialised the first-fragment minimum on this stream.
 int big_pipeline(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *p, cg_vec4 light,
@@ -711,9 +925,7 @@ int big_pipeline(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *
                  cg_stats *stats, bool events_open, bool clip_ran, int tex_mask, const RastSeq *seq)
 {
     if (p->width <= 2 || p->height <= 2 || p->height > kRastMaxRows) return CG_E_INVALID;
-    if (p->colour_mode != 0)
-        return ctx_invalid(c, "compact route: colour modes 1-2 are not built for it (their count, scan, generator "
-                              "and chain kernels read the dense layout); colour mode 0 only");
+    if (p->colour_mode != 0 && ctx_rast_forced_compact(c)) return ctx_invalid(c, kForcedColour);
     const int W = p->width, H = p->height;
     const size_t npx = (size_t)W * H;
     hipError_t e;
@@ -731,7 +943,9 @@ int big_pipeline(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *
     if (!span_off) return ctx_fail(c, e, "alloc span offsets");
     u64 *row_off = (u64 *)ctx_buf(c, kBufRowOff, ((size_t)H + 2) * sizeof(u64), &e);
     if (!row_off) return ctx_fail(c, e, "alloc row offsets");
-    void *state = ctx_buf(c, 3, npx * sizeof(uint32_t), &e);
+    const bool colour = p->colour_mode != 0;
+    // fill -> post state: 4 B/pixel in colour mode 0, the colour walk's 16 B in modes 1-2
+    void *state = ctx_buf(c, 3, npx * (colour ? sizeof(float4) : sizeof(uint32_t)), &e);
     if (!state) return ctx_fail(c, e, "alloc state");
     hipEvent_t e0, e1;
     ctx_events(c, &e0, &e1);
@@ -765,15 +979,32 @@ int big_pipeline(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *
                            (const u64 *)span_off, n_spans, spans, span_ty, hdr, first_tri);
         if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "rast_big_setup launch");
     }
+    // -- colour modes 1-2: the entries of c each span takes, their offsets
+    u64 *seg_off = nullptr, n_ent = 0;
+    if (colour) {
+        int *nseg = (int *)ctx_buf(c, kBufNseg, ns * sizeof(int), &e);
+        if (!nseg) return ctx_fail(c, e, "alloc span segments");
+        seg_off = (u64 *)ctx_buf(c, kBufSegOff, (ns + 1) * sizeof(u64), &e);
+        if (!seg_off) return ctx_fail(c, e, "alloc segment offsets");
+        {
+            KtScope kt(KT_RAST_BIG_COUNT, st);
+            if (n_spans > 0)
+                hipLaunchKernelGGL(rast_big_segs_kernel, dim3((unsigned)((n_spans + 255) / 256)), dim3(256), 0, st, A,
+                                   (const RastSpan *)spans, (const uint2 *)span_ty, n_spans, (const RastHdr *)hdr, nseg);
+            if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "rast_big_segs launch");
+            if (const int rc = big_scan(c, st, nseg, (long long)n_spans, seg_off)) return rc;
+        }
+        if (const int rc = big_read(c, st, &n_ent, seg_off + n_spans, sizeof(u64), "segment total")) return rc;
+    }
     // -- row lists: count, scan, (host: totals), write
     u64 tot[2] = {0, 0};   // records, the longest row
     {
         KtScope kt(KT_RAST_BIG_ROWS, st);
         if (chunks > 0)
-            hipLaunchKernelGGL(rast_big_rows_kernel<false>, dim3((unsigned)chunks), dim3(64), (size_t)H * sizeof(int), st,
-                               A, (const RastSpan *)spans, (const uint2 *)span_ty, n_spans, hist,
-                               (const RastHdr *)hdr, (const int *)first_tri, (const u64 *)row_off, (RowRec *)nullptr,
-                               (u64)0);
+            hipLaunchKernelGGL((rast_big_rows_kernel<false, false>), dim3((unsigned)chunks), dim3(64),
+                               (size_t)H * sizeof(int), st, A, (const RastSpan *)spans, (const uint2 *)span_ty, n_spans,
+                               hist, (const RastHdr *)hdr, (const int *)first_tri, (const u64 *)row_off,
+                               (RowRec *)nullptr, (u64)0, (const u64 *)nullptr, (u64 *)nullptr);
         hipLaunchKernelGGL(rast_big_colscan_kernel, dim3((H + 63) / 64), dim3(64), 0, st, hist, chunks, H, count);
         hipLaunchKernelGGL(rast_big_rowoff_kernel, dim3(1), dim3(kScanThreads), 0, st, (const int *)count, H, row_off);
         if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "rast_big_rows launch");
@@ -782,46 +1013,63 @@ int big_pipeline(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *
     const u64 n_recs = tot[0];
     RowRec *recs = (RowRec *)ctx_buf(c, 8, (size_t)std::max<u64>(n_recs, 1) * sizeof(RowRec), &e);
     if (!recs) return ctx_fail(c, e, "alloc row records");
-    A.state16 = tot[1] < 32768;
+    A.state16 = !colour && tot[1] < 32768;
+    u64 *rec_ent = nullptr;
+    if (colour && !(rec_ent = (u64 *)ctx_buf(c, kBufRecEnt, (size_t)std::max<u64>(n_recs, 1) * sizeof(u64), &e)))
+        return ctx_fail(c, e, "alloc record entries");
     if (chunks > 0 && n_recs > 0) {
         KtScope kt(KT_RAST_BIG_ROWS, st);
-        hipLaunchKernelGGL(rast_big_rows_kernel<true>, dim3((unsigned)chunks), dim3(64), (size_t)H * sizeof(int), st, A,
-                           (const RastSpan *)spans, (const uint2 *)span_ty, n_spans, hist, (const RastHdr *)hdr,
-                           (const int *)first_tri, (const u64 *)row_off, recs, n_recs);
+        if (colour)
+            hipLaunchKernelGGL((rast_big_rows_kernel<true, true>), dim3((unsigned)chunks), dim3(64),
+                               (size_t)H * sizeof(int), st, A, (const RastSpan *)spans, (const uint2 *)span_ty, n_spans,
+                               hist, (const RastHdr *)hdr, (const int *)first_tri, (const u64 *)row_off, recs, n_recs,
+                               (const u64 *)seg_off, rec_ent);
+        else
+            hipLaunchKernelGGL((rast_big_rows_kernel<true, false>), dim3((unsigned)chunks), dim3(64),
+                               (size_t)H * sizeof(int), st, A, (const RastSpan *)spans, (const uint2 *)span_ty, n_spans,
+                               hist, (const RastHdr *)hdr, (const int *)first_tri, (const u64 *)row_off, recs, n_recs,
+                               (const u64 *)nullptr, (u64 *)nullptr);
         if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "rast_big_rows launch");
     }
-    // -- fill and post
-    {
-        KtScope kt(KT_RAST_BIG_FILL, st);
-        const int fgrid = xcd_grid(H, ((W + kFillPx - 1) / kFillPx * kXcdRows + 3) / 4);
-        if (A.textured)
-            hipLaunchKernelGGL(rast_big_fill_kernel<true>, dim3(fgrid), dim3(256), 0, st, A, (const RowRec *)recs,
-                               (const u64 *)row_off, (const int *)count, n_recs, (uint32_t *)state, d_depth, d_shadow);
-        else
-            hipLaunchKernelGGL(rast_big_fill_kernel<false>, dim3(fgrid), dim3(256), 0, st, A, (const RowRec *)recs,
-                               (const u64 *)row_off, (const int *)count, n_recs, (uint32_t *)state, d_depth, d_shadow);
-        if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "rast_big_fill launch");
-    }
-    {
-        KtScope kt(KT_RAST_BIG_POST, st);
-        const int post_grid = xcd_grid(H, (W + kPostTW - 1) / kPostTW);
-        if (A.textured)
-            hipLaunchKernelGGL(rast_big_post_kernel<true>, dim3(post_grid), dim3(256), 0, st, d_tris, A,
-                               (const void *)state, (const RowRec *)recs, (const u64 *)row_off, n_recs, d_argb);
-        else
-            hipLaunchKernelGGL(rast_big_post_kernel<false>, dim3(post_grid), dim3(256), 0, st, d_tris, A,
-                               (const void *)state, (const RowRec *)recs, (const u64 *)row_off, n_recs, d_argb);
-        if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "rast_big_post launch");
-    }
-    if (seq) {
-        const int rc = rast_seq_chain_mode0(c, st, *seq);
+    long long n_shaded = -1;
+    if (colour) {
+        const int rc = big_colour(c, A, p, recs, row_off, count, n_recs, rec_ent, n_ent, (float4 *)state, d_argb, d_depth,
+                                  d_shadow, st, seq, &n_shaded);
         if (rc) return rc;
+    } else {
+        // -- fill and post
+        {
+            KtScope kt(KT_RAST_BIG_FILL, st);
+            const int fgrid = xcd_grid(H, ((W + kFillPx - 1) / kFillPx * kXcdRows + 3) / 4);
+            if (A.textured)
+                hipLaunchKernelGGL(rast_big_fill_kernel<true>, dim3(fgrid), dim3(256), 0, st, A, (const RowRec *)recs,
+                                   (const u64 *)row_off, (const int *)count, n_recs, (uint32_t *)state, d_depth, d_shadow);
+            else
+                hipLaunchKernelGGL(rast_big_fill_kernel<false>, dim3(fgrid), dim3(256), 0, st, A, (const RowRec *)recs,
+                                   (const u64 *)row_off, (const int *)count, n_recs, (uint32_t *)state, d_depth, d_shadow);
+            if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "rast_big_fill launch");
+        }
+        {
+            KtScope kt(KT_RAST_BIG_POST, st);
+            const int post_grid = xcd_grid(H, (W + kPostTW - 1) / kPostTW);
+            if (A.textured)
+                hipLaunchKernelGGL(rast_big_post_kernel<true>, dim3(post_grid), dim3(256), 0, st, d_tris, A,
+                                   (const void *)state, (const RowRec *)recs, (const u64 *)row_off, n_recs, d_argb);
+            else
+                hipLaunchKernelGGL(rast_big_post_kernel<false>, dim3(post_grid), dim3(256), 0, st, d_tris, A,
+                                   (const void *)state, (const RowRec *)recs, (const u64 *)row_off, n_recs, d_argb);
+            if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "rast_big_post launch");
+        }
+        if (seq) {
+            const int rc = rast_seq_chain_mode0(c, st, *seq);
+            if (rc) return rc;
+        }
     }
     if (stats && (e = hipEventRecord(e1, st)) != hipSuccess) return ctx_fail(c, e, "event");
     if (stats) {
         stats->n_tris = n;
         stats->n_spans = 0;   // as the dense route reports it; the frame's spans: cg_rast_scratch_info
-        stats->n_shaded = -1;
+        stats->n_shaded = n_shaded;
     }
     *ctx_rast_last(c) = RastLast{CG_RAST_ROUTE_COMPACT, (long long)n, (long long)n_spans, (long long)n_recs, nullptr,
                                  nullptr, H, st};
@@ -844,9 +1092,7 @@ int rast_big_draw(cg_ctx *c, const cg_rtri *d_room, int n_room, const cg_rtri *d
                   cg_stats *stats, int **n_out, int tex_mask, const RastSeq *seq)
 {
     if (p->width <= 2 || p->height <= 2 || p->height > kRastMaxRows || p->focal == 0.0f) return CG_E_INVALID;
-    if (p->colour_mode != 0)
-        return ctx_invalid(c, "compact route: colour modes 1-2 are not built for it (their count, scan, generator "
-                              "and chain kernels read the dense layout); colour mode 0 only");
+    if (p->colour_mode != 0 && ctx_rast_forced_compact(c)) return ctx_invalid(c, kForcedColour);
     const long long n_in_ll = (long long)n_room + 7ll * n_boxes;
     if (n_in_ll > kRastMaxInputs) return ctx_invalid(c, "more than 4194304 input triangles");
     const int n_in = (int)n_in_ll;

@@ -36,15 +36,6 @@ int ctx_fail(cg_ctx *c, hipError_t e, const char *what);
 
 constexpr int kRandChunk = 31 * 32;    // rand() values per generator thread
 
-__device__ __forceinline__ RastArgs with_device_light(RastArgs A)
-{
-    if (A.d_light) {                                      // light from the device geometry (:223)
-        const cg_vec4 L = *A.d_light;
-        A.light[0] = L.x; A.light[1] = L.y; A.light[2] = L.z;
-    }
-    return A;
-}
-
 // The row's records (lane q holds record base + q) overlapping [x0, x0 + 63].
 struct RecLane {
     int lx, rx, shd;
@@ -314,14 +305,6 @@ __global__ __launch_bounds__(256) void rast_rand_dev_kernel(const uint32_t *__re
     rand_chunk(w, jt, b, nvals, out);
 }
 
-// LO + rand() / (RAND_MAX/HI - LO), all float (skeleton.cpp:563-565, :649-651)
-__device__ __forceinline__ float rand_unit(int32_t v)
-{
-    const float LO = 0.2f, HI = 0.5f;
-    const float den = (float)2147483647 / HI - LO;        // RAND_MAX / HI - LO
-    return LO + (float)v / den;
-}
-
 __global__ __launch_bounds__(64) void rast_fill_rand_kernel(RastArgs A0, const RowRec *__restrict__ recs,
                                                           const int *__restrict__ count, const int *__restrict__ pc,
                                                           const long long *__restrict__ tbase,
@@ -420,6 +403,32 @@ static const std::vector<uint32_t> &rand_jump_table(long long nb)
     return jtab;
 }
 
+// The 3 S rand() values of a frame whose first call has index `offset`, generated on `st` into
+// the context's buffer rnd_buf (the jump table into jt_buf; both sized by S).  The upload reads
+// the process's jump table from host memory: the caller synchronises `st` before it returns.
+int rast_rand_stream(cg_ctx *c, int rnd_buf, int jt_buf, uint64_t offset, long long S, hipStream_t st, int32_t **out)
+{
+    hipError_t e;
+    const long long nvals = 3 * S;
+    const int nb = (int)((nvals + kRandChunk - 1) / kRandChunk);
+    int32_t *rnd = (int32_t *)ctx_buf(c, rnd_buf, (size_t)(nvals > 0 ? nvals : 1) * sizeof(int32_t), &e);
+    if (!rnd) return ctx_fail(c, e, "alloc rand stream");
+    if (nb > 0) {
+        const std::vector<uint32_t> &jtab = rand_jump_table(nb);
+        uint32_t *jt = (uint32_t *)ctx_buf(c, jt_buf, (size_t)nb * kRandDeg * sizeof(uint32_t), &e);
+        if (!jt) return ctx_fail(c, e, "alloc jump table");
+        if ((e = hipMemcpyAsync(jt, jtab.data(), (size_t)nb * kRandDeg * sizeof(uint32_t), hipMemcpyHostToDevice, st)) !=
+            hipSuccess)
+            return ctx_fail(c, e, "upload jump table");
+        RandWindow W;
+        rand_window(offset, W.w);
+        hipLaunchKernelGGL(rast_rand_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, W, jt, nb, nvals, rnd);
+        if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "rand generator launch");
+    }
+    *out = rnd;
+    return CG_OK;
+}
+
 // Host side of colour modes 1-2, between rast_rows_kernel and the post-pass.
 // Synchronises once (the stream's length S decides the generator's size).
 int rast_colour_fill(cg_ctx *c, const RastArgs &A, const cg_rast_params *p, const RowRec *recs, const int *count,
@@ -445,21 +454,8 @@ int rast_colour_fill(cg_ctx *c, const RastArgs &A, const cg_rast_params *p, cons
         (e = hipStreamSynchronize(st)) != hipSuccess)
         return ctx_fail(c, e, "shaded-fragment count");
     *n_shaded = S;
-    const long long nvals = 3 * S;
-    const int nb = (int)((nvals + kRandChunk - 1) / kRandChunk);
-    int32_t *rnd = (int32_t *)ctx_buf(c, 12, (size_t)(nvals > 0 ? nvals : 1) * sizeof(int32_t), &e);
-    if (!rnd) return ctx_fail(c, e, "alloc rand stream");
-    if (nb > 0) {
-        const std::vector<uint32_t> &jtab = rand_jump_table(nb);
-        uint32_t *jt = (uint32_t *)ctx_buf(c, 13, (size_t)nb * kRandDeg * sizeof(uint32_t), &e);
-        if (!jt) return ctx_fail(c, e, "alloc jump table");
-        if ((e = hipMemcpyAsync(jt, jtab.data(), (size_t)nb * kRandDeg * sizeof(uint32_t), hipMemcpyHostToDevice, st)) !=
-            hipSuccess)
-            return ctx_fail(c, e, "upload jump table");
-        RandWindow W;
-        rand_window(p->rand_offset, W.w);
-        hipLaunchKernelGGL(rast_rand_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, W, jt, nb, nvals, rnd);
-    }
+    int32_t *rnd = nullptr;
+    if (const int rc = rast_rand_stream(c, 12, 13, p->rand_offset, S, st, &rnd)) return rc;
     hipLaunchKernelGGL(rast_fill_rand_kernel, dim3(H), dim3(64), (size_t)(max_recs > 0 ? max_recs : 1) * 8, st, A,
                        recs, count, pc, tbase, rnd, p->colour_mode, state, d_depth, shadow,
                        (const cg_rast_seq_frame *)nullptr);
@@ -540,6 +536,19 @@ int rast_seq_chain_mode0(cg_ctx *c, hipStream_t st, const RastSeq &q)
     if (q.wait_ev && (e = hipStreamWaitEvent(st, q.wait_ev, 0)) != hipSuccess) return ctx_fail(c, e, "chain wait");
     hipLaunchKernelGGL(rast_seq_chain_kernel, dim3(1), dim3(64), 0, st, (const long long *)nullptr, q.info, q.first,
                        (unsigned long long)q.start, q.cap, 0);
+    if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "sequence chain launch");
+    if (q.done_ev && (e = hipEventRecord(q.done_ev, st)) != hipSuccess) return ctx_fail(c, e, "chain event");
+    return CG_OK;
+}
+
+// A colour mode 1-2 frame of a sequence on the compact route: its record from the frame's own
+// fragment count *total (device).  The route sizes the stream by that count, so no capacity flags it.
+int rast_seq_chain_exact(cg_ctx *c, hipStream_t st, const RastSeq &q, const long long *total)
+{
+    hipError_t e;
+    if (q.wait_ev && (e = hipStreamWaitEvent(st, q.wait_ev, 0)) != hipSuccess) return ctx_fail(c, e, "chain wait");
+    hipLaunchKernelGGL(rast_seq_chain_kernel, dim3(1), dim3(64), 0, st, total, q.info, q.first,
+                       (unsigned long long)q.start, LLONG_MAX, 1);
     if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "sequence chain launch");
     if (q.done_ev && (e = hipEventRecord(q.done_ev, st)) != hipSuccess) return ctx_fail(c, e, "chain event");
     return CG_OK;

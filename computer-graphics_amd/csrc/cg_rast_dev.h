@@ -82,6 +82,8 @@ struct RastLast {
     hipStream_t st = nullptr;
 };
 RastLast *ctx_rast_last(cg_ctx *c);
+// cg_rast_set_route(ctx, 1) holds: the A/B hook's compact frames are colour mode 0 only
+bool ctx_rast_forced_compact(cg_ctx *c);
 int rast_big_render(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *p, cg_vec4 light, uint32_t *d_argb,
                     float *d_depth, int32_t *d_shadow, hipStream_t st, cg_stats *stats, int tex_mask);
 int rast_big_draw(cg_ctx *c, const cg_rtri *d_room, int n_room, const cg_rtri *d_boxes, int n_boxes,
@@ -214,6 +216,23 @@ __device__ __forceinline__ vec3 rast_tex_normal(const RastArgs &A, int tex, int 
     return v3(vx * inv, vy * inv, vz * inv);
 }
 
+// LO + rand() / (RAND_MAX/HI - LO), all float (skeleton.cpp:563-565, :649-651)
+__device__ __forceinline__ float rand_unit(int32_t v)
+{
+    const float LO = 0.2f, HI = 0.5f;
+    const float den = (float)2147483647 / HI - LO;        // RAND_MAX / HI - LO
+    return LO + (float)v / den;
+}
+
+__device__ __forceinline__ RastArgs with_device_light(RastArgs A)
+{
+    if (A.d_light) {                                      // light from the device geometry (:223)
+        const cg_vec4 L = *A.d_light;
+        A.light[0] = L.x; A.light[1] = L.y; A.light[2] = L.z;
+    }
+    return A;
+}
+
 // Shade state bit: the pixel's screen colour is stored directly in .yzw
 // (colour modes 1-2; low/high buffers stay cleared), instead of a triangle
 // index whose colour the post-pass multiplies by (D + k).
@@ -326,6 +345,15 @@ constexpr uint32_t kStShadow = 0x80000000u;
 // registers; records walked in triangle order (the reference's ordered
 // z-buffer), one uniform overlap test per record.
 constexpr int kFillPx = 64;   // pixels per wave; 128 / 256 measured 3 % / 10 % slower (C3, round 1)
+
+// cg_rast_span_segments: the fill segments that the visible extent [max(lx, 0), min(rx, W)) of a
+// span overlaps -- their number (0: no fragment on screen) and the first one.
+__host__ __device__ inline int rast_span_segments(int lx, int rx, int W, int *first)
+{
+    const int a = lx > 0 ? lx : 0, b = rx < W ? rx : W;
+    *first = a / kFillPx;
+    return b > a ? (b - 1) / kFillPx - a / kFillPx + 1 : 0;
+}
 
 // shade buffers of one pixel as they stand after the fill (:580-585), from its
 // state and its triangle's colour

@@ -283,8 +283,9 @@ struct cg_ctx {
     // RAST scratch (owned by cg_rast.hip)
     DevBuf rtris, rhdr, rspan, rpix, rargb, rdepth, rshadow, rcount, rrecs, rgeo, rroom, rboxes;
     DevBuf rpc, rtl, rrnd, rjt;          // colour modes 1-2 (cg_rast_colour.hip)
-    DevBuf rbig[8];                      // the compact route's own buffers (cg_rast_big.hip)
+    DevBuf rbig[15];                     // the compact route's own buffers (cg_rast_big.hip)
     int rast_route = -1;                 // cg_rast_set_route: -1 automatic, else the forced route
+    long long route_limit = 0;           // cg_rast_set_route_limit: 0 = cg_rast_route's 131072
     RastLast rlast;                      // the latest rasteriser frame (cg_rast_scratch_info)
     // cg_rast_draw_sequence_device: the generator's tables (windows, seed words, J_b for
     // rseq_chunks chunks) and the stream's capacity in fragments (0: 4 * W * H)
@@ -353,8 +354,13 @@ void *ctx_buf(cg_ctx *c, int which, size_t bytes, hipError_t *e)
     case 16: b = &c->rtexel; break;
     case 17: b = &c->iscratch; break;
     case 18: b = &c->rseq; break;
-    case 20: case 21: case 22: case 23: case 24: case 25: case 26: case 27: b = &c->rbig[which - 20]; break;
-    default: *e = hipErrorInvalidValue; return nullptr;
+    default:
+        if (which >= 20 && which < 20 + (int)(sizeof(c->rbig) / sizeof(c->rbig[0]))) {
+            b = &c->rbig[which - 20];
+            break;
+        }
+        *e = hipErrorInvalidValue;
+        return nullptr;
     }
     *e = b->ensure(bytes);
     return *e == hipSuccess ? b->p : nullptr;
@@ -390,7 +396,13 @@ void rast_release(cg_ctx *c)
     c->twoven_op.release(); c->twoven_nrm.release(); c->tgrill.release(); c->tgrill_op.release();
     c->tgrill_nrm.release(); c->rtexel.release();
 }
-int ctx_rast_route(cg_ctx *c, long long cap) { return c->rast_route >= 0 ? c->rast_route : cg_rast_route(cap); }
+int ctx_rast_route(cg_ctx *c, long long cap)
+{
+    if (c->rast_route >= 0) return c->rast_route;
+    if (c->route_limit > 0) return cap <= c->route_limit ? CG_RAST_ROUTE_DENSE : CG_RAST_ROUTE_COMPACT;
+    return cg_rast_route(cap);
+}
+bool ctx_rast_forced_compact(cg_ctx *c) { return c->rast_route == CG_RAST_ROUTE_COMPACT; }
 RastLast *ctx_rast_last(cg_ctx *c) { return &c->rlast; }
 // the device texture maps and which textures are renderable (bit k: texture k)
 int rast_tex_maps(cg_ctx *c, RastTexMaps *m)
@@ -2207,6 +2219,22 @@ extern "C" int cg_rast_set_route(cg_ctx *c, int route)
     return CG_OK;
 }
 
+extern "C" int cg_rast_set_route_limit(cg_ctx *c, long long list_capacity)
+{
+    if (!c) return CG_E_INVALID;
+    if (list_capacity < 0) return ctx_invalid(c, "cg_rast_set_route_limit: a list capacity, or 0 for the default");
+    c->route_limit = list_capacity;
+    return CG_OK;
+}
+
+extern "C" int cg_rast_span_segments(int lx, int rx, int width, int *first)
+{
+    int f = 0;
+    const int k = rast_span_segments(lx, rx, width, &f);
+    if (first) *first = f;
+    return k;
+}
+
 extern "C" int cg_rast_row_blocks(int *batch, int *chunk)
 {
     if (!batch || !chunk) return CG_E_INVALID;
@@ -2329,6 +2357,7 @@ static int rast_lanes_ready(cg_ctx *c, int L)
         }
         cg_ctx *l = c->lanes[k];
         l->rast_route = c->rast_route;          // the lanes follow their parent
+        l->route_limit = c->route_limit;
         if (c->lane_gen[k] != c->scene_gen) {   // the parent's scene, device to device
             CG_TRY(c, l->rroom.ensure(c->rroom.bytes), "alloc lane room");
             CG_TRY(c, l->rboxes.ensure(c->rboxes.bytes), "alloc lane boxes");
@@ -2420,7 +2449,8 @@ static int rast_sequence_device(cg_ctx *c, const cg_rast_params *ps, int n_frame
         const int rc = rast_lanes_ready(c, L);
         if (rc) return rc;
     }
-    if (colour) {
+    // (the compact route sizes each frame's stream by the frame's own count: no tables, no capacity)
+    if (colour && !compact) {
         const int rc = rast_seq_tables(c, nb, &c->rseq_chunks, &q.tables);
         if (rc) return rc;
     }
@@ -2432,7 +2462,7 @@ static int rast_sequence_device(cg_ctx *c, const cg_rast_params *ps, int n_frame
             if (!c->seq_ev[k]) CG_TRY(c, hipEventCreateWithFlags(&c->seq_ev[k], hipEventDisableTiming), "event");
             if (!(win[k] = (uint32_t *)ctx_buf(l, 18, 64 * sizeof(uint32_t), &e))) return ctx_fail(c, e, "alloc window");
         }
-        if (!colour) continue;
+        if (!colour || compact) continue;
         // everything a colour frame sizes differently from a mode 0 frame, before the first
         // launch: the frames then find every buffer in place (a buffer that grows waits)
         if (!ctx_buf(l, 3, px * sizeof(float4), &e)) return ctx_fail(c, e, "alloc state");

@@ -465,7 +465,10 @@ int cg_rast_render_device(cg_ctx *ctx, const cg_rtri *d_tris, int n, const cg_ra
  * the record total and the longest row -- and allocates exactly what the frame
  * needs, grow-only: no pool can overflow and there is no fallback path.  (So a
  * compact-route frame cannot be captured into a graph.)  cg_rast_render_device
- * on the compact route waits likewise for the last two. */
+ * on the compact route waits likewise for the last two.  A colour mode 1-2
+ * frame on the compact route waits twice more, for its segment total and for
+ * its shaded-fragment count S (the rand() stream is sized by it), and returns
+ * after the frame ran, as the dense route's colour modes do. */
 int cg_rast_set_scene(cg_ctx *ctx, const cg_rtri *room, int n_room, const cg_rtri *boxes, int n_boxes);
 int cg_rast_draw(cg_ctx *ctx, const cg_rast_params *p, uint32_t *argb, float *depth, int32_t *shadow,
                  cg_stats *stats);
@@ -481,18 +484,32 @@ int cg_rast_draw_device(cg_ctx *ctx, const cg_rast_params *p, uint32_t *d_argb, 
  * else COMPACT; list_capacity is 32 * (n_room + 7 * n_boxes) for the
  * cg_rast_draw* entries and n for cg_rast_render*.
  * The compact route serves cg_rast_draw, cg_rast_draw_device, cg_rast_render
- * and cg_rast_render_device in colour mode 0 with texture modes 0-3 and the
- * indirect_first rule; cg_rast_draw_frames_device and
- * cg_rast_draw_sequence_device run its frames one after another on `stream`
- * (no lanes: each would hold its own copy of the scratch).  Colour modes 1-2
- * on the compact route return CG_E_INVALID with a message: their count, scan,
- * generator and chain kernels are built for the dense layout only. */
+ * and cg_rast_render_device in colour modes 0-2 with texture modes 0-3 (modes
+ * 1-2 ignore textures, as the reference does) and the indirect_first rule;
+ * cg_rast_draw_frames_device and cg_rast_draw_sequence_device run its frames
+ * one after another on `stream` (no lanes: each would hold its own copy of
+ * the scratch).  Its colour modes 1-2 number the shaded fragments from the
+ * span order itself (triangle, row, 64-pixel segment) and generate exactly
+ * 3 S rand() values; the 16-byte state, the segment counts and the stream are
+ * held only once a mode 1-2 frame ran, grow-only, and count in
+ * cg_rast_scratch_info's out[0]. */
 enum { CG_RAST_ROUTE_DENSE = 0, CG_RAST_ROUTE_COMPACT = 1 };
 int cg_rast_route(long long list_capacity);
-/* Test and A/B hook: -1 automatic (the default), 0 forces DENSE, 1 forces
- * COMPACT for this context's frames (its lanes follow).  A forced dense
- * cg_rast_draw* of more than 4096 input triangles fails with CG_E_INVALID. */
+/* Test and A/B hook for colour mode 0: -1 automatic (the default), 0 forces
+ * DENSE, 1 forces COMPACT for this context's frames (its lanes follow).  A
+ * forced dense cg_rast_draw* of more than 4096 input triangles fails with
+ * CG_E_INVALID; so does a colour mode 1-2 frame forced onto the compact route
+ * (with a message): modes 1-2 take that route on the automatic choice only. */
 int cg_rast_set_route(cg_ctx *ctx, int route);
+/* Test and A/B hook: the list capacity above which this context's frames take the compact
+ * route on the automatic choice; 0 = the default (131072, what cg_rast_route applies).
+ * Negative: CG_E_INVALID. */
+int cg_rast_set_route_limit(cg_ctx *ctx, long long list_capacity);
+/* Host-only: the 64-pixel fill segments that the visible extent [max(lx, 0), min(rx, width))
+ * of a span with fragments x in [lx, rx) overlaps -- the entries the compact route's colour
+ * modes 1-2 keep for it.  Returns their number (0: nothing on screen) and writes the first
+ * segment to *first (may be NULL). */
+int cg_rast_span_segments(int lx, int rx, int width, int *first);
 /* Rasteriser scratch after the latest rasteriser frame (waits for it, on the
  * stream it ran on): out[0] device bytes held for rasteriser scratch (lanes
  * included), out[1] the route the frame took, out[2] its clipped triangles,
@@ -537,7 +554,11 @@ typedef struct { uint64_t rand_offset; int64_t n_shaded; int32_t status; int32_t
  * A mode 1-2 frame that shades more fragments than the rand() stream's capacity
  * gets status CG_E_CAPACITY and its planes are left as they were; its record
  * and every later frame stay exact (render it alone with cg_rast_draw at
- * d_info[f].rand_offset).  One sequence per context at a time. */
+ * d_info[f].rand_offset).  One sequence per context at a time.
+ * On the compact route the frames run in turn on `stream` and the call waits for
+ * each frame's counts; a mode 1-2 frame sizes its stream from its own shaded
+ * fragments, so it never reports CG_E_CAPACITY and cg_rast_set_rand_capacity
+ * is ignored there.  The records are the same. */
 int cg_rast_draw_sequence_device(cg_ctx *ctx, const cg_rast_params *ps, int n_frames, uint32_t *d_argb,
                                  float *d_depth, int32_t *d_shadow, size_t frame_stride,
                                  cg_rast_seq_frame *d_info, void *stream);
@@ -554,8 +575,8 @@ int cg_rast_draw_sequence_device(cg_ctx *ctx, const cg_rast_params *ps, int n_fr
  * the index is never read back between chunks.  A frame flagged CG_E_CAPACITY is then rendered
  * alone with cg_rast_draw at its recorded index, straight into its host slot, and reports status
  * 0; a status that is non-zero on return means that frame is not in host memory, and the call
- * returns that code.  Both routes as the device form (compact-route frames in turn; modes 1-2
- * refused there).  stats (optional): kernel_ms the device time spanning the renders, total_ms the
+ * returns that code.  Both routes as the device form (compact-route frames in turn, all three
+ * colour modes).  stats (optional): kernel_ms the device time spanning the renders, total_ms the
  * call, n_tris the last frame's clipped count, n_shaded the sum over the mode 1-2 frames (-1: none).
  * Returns when every frame, and info, is in host memory; the only host waits are those of the
  * downloads and the closing synchronise.  Slots and records grow only: after the first call of a

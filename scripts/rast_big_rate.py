@@ -1,5 +1,6 @@
 """Frame rate, phase times and scratch of the rasteriser's compact route (cg_rast_big.hip).
-cg_rast_draw_device at 1920 x 1080, focal 768, colour mode 0:
+cg_rast_draw_device at 1920 x 1080, focal 768, colour mode 0 (and, with --colour-modes, the random
+scenes in modes 1-2 beside it on the same build: legs random_<n>_mode<m>, their time over mode 0's):
   reference scene   the dense route against the forced compact route: what the indirection
                     and the compact route's three host waits cost on a small frame;
   random scenes     cg_rast_random_scene(0x5EED, n, 0.02) as the room, n = 1e4, 1e5, 1e6, on the
@@ -7,12 +8,13 @@ cg_rast_draw_device at 1920 x 1080, focal 768, colour mode 0:
 Every leg is warmed up, then timed over windows of about --window seconds; the legs alternate
 and each window is closed by a device synchronise; medians over --repeats windows.  Per leg:
 frames/s, the phases' milliseconds from HIP events (cg_kernel_timing: rast_big_clip / _setup /
-_rows / _fill / _post, each a scope over its launches), cg_rast_scratch_info, and the row-list
+_rows / _fill / _post, in modes 1-2 also _count / _rand / _shade; each a scope over its launches),
+cg_rast_scratch_info, and the row-list
 pass's work (spans tested and records written) beside the dense formulas H x 32 n_in header
 tests and 2560 n_in H bytes.  The 1e6 scene is also rendered once at 96 x 54 on both routes
 and compared whole.  Usage:
   python scripts/rast_big_rate.py [--repeats 3] [--window 0.5] [--sizes 10000,100000,1000000]
-                                  [--out profiles/rast_big_rate.json]"""
+                                  [--colour-modes 0,1] [--out profiles/rast_big_rate.json]"""
 import argparse
 import json
 import os
@@ -31,11 +33,13 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--repeats", type=int, default=3)
 ap.add_argument("--window", type=float, default=0.5, help="seconds per timed window")
 ap.add_argument("--sizes", default="10000,100000,1000000")
+ap.add_argument("--colour-modes", default="0", help="colour modes of the random scenes' legs, e.g. 0,1")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rast_big_rate.json"))
 args = ap.parse_args()
 
 W, H, F = 1920, 1080, 768.0
 PHASES = ("rast_big_clip", "rast_big_setup", "rast_big_rows", "rast_big_fill", "rast_big_post")
+COLOUR_PHASES = ("rast_big_count", "rast_big_rand", "rast_big_shade")
 DENSE_KERNELS = ("rast_fill_kernel", "rast_post_kernel")
 dev = torch.device("cuda", 0)
 torch.cuda.set_device(dev)
@@ -43,8 +47,9 @@ p = cgamd.rast_params(W, H, F)
 d_argb = torch.zeros(W * H, dtype=torch.int32, device=dev)
 no_boxes = (cgamd.RTri * 1)()
 sizes = [int(s) for s in args.sizes.split(",") if s]
+modes = [int(m) for m in args.colour_modes.split(",") if m]
 batch, chunk = cgamd.rast_row_blocks()
-result = {"workload": f"cg_rast_draw_device, {W}x{H}, focal {F}, colour mode 0", "repeats": args.repeats,
+result = {"workload": f"cg_rast_draw_device, {W}x{H}, focal {F}, colour mode 0 (random scenes: modes {modes})", "repeats": args.repeats,
           "window_s": args.window, "row_blocks": {"batch": batch, "chunk": chunk}, "legs": {}}
 
 
@@ -73,17 +78,23 @@ for n in sizes:
     n_in[f"random_{n}"] = n
 
 
-def make_leg(ctx, route):
+def make_leg(ctx, route, mode=0):
+    pm = cgamd.rast_params(W, H, F, colour_mode=mode)
+
     def fn():
         ctx.rast_set_route(route)
-        ctx.rast_draw_device(p, d_argb.data_ptr())
+        ctx.rast_draw_device(pm, d_argb.data_ptr())
     return fn
 
 
 legs = {"reference_dense": (ctxs["reference"], make_leg(ctxs["reference"], cgamd.RAST_ROUTE_DENSE), "reference"),
         "reference_compact": (ctxs["reference"], make_leg(ctxs["reference"], cgamd.RAST_ROUTE_COMPACT), "reference")}
+leg_mode = {}
 for n in sizes:
-    legs[f"random_{n}"] = (ctxs[f"random_{n}"], make_leg(ctxs[f"random_{n}"], -1), f"random_{n}")
+    for m in modes:   # a scene's modes are neighbours in the round: they alternate
+        k = f"random_{n}" if m == 0 else f"random_{n}_mode{m}"
+        legs[k] = (ctxs[f"random_{n}"], make_leg(ctxs[f"random_{n}"], -1, m), f"random_{n}")
+        leg_mode[k] = m
 
 try:
     # the reference frame is the same on both routes before anything is timed
@@ -110,7 +121,7 @@ try:
         for _ in range(frames):
             fn()
         torch.cuda.synchronize(dev)
-        names = DENSE_KERNELS if k == "reference_dense" else PHASES
+        names = DENSE_KERNELS if k == "reference_dense" else PHASES + (COLOUR_PHASES if leg_mode.get(k, 0) else ())
         phase_ms = {nm: cgamd.kernel_time(nm)[0] / frames for nm in names}
         cgamd.kernel_timing(False)
         info = ctx.rast_scratch_info()
@@ -123,6 +134,7 @@ try:
             "phase_ms": phase_ms,
             "scratch": info,
             "n_in": ni,
+            "colour_mode": leg_mode.get(k, 0),
             "dense_formula_bytes": 2560 * ni * H,
             "row_list_work": {"dense_header_tests": H * 32 * ni, "spans_tested": info["spans"],
                               "records_written": info["recs"], "chunks": -(-info["spans"] // chunk)},
@@ -130,6 +142,16 @@ try:
     ref = result["legs"]
     result["compact_over_dense_reference"] = (ref["reference_compact"]["frames_per_s"]["median"]
                                                / ref["reference_dense"]["frames_per_s"]["median"])
+
+    # modes 1-2 beside mode 0 on the same scene: frame time over mode 0's, and the fragments that drew
+    for k, m in leg_mode.items():
+        base = k.split("_mode")[0]
+        if m == 0 or base not in ref:
+            continue
+        ctx = legs[k][0]
+        ctx.rast_set_route(-1)
+        ref[k]["n_shaded"] = ctx.rast_draw(cgamd.rast_params(W, H, F, colour_mode=m))[3].n_shaded
+        ref[k]["ms_over_mode_0"] = ref[k]["ms_per_frame"] / ref[base]["ms_per_frame"]
 
     # the largest scene once more at 96 x 54, both routes, compared whole
     if sizes:
