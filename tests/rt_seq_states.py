@@ -1,7 +1,12 @@
 """Key scripts of the raytracer's Update() (raytracer/Source/skeleton.cpp:192-256) as per-frame
 states, shared by test_rt_sequence.py and test_rt_sequence_gpu.py.  Every state is built in
 float32, step by step as the keys arrive: the light and the camera move by float32(0.1), the yaw
-by float32(0.174533) (so that it returns to exactly 0), the focal length by 10."""
+by float32(0.174533) (so that it returns to exactly 0), the focal length by 10.
+
+This generator is simplified on purpose: its tests compare the GPU with the oracle at whatever
+state it makes.  The reference itself steps the yaw in double and narrows to float, so 'm' then 'n'
+leaves yaw = -5.372047e-09 there; the states the real program reaches, that one included, are in
+tests/golden/ref_sessions.json and rendered by tests/test_ref_sessions_gpu.py."""
 import numpy as np
 
 import cgamd
