@@ -1035,6 +1035,19 @@ class Context:
                                                   out.size), "cg_image_decode_jpeg")
         return out if ch == 3 else out[:, :, 0]
 
+    def decode_jpeg_device(self, data: bytes, d_out, cap, stream=None):
+        """cg_image_decode_jpeg_device: the same bytes as decode_jpeg, written to the device
+        address d_out (room for `cap` bytes), asynchronously on `stream` (a HIP stream handle;
+        None: the context's).  Returns the status (CG_OK, or CG_E_CAPACITY when cap is less
+        than width * height * channels, in which case nothing is written); raises on any
+        other failure."""
+        buf = np.frombuffer(data, np.uint8)
+        rc = self.lib.cg_image_decode_jpeg_device(self.h, buf.ctypes.data_as(P), buf.size, P(d_out), cap,
+                                                  P(stream) if stream else None)
+        if rc != CG_E_CAPACITY:
+            self._check(rc, "cg_image_decode_jpeg_device")
+        return rc
+
     def load_textures_jpeg(self, directory: str) -> dict:
         """Decode the reference's texture files found in `directory` (names as
         skeleton.cpp:135-146) -> {map name: BGR array}, ready for rast_set_textures."""

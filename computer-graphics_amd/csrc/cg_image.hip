@@ -18,7 +18,8 @@
 //   jpeg_colour_kernel   YCbCr -> BGR (libjpeg 9's fixed-point tables, computed
 //                        inline), one thread per pixel
 // Output is BGR bytes (gray for 1-component files), row-major, as imread
-// returns them.  Unsupported inputs (arithmetic coding, 12-bit, lossless,
+// returns them.  A 3-component file is YCbCr or RGB by libjpeg's rule
+// (JpegFrame::rgb).  Unsupported inputs (arithmetic coding, 12-bit, lossless,
 // sampling factors that libjpeg 9 would still upsample) return CG_E_INVALID.
 #include <cstdio>
 #include <cstring>
@@ -173,13 +174,25 @@ struct Component {
 
 struct JpegFrame {
     int width = 0, height = 0, ncomp = 0;
-    bool progressive = false, adobe_rgb = false;
+    bool progressive = false;
+    // what decides the colour space of a 3-component file (libjpeg jdapimin.c
+    // default_decompress_parms), from the markers ahead of the first scan
+    bool saw_jfif = false, saw_adobe = false, saw_scan = false;
+    int adobe_transform = 0;
     int hmax = 1, vmax = 1, mcus_x = 0, mcus_y = 0, restart = 0;
     uint16_t quant[4][64] = {};   // natural order
     bool quant_present[4] = {};
     HuffTable dc[4], ac[4];
     Component comp[3];
     int eobrun = 0;
+    // JFIF means YCbCr; else an Adobe marker decides by its transform (0: RGB,
+    // anything else YCbCr); else the component ids 'R','G','B' mean RGB
+    bool rgb() const
+    {
+        if (ncomp != 3 || saw_jfif) return false;
+        if (saw_adobe) return adobe_transform == 0;
+        return comp[0].id == 'R' && comp[1].id == 'G' && comp[2].id == 'B';
+    }
 };
 
 inline int be16(const uint8_t *p) { return (p[0] << 8) | p[1]; }
@@ -452,8 +465,10 @@ const char *JpegDecoder::parse(const uint8_t *data, size_t n, bool header_only)
         } else if (m == 0xDD) {
             if (len < 4) return "truncated JPEG restart interval";
             f_.restart = be16(p + 2);
+        } else if (m == 0xE0 && len >= 16 && !memcmp(p + 2, "JFIF", 5)) {
+            if (!f_.saw_scan) f_.saw_jfif = true;
         } else if (m == 0xEE && len >= 14 && !memcmp(p + 2, "Adobe", 5)) {
-            f_.adobe_rgb = p[13] == 0;
+            if (!f_.saw_scan) f_.saw_adobe = true, f_.adobe_transform = p[13];
         } else if (m == 0xC0 || m == 0xC1 || m == 0xC2) {
             if (const char *e = frame(p, len, m)) return e;
             if (header_only) return nullptr;
@@ -461,6 +476,7 @@ const char *JpegDecoder::parse(const uint8_t *data, size_t n, bool header_only)
             return "lossless / arithmetic / hierarchical JPEG is not supported";
         } else if (m == 0xDA) {
             if (!have_frame_) return "JPEG scan before frame header";
+            f_.saw_scan = true;
             if (const char *e = scan(p, end)) return e;
             continue;
         }
@@ -708,7 +724,7 @@ int decode_into(cg_ctx *c, const uint8_t *data, size_t n, uint8_t *d_out, size_t
     uint8_t *dst = to_host ? planes + plane_bytes * f.ncomp : d_out;
     const long npx = (long)f.width * f.height;
     hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, st, planes, pitch,
-                       plane_bytes, f.width, f.height, f.ncomp, f.adobe_rgb ? 1 : 0, dst);
+                       plane_bytes, f.width, f.height, f.ncomp, f.rgb() ? 1 : 0, dst);
     if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "jpeg kernels");
     if (to_host) {
         if ((e = hipMemcpyAsync(h_out, dst, out_bytes, hipMemcpyDeviceToHost, st)) != hipSuccess ||

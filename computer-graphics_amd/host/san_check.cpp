@@ -5,7 +5,11 @@
 // rasteriser/Source/skeleton.cpp:205-241, 720-1673), the RT column window,
 // the opacity maps, glibc rand(), the starfield, and the JPEG parser and
 // entropy decoder on the reference's textures and on damaged copies.
-//   san_check TEXTURE_DIR
+//   san_check TEXTURE_DIR [JPEG_DIR]
+// JPEG_DIR: every .jpg in it (tests/golden/jpeg_san: baseline, restart
+// intervals, one scan per component, gray) is walked like the textures.
+#include <dirent.h>
+
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -104,13 +108,27 @@ int main(int argc, char **argv)
 {
     const std::string dir = argc > 1 ? argv[1] : "tests/golden/textures";
     // JPEG: the reference's maps, truncated and corrupted copies
-    const char *files[] = {"Metal_Grill_002_basecolor.jpg", "Metal_Grill_002_opacity.jpg", "Metal_Grill_002_normal.jpg",
+    std::vector<std::string> files;
+    for (const char *fn : {"Metal_Grill_002_basecolor.jpg", "Metal_Grill_002_opacity.jpg", "Metal_Grill_002_normal.jpg",
                            "woven1024x1024.jpg", "Wood_wicker_003_ambientOcclusion.jpg", "Wood_wicker_003_opacity.jpg",
-                           "Wood_wicker_003_normal.jpg"};
+                           "Wood_wicker_003_normal.jpg"})
+        files.push_back(dir + "/" + fn);
+    if (argc > 2) {
+        const size_t before = files.size();
+        DIR *dp = opendir(argv[2]);
+        if (!dp) fail("opening the JPEG directory", -1);
+        while (const dirent *de = readdir(dp)) {
+            const std::string name = de->d_name;
+            if (name.size() > 4 && name.compare(name.size() - 4, 4, ".jpg") == 0)
+                files.push_back(std::string(argv[2]) + "/" + name);
+        }
+        closedir(dp);
+        if (files.size() == before) fail("no .jpg in the JPEG directory", -1);
+    }
     int checked = 0;
-    for (const char *fn : files) {
-        std::vector<uint8_t> j = slurp(dir + "/" + fn);
-        if (j.empty()) fail(fn, -1);
+    for (const std::string &fn : files) {
+        std::vector<uint8_t> j = slurp(fn);
+        if (j.empty()) fail(fn.c_str(), -1);
         int w, h, c;
         if (int rc = cg_image_jpeg_info(j.data(), j.size(), &w, &h, &c)) fail("cg_image_jpeg_info", rc);
         if (int rc = cg_image_jpeg_check(j.data(), j.size())) fail("cg_image_jpeg_check", rc);

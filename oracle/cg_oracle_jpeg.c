@@ -75,7 +75,7 @@ typedef struct {
 } bits;
 
 typedef struct {
-    int w, h, nc, progressive, hmax, vmax, mcux, mcuy, restart, adobe, adobe_transform;
+    int w, h, nc, progressive, hmax, vmax, mcux, mcuy, restart, jfif, adobe, adobe_transform, scans;
     uint16_t q[4][64];     /* natural order */
     huff dc[4], ac[4];
     comp c[4];
@@ -557,9 +557,10 @@ int cgo_jpeg_decode(const uint8_t *data, size_t n, uint8_t *out, size_t cap)
             }
         } else if (m == 0xDD) {                             /* DRI */
             d->restart = u16(p + 2);
-        } else if (m == 0xEE && len >= 12 && !memcmp(p + 2, "Adobe", 5)) {
-            d->adobe = 1;
-            d->adobe_transform = p[13];
+        } else if (m == 0xE0 && len >= 16 && !memcmp(p + 2, "JFIF", 5)) {
+            if (!d->scans) d->jfif = 1;                     /* APP0, 14 data bytes at least */
+        } else if (m == 0xEE && len >= 14 && !memcmp(p + 2, "Adobe", 5)) {
+            if (!d->scans) { d->adobe = 1; d->adobe_transform = p[13]; }   /* APP14, 12 data bytes */
         } else if (m == 0xC0 || m == 0xC1 || m == 0xC2) {  /* SOF0/1/2, Huffman */
             if (p[2] != 8) { err = -4; break; }
             d->progressive = (m == 0xC2);
@@ -596,6 +597,7 @@ int cgo_jpeg_decode(const uint8_t *data, size_t n, uint8_t *out, size_t cap)
             break;
         } else if (m == 0xDA) {                             /* SOS */
             if (!have_frame) { err = -3; break; }
+            d->scans = 1;
             p = scan(d, p, end, &err);
             continue;
         }
@@ -624,7 +626,11 @@ int cgo_jpeg_decode(const uint8_t *data, size_t n, uint8_t *out, size_t cap)
                 }
         }
         if (!err) {
-            int rgb = d->adobe && d->adobe_transform == 0;
+            /* jdapimin.c default_decompress_parms, from the markers ahead of the first scan:
+             * JFIF means YCbCr; else an Adobe marker decides by its transform (0: RGB, anything
+             * else YCbCr); else the component ids 'R','G','B' mean RGB, any others YCbCr */
+            int rgb = d->jfif ? 0 : d->adobe ? d->adobe_transform == 0
+                    : (d->c[0].id == 'R' && d->c[1].id == 'G' && d->c[2].id == 'B');
             for (int y = 0; y < d->h; ++y)
                 for (int x = 0; x < d->w; ++x) {
                     size_t o = (size_t)y * pw + x, dst = ((size_t)y * d->w + x) * d->nc;

@@ -12,8 +12,11 @@
  *  - the JPEG decoder on the reference's textures and on truncated /
  *    corrupted copies;
  *  - the raytracer at small sizes (sphere tangency, FP64 islands), glibc rand().
- * Usage: san_oracle TEXTURE_DIR    (exit 0 = clean; the sanitizers abort otherwise)
+ * Usage: san_oracle TEXTURE_DIR [JPEG_DIR]   (exit 0 = clean; the sanitizers abort otherwise)
+ * JPEG_DIR: every .jpg in it (tests/golden/jpeg_san: baseline, restart intervals, one scan
+ * per component, gray) gets the same decode, truncations and byte flips as the textures.
  */
+#include <dirent.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -68,6 +71,19 @@ static void yaw_R(float yaw, float *R)
 int main(int argc, char **argv)
 {
     const char *dir = argc > 1 ? argv[1] : "tests/golden/textures";
+    int extra = 0;
+    if (argc > 2) {
+        DIR *dp = opendir(argv[2]);
+        if (!dp) { fprintf(stderr, "cannot open %s\n", argv[2]); return 2; }
+        for (struct dirent *de; (de = readdir(dp)) != NULL;) {
+            size_t len = strlen(de->d_name);
+            if (len < 4 || strcmp(de->d_name + len - 4, ".jpg")) continue;
+            free(decode(argv[2], de->d_name));
+            ++extra;
+        }
+        closedir(dp);
+        if (!extra) { fprintf(stderr, "no .jpg in %s\n", argv[2]); return 2; }
+    }
     /* textures: grill + woven decoded, marble synthetic */
     cgo_rast_textures tx;
     memset(&tx, 0, sizeof tx);
@@ -161,7 +177,7 @@ int main(int argc, char **argv)
     uint32_t *sf = malloc(sizeof(uint32_t) * 320 * 256);
     cgo_starfield_init(stars, 100);
     for (int k = 0; k < 50; ++k) { cgo_starfield_update(stars, 100, 16.0f); cgo_starfield_draw(stars, 100, 320, 256, sf); }
-    printf("sanitized oracle: %ld frames clean\n", frames);
+    printf("sanitized oracle: %ld frames, %d extra JPEGs clean\n", frames, extra);
     free(stars); free(sf); free(rt); free(argb); free(depth); free(shadow); free(marble);
     free((void *)tx.grill); free((void *)tx.grill_opacity); free((void *)tx.grill_normal); free((void *)tx.woven);
     free((void *)tx.woven_ao); free((void *)tx.woven_opacity); free((void *)tx.woven_normal);

@@ -12,6 +12,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TEX = os.path.join(ROOT, "tests", "golden", "textures")
+JPEGS = os.path.join(ROOT, "tests", "golden", "jpeg_san")   # baseline / restart / per-component-scan files
 ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1")
 
 
@@ -22,7 +23,7 @@ def _make(path, target):
 
 
 def _run(exe):
-    r = subprocess.run([exe, TEX], capture_output=True, text=True, env=ENV, timeout=600)
+    r = subprocess.run([exe, TEX, JPEGS], capture_output=True, text=True, env=ENV, timeout=600)
     out = r.stdout + r.stderr
     assert r.returncode == 0, out[-4000:]
     assert "runtime error" not in out and "AddressSanitizer" not in out, out[-4000:]
