@@ -151,6 +151,11 @@ _SIGS = {
     "cg_rt_shard_rows": (C.c_int, [C.c_int, C.POINTER(RtShard)]),
     "cg_rt_unstripe_device": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, C.c_int, P, P]),
     "cg_rt_unstripe_batch_device": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P]),
+    "cg_rt_pixel_ray": (C.c_int, [C.POINTER(RtCamera), C.c_int, C.c_int, C.c_int, C.POINTER(Vec4), C.POINTER(Vec4)]),
+    "cg_rt_hits_device": (C.c_int, [P, C.POINTER(RtCamera), C.c_int, C.c_void_p, P, P, P, P]),
+    "cg_rt_hits": (C.c_int, [P, C.POINTER(RtCamera), C.c_int, P, P, P]),
+    "cg_rt_pick": (C.c_int, [P, C.POINTER(RtCamera), C.c_int, C.c_int, C.c_int, C.POINTER(Isect),
+                             C.POINTER(C.c_int)]),
     "cg_rt_probe_closest": (C.c_int, [P, C.POINTER(Vec4), C.POINTER(Vec4), C.c_int,
                                       C.POINTER(Isect), C.POINTER(C.c_int)]),
     "cg_rt_probe_direct_light": (C.c_int, [P, C.POINTER(Isect), C.POINTER(Light), C.c_int,
@@ -300,6 +305,38 @@ def rt_camera(width, height, focal=256.0, cam=(0.0, 0.0, -3.0, 1.0), R=None, ind
     c.R = R if R is not None else identity16()
     c.indirect = indirect
     return c
+
+
+HIT_NONE = -(1 << 31)   # cg_render.h CG_RT_HIT_NONE
+# cg_isect as a numpy record: 28 B, the reference's Intersection
+ISECT_DTYPE = np.dtype([("position", np.float32, 4), ("distance", np.float32), ("triangleIndex", np.int32),
+                        ("sphereIndex", np.int32)])
+assert ISECT_DTYPE.itemsize == C.sizeof(Isect)
+
+
+def rt_pixel_ray(cam, x, y, sub_ray=4):
+    """cg_rt_pixel_ray (host-only; no GPU needed): (start, dir) of pixel (x, y)'s sub-ray as two
+    float32[4] arrays; ValueError for a pixel outside the frame or a sub-ray outside 0..8."""
+    s, d = Vec4(), Vec4()
+    rc = load().cg_rt_pixel_ray(C.byref(cam), x, y, sub_ray, C.byref(s), C.byref(d))
+    if rc != CG_OK:
+        raise ValueError(f"cg_rt_pixel_ray: {rc}")
+    return (np.array([s.x, s.y, s.z, s.w], np.float32), np.array([d.x, d.y, d.z, d.w], np.float32))
+
+
+def rt_pixel_rays(cam, sub_ray=4, pixels=None):
+    """cg_rt_pixel_ray for many pixels: (starts, dirs) as float32[n, 4]; pixels an iterable of flat
+    indices y * W + x (None: the whole frame, row-major)."""
+    lib, W = load(), cam.width
+    idx = range(W * cam.height) if pixels is None else [int(p) for p in pixels]
+    n = len(idx)
+    starts, dirs = np.zeros((max(n, 1), 4), np.float32), np.zeros((max(n, 1), 4), np.float32)
+    ps, pd = C.cast(starts.ctypes.data, C.POINTER(Vec4)), C.cast(dirs.ctypes.data, C.POINTER(Vec4))
+    fn, pc = lib.cg_rt_pixel_ray, C.byref(cam)
+    for k, p in enumerate(idx):
+        if fn(pc, p % W, p // W, sub_ray, C.byref(ps[k]), C.byref(pd[k])) != CG_OK:
+            raise ValueError(f"cg_rt_pixel_ray: pixel {p}, sub-ray {sub_ray}")
+    return starts[:n], dirs[:n]
 
 
 def default_lights():
@@ -910,6 +947,45 @@ class Context:
         self._check(self.lib.cg_rt_unstripe_batch_device(self.h, P(d_gathered), width, height, nranks, stripe_h,
                                                          nframes, P(d_frames), P(stream) if stream else None),
                     "cg_rt_unstripe_batch_device")
+
+    def rt_hits_device(self, cam, sub_ray=4, shard=None, d_isect=None, d_index=None, d_distance=None, stream=None):
+        """cg_rt_hits_device: the shard's hit planes into device memory (addresses; any may be None,
+        not all three): cg_rt_shard_rows() rows of W records / int32 / float32."""
+        sh = C.cast(C.byref(shard), C.c_void_p) if shard is not None else None
+        self._check(self.lib.cg_rt_hits_device(self.h, C.byref(cam), sub_ray, sh, P(d_isect) if d_isect else None,
+                                               P(d_index) if d_index else None,
+                                               P(d_distance) if d_distance else None,
+                                               P(stream) if stream else None), "cg_rt_hits_device")
+
+    def rt_hits(self, cam, sub_ray=4, isect=True, index=True, distance=True):
+        """cg_rt_hits: the whole frame's hit planes in host memory as (isect ISECT_DTYPE[H * W], index
+        int32[H * W], distance float32[H * W]); a plane that was not asked for is None."""
+        n = cam.width * cam.height
+        a = np.zeros(n, ISECT_DTYPE) if isect else None
+        b = np.zeros(n, np.int32) if index else None
+        d = np.zeros(n, np.float32) if distance else None
+        self._check(self.lib.cg_rt_hits(self.h, C.byref(cam), sub_ray, a.ctypes.data_as(P) if isect else None,
+                                        b.ctypes.data_as(P) if index else None,
+                                        d.ctypes.data_as(P) if distance else None), "cg_rt_hits")
+        return a, b, d
+
+    def rt_pick(self, cam, x, y, sub_ray=4):
+        """cg_rt_pick: (record as a 1-element ISECT_DTYPE array, hit) of one pixel's sub-ray."""
+        out, hit = np.zeros(1, ISECT_DTYPE), C.c_int()
+        self._check(self.lib.cg_rt_pick(self.h, C.byref(cam), x, y, sub_ray,
+                                        C.cast(out.ctypes.data, C.POINTER(Isect)), C.byref(hit)), "cg_rt_pick")
+        return out, bool(hit.value)
+
+    def rt_probe_closest_np(self, starts, dirs):
+        """cg_rt_probe_closest on float32[n, 4] arrays: (records ISECT_DTYPE[n], hit int32[n])."""
+        S, D = np.ascontiguousarray(starts, np.float32), np.ascontiguousarray(dirs, np.float32)
+        n = len(S)
+        out, hit = np.zeros(n, ISECT_DTYPE), np.zeros(n, np.int32)
+        self._check(self.lib.cg_rt_probe_closest(self.h, C.cast(S.ctypes.data, C.POINTER(Vec4)),
+                                                 C.cast(D.ctypes.data, C.POINTER(Vec4)), n,
+                                                 C.cast(out.ctypes.data, C.POINTER(Isect)),
+                                                 C.cast(hit.ctypes.data, C.POINTER(C.c_int))), "cg_rt_probe_closest")
+        return out, hit
 
     def rt_probe_closest(self, starts, dirs):
         n = len(starts)

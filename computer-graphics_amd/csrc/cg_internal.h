@@ -172,6 +172,15 @@ struct BigCaps {
     long long sup, bin, sbin, sorted;
 };
 
+// A hits-only pass (cg_rt_hits_device): ClosestIntersection of sub-ray `sub_ray` of every pixel of
+// the shard's rows into up to three planes of rows_out x W (device memory; any may be null).
+struct RtHits {
+    int sub_ray;
+    cg_isect *isect;
+    int32_t *index;      // triangle k, sphere q as -1 - q, CG_RT_HIT_NONE
+    float *distance;
+};
+
 // Frame arguments, passed by value (kernarg -> SGPRs).
 struct RtFrame {
     int W, H;
@@ -255,7 +264,9 @@ enum KtId {
     // the compact rasteriser route's phases (cg_rast_big.hip), each a scope over its launches
     KT_RAST_BIG_CLIP, KT_RAST_BIG_SETUP, KT_RAST_BIG_ROWS, KT_RAST_BIG_FILL, KT_RAST_BIG_POST,
     // its colour modes 1-2: segments + count + scans, the generator, number + shade
-    KT_RAST_BIG_COUNT, KT_RAST_BIG_RAND, KT_RAST_BIG_SHADE, KT_COUNT
+    KT_RAST_BIG_COUNT, KT_RAST_BIG_RAND, KT_RAST_BIG_SHADE,
+    // a hits-only pass of the large-scene path: a scope over it, its walk, its gather
+    KT_RT_HITS_PASS, KT_RT_HITS_WALK, KT_RT_HITS_GATHER, KT_COUNT
 };
 // HIP events on `st` around the scope's launches while timing is on (id
 // outside [0, KT_COUNT): nothing).

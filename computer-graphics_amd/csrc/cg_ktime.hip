@@ -24,6 +24,8 @@ static const char *const kKtNames[KT_COUNT] = {
     "rt_big_frame",             "rast_fill_kernel",      "rast_post_kernel",        "rast_big_clip",
     "rast_big_setup",           "rast_big_rows",         "rast_big_fill",           "rast_big_post",
     "rast_big_count",           "rast_big_rand",         "rast_big_shade",
+    // a hits-only pass (cg_rt_hits_device) on a large scene: the whole pass, its walk, its gather
+    "rt_hits_pass",             "rt_hits_walk",          "rt_hits_gather",
 };
 
 namespace {

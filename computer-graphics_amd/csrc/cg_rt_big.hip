@@ -105,6 +105,7 @@ struct BigBufs {
     int bins_x, bins_y, tiles_x, tiles_y;
     int lat_w, lat_h;             // lattice mode: (2 W + 1) x (2 rows + 1) points; 0 = per-pixel mode
     int lat_yaw;                  // lattice columns per pixel (yawed camera): 3 W x (2 rows + 1) points
+    int hits_ray;                 // hits-only pass (launch_rt_big with RtHits): 1 + the sub-ray every pixel traces; 0: a frame
     int *sup_pool;                // [cap_sup] triangles the super-bins' certificates keep
     unsigned long long *sup_pbox_pool, *sup_flat_pbox;   // [cap_sup]: their projected boxes (super-bin bundle)
     Chunk *sup_chunk;             // [n_sups][nch]
@@ -1456,23 +1457,31 @@ __device__ __forceinline__ int launder(int v)
 // yawed (7 slots) and per-pixel (9 slots) modes need 3 for no scratch.  More
 // waves with some scratch are faster now (below).  CG_WALK_WAVES overrides
 // every mode (A/B builds).
+#ifndef CG_HITS_WAVES
+#define CG_HITS_WAVES 4
+#endif
 #ifdef CG_WALK_WAVES
 template <int LM> constexpr int walk_waves() { return CG_WALK_WAVES; }
 #else
 // Round 6, with the hints' grid walks queued: the lattice mode at 5 (96 VGPRs, 68 B of scratch;
 // C5 210.9 -> 216.7 fps, 6 waves 216.3) and the yawed mode at 4 (C5-yaw 145.0 -> 151.2, 5 waves
 // 149.6, 6 124.9); the per-pixel mode (no bench configuration) stays at 3
-template <int LM> constexpr int walk_waves() { return LM == 1 ? 5 : LM == 2 ? 4 : 3; }
+// the hits-only walk (one slot per lane): CG_HITS_WAVES, from its resource report
+template <int LM> constexpr int walk_waves() { return LM == 1 ? 5 : LM == 2 ? 4 : LM == 3 ? CG_HITS_WAVES : 3; }
 #endif
 
-template <int LM>   // 0: per-pixel mode, 1: lattice, 2: lattice with per-pixel columns
+// LM 3, the hits-only walk: one ray slot per lane, per-pixel geometry whatever the camera, the slot's
+// direction from B.hits_ray.  The bins' and tiles' direction boxes cover all nine sub-rays of their
+// pixels, so the lists are exact for any one of them.
+template <int LM>   // 0: per-pixel mode, 1: lattice, 2: lattice with per-pixel columns, 3: hits only (one sub-ray a pixel)
 __global__ __launch_bounds__(kRtThreads, walk_waves<LM>()) void rt_big_primary_kernel(RtFrame F, const RtTri *__restrict__ tc,
                                                                     const RtShade *__restrict__ shade,
                                                                     const RtSphere *__restrict__ sph, BigBufs B)
 {
     WGTB_T0;
-    constexpr bool kLat = LM > 0;
-    constexpr int NS = LM == 0 ? 9 : (LM == 1 ? 5 : 7);   // ray slots per lane (lattice: owned points / 64)
+    constexpr bool kLat = LM == 1 || LM == 2;
+    constexpr bool kHits = LM == 3;
+    constexpr int NS = LM == 0 ? 9 : (LM == 1 ? 5 : (LM == 2 ? 7 : 1));   // ray slots per lane (lattice: owned points / 64)
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;   // wave: uniform (SGPR)
     int bx = blockIdx.x, by = blockIdx.y;
     if (B.walk_order) {   // heavy-first (rt_walk_order_kernel): the long lists start early, not in the tail
@@ -1538,7 +1547,10 @@ __global__ __launch_bounds__(kRtThreads, walk_waves<LM>()) void rt_big_primary_k
     x0 = uniform_f32(x0); x1 = uniform_f32(x1); y0 = uniform_f32(y0); y1 = uniform_f32(y1);
     auto slot_nd = [&](int s) -> vec3 {                                              // :137
         if constexpr (kLat) return v3(rx[s], ry[s], F.focal);
-        else return v3(dir.x + (m * (float)(s / 3 - 1)), dir.y + (m * (float)(s % 3 - 1)), F.focal);
+        else if constexpr (kHits) {   // the pass's one sub-ray in slot 0
+            const int hs = B.hits_ray - 1;
+            return v3(dir.x + (m * (float)(hs / 3 - 1)), dir.y + (m * (float)(hs % 3 - 1)), F.focal);
+        } else return v3(dir.x + (m * (float)(s / 3 - 1)), dir.y + (m * (float)(s % 3 - 1)), F.focal);
     };
     const bool any = x0 <= x1;
     const int bin = (tx / kBinTilesX) + (ty / kBinTilesY) * B.bins_x;
@@ -1708,13 +1720,13 @@ __global__ __launch_bounds__(kRtThreads, walk_waves<LM>()) void rt_big_primary_k
         }
         B.hit_bi[id] = hit;
         B.hit_t[id] = bt[s];
-        if (!kLat && hit != INT_MIN && F.n_lights > 0) {
+        if (LM == 0 && hit != INT_MIN && F.n_lights > 0) {
             const float t = bt[s];
             vec3 pos = v3(F.cam[0] + t * nd.x, F.cam[1] + t * nd.y, F.cam[2] + t * nd.z);
             shadow_box_add(sb, lmin, lmax, pos, hit_normal(shade, sph, hit, pos));
         }
     }
-    if constexpr (!kLat) {   // the many-light path's boxes (per-pixel mode only)
+    if constexpr (LM == 0) {   // the many-light path's boxes (per-pixel mode only)
         ShadowBox W;
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
@@ -2450,6 +2462,45 @@ __global__ __launch_bounds__(kRtThreads) void rt_big_shade_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Hits-only pass: the walk's slots (rt_big_primary_kernel<3>: hit_bi / hit_t per pixel) as the
+// reference's Intersection records (skeleton.cpp:40-45), one thread per pixel.  distance = t *
+// length(dir) is the product the walk compared (tri_closest :307), a sphere's distance its t
+// (:341-355), position = start + dir * t (:330-331, :349).  Pixels of padding rows, and rays that
+// hit nothing, get the reference's initial record: distance FLT_MAX, the rest 0.
+__global__ __launch_bounds__(256) void rt_hits_gather_kernel(RtFrame F, BigBufs B, RtHits Hs)
+{
+    const int u = blockIdx.x * 64 + (threadIdx.x & 63), L = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (u >= F.W || L >= F.rows_out) return;
+    const size_t pix = (size_t)L * F.W + u;
+    const int v = shard_row(F, L);
+    cg_isect ci;
+    ci.position = cg_vec4{0, 0, 0, 0};
+    ci.distance = FLT_MAX;
+    ci.triangleIndex = 0;
+    ci.sphereIndex = 0;
+    int index = INT_MIN;
+    if (v < F.H) {
+        const int hit = B.hit_bi[pix];
+        if (hit != INT_MIN) {
+            const float t = B.hit_t[pix];
+            const int hs = Hs.sub_ray;
+            vec4 dir = v4((float)(u - F.W / 2), (float)(v - F.H / 2), F.focal, 1.0f);        // :126
+            dir = mat4_mul(F.R, dir);                                                    // :128
+            const vec3 d = v3(dir.x + (0.5f * (float)(hs / 3 - 1)), dir.y + (0.5f * (float)(hs % 3 - 1)), F.focal);   // :137
+            const vec3 td = d * t;
+            ci.position = cg_vec4{F.cam[0] + td.x, F.cam[1] + td.y, F.cam[2] + td.z, F.cam[3] + 0};
+            ci.distance = hit >= 0 ? t * length(d) : t;
+            ci.triangleIndex = hit >= 0 ? hit : -1;
+            ci.sphereIndex = hit >= 0 ? -1 : -1 - hit;
+            index = hit;
+        }
+    }
+    if (Hs.isect) Hs.isect[pix] = ci;
+    if (Hs.index) Hs.index[pix] = index;
+    if (Hs.distance) Hs.distance[pix] = ci.distance;
+}
+
+// ---------------------------------------------------------------------------
 // Lattice mode (K1): contiguous rows (whole frame or band), verdict bits for
 // every light in one word per point, and R leaving y alone with dir.x a
 // function of x alone (cg_rt.hip rt_lattice_ok): 1 = shared half-pixel
@@ -2466,9 +2517,10 @@ int rt_big_mode(const RtFrame &F)
 }
 static bool rt_big_lattice(const RtFrame &F) { return rt_big_mode(F) != 0; }
 
-BigBufs big_layout(const RtFrame &F, const BigCaps &caps)
+BigBufs big_layout(const RtFrame &F, const BigCaps &caps, int hits_ray = 0)
 {
     BigBufs B{};
+    B.hits_ray = hits_ray;
     B.bins_x = (F.W + kBinW - 1) / kBinW;
     B.bins_y = (F.rows_out + kBinH - 1) / kBinH;
     B.tiles_x = (F.W + 7) / 8;
@@ -2481,7 +2533,7 @@ BigBufs big_layout(const RtFrame &F, const BigCaps &caps)
     B.cap_sbin = caps.sbin;
     B.cap_sorted = caps.sorted;
     const int rows = std::min(F.rows_out, F.H - F.row0);
-    const int mode = rt_big_mode(F);
+    const int mode = hits_ray ? 0 : rt_big_mode(F);   // a hits-only pass: per-pixel geometry whatever the camera
     if (mode && rows > 0) {
         B.lat_yaw = mode == 2;
         B.lat_w = mode == 2 ? 3 * F.W : 2 * F.W + 1;
@@ -2501,7 +2553,7 @@ size_t big_counter_bytes(const BigBufs &B)
 // Ray slots (hits) and verdict words of the mode.
 static size_t big_slots(const BigBufs &B, const RtFrame &F)
 {
-    return B.lat_w ? (size_t)B.lat_w * B.lat_h : 9 * (size_t)F.rows_out * F.W;
+    return B.lat_w ? (size_t)B.lat_w * B.lat_h : (B.hits_ray ? 1 : 9) * (size_t)F.rows_out * F.W;
 }
 static size_t big_words(const BigBufs &B, const RtFrame &F)
 {
@@ -2604,14 +2656,16 @@ static void lit_bounds(BigBufs &B, const RtFrame &F, const RtGrid &G)
 hipError_t launch_rt_big(const RtFrame &F, RtTri *d_tc, const RtShade *d_shade, const RtSphere *d_sph,
                          const RtGrid &grid, void *scratch, uint32_t *d_out, hipStream_t st, const RtGeo *d_geo,
                          const cg_tri *d_tris,
-                         int pend_cap, const BigCaps &caps, unsigned long long *h_demand, int dry)
+                         int pend_cap, const BigCaps &caps, unsigned long long *h_demand, int dry, const RtHits *hits)
 {
-    BigBufs B = big_layout(F, caps);
+    // hits != null: a hits-only pass -- the same certificate and list passes, one ray slot per pixel
+    // in the walk, a gather into the caller's planes; no light set, no shadow or shading pass
+    BigBufs B = big_layout(F, caps, hits ? hits->sub_ray + 1 : 0);
     if (2 * B.bins_x * B.bins_y > kMaxSubs) return hipErrorInvalidValue;   // rt_bin_scan_kernel's LDS table
     big_carve(B, F, scratch);
     B.grid = grid;
     B.max_pend = pend_cap > 0 ? std::min(pend_cap, kMaxPend) : kMaxPend;
-    lit_bounds(B, F, grid);
+    if (!hits) lit_bounds(B, F, grid);
     const int bins = B.bins_x * B.bins_y;
     hipError_t e = hipMemsetAsync(B.pool_n, 0, big_counter_bytes(B), st);
     if (e != hipSuccess) return e;
@@ -2681,6 +2735,12 @@ hipError_t launch_rt_big(const RtFrame &F, RtTri *d_tc, const RtShade *d_shade, 
         const char *wo = std::getenv("CG_WALK_ORDER");
         if (wo && wo[0] == '0') B.walk_order = nullptr;
         else hipLaunchKernelGGL(rt_walk_order_kernel, dim3(1), dim3(1024), 0, st, B, (int)pgrid.x, (int)pgrid.y);
+    }
+    if (hits) {
+        kt_launch(KT_RT_HITS_WALK, rt_big_primary_kernel<3>, pgrid, dim3(kRtThreads), 0, st, F, d_tc, d_shade, d_sph, B);
+        kt_launch(KT_RT_HITS_GATHER, rt_hits_gather_kernel, dim3((F.W + 63) / 64, (F.rows_out + 3) / 4), dim3(256), 0, st,
+                  F, B, *hits);
+        return demand();
     }
     {
         const int kt_id = KT_RT_BIG_PRIMARY;
@@ -2789,9 +2849,9 @@ bool rt_grid_build(const cg_tri *t, int n, RtGrid &g, std::vector<int> &start, s
     return true;
 }
 
-size_t rt_big_scratch_bytes(const RtFrame &F, const BigCaps &caps)
+size_t rt_big_scratch_bytes(const RtFrame &F, const BigCaps &caps, bool hits)
 {
-    BigBufs B = big_layout(F, caps);
+    BigBufs B = big_layout(F, caps, hits ? 1 : 0);
     return big_scratch_bytes(B, F);
 }
 

@@ -53,11 +53,16 @@ void rt_box_columns(const double lo[3], const double hi[3], const cg_rt_camera *
 size_t rt_lattice_tiles(const RtFrame &);
 hipError_t launch_rt_big(const RtFrame &, RtTri *, const RtShade *, const RtSphere *, const RtGrid &, void *,
                          uint32_t *, hipStream_t, const RtGeo *, const cg_tri *, int, const BigCaps &,
-                         unsigned long long *, int);
+                         unsigned long long *, int, const RtHits * = nullptr);
+hipError_t launch_rt_hits_small(const RtFrame &, const cg_tri *, const RtSphere *, const RtHits &, hipStream_t);
+hipError_t launch_rt_pick(const RtFrame &, const cg_tri *, const RtSphere *, cg_vec4, cg_vec4, void *, cg_isect *, int *,
+                          hipStream_t);
+size_t rt_pick_scratch_bytes();
+void rt_pixel_ray(const cg_rt_camera *, int, int, int, cg_vec4 *, cg_vec4 *);
 bool rt_big_shadow_lists(const RtFrame &);
 int rt_big_mode(const RtFrame &);
 bool rt_grid_build(const cg_tri *, int, RtGrid &, std::vector<int> &, std::vector<int> &, size_t);
-size_t rt_big_scratch_bytes(const RtFrame &, const BigCaps &);
+size_t rt_big_scratch_bytes(const RtFrame &, const BigCaps &, bool hits = false);
 hipError_t launch_rt_unstripe(const uint32_t *, int, int, int, int, int, int, uint32_t *, hipStream_t);
 hipError_t launch_rt_pack_rgb24(const uint32_t *, int, int, int, int, uint8_t *, hipStream_t);
 hipError_t launch_rt_assemble(const uint8_t *, const RtBlocks &, int, uint32_t *, size_t, hipStream_t);
@@ -248,6 +253,7 @@ struct cg_ctx {
     hipEvent_t big_ev = nullptr;
     bool big_ev_live = false;
     unsigned long long big_last[4] = {};
+    bool big_last_hits = false;                 // big_last came from a hits-only pass (its own capacities)
     long long big_overflows = 0;
     // Large scenes, several frames in flight (rt_render_frames): slots 1 ..
     // kBigSlots - 1 with their own buffers, stream and demand read-back; slot 0
@@ -263,6 +269,19 @@ struct cg_ctx {
         hipStream_t st = nullptr;
     } xs[kBigSlots - 1];
     hipEvent_t bev_start = nullptr;
+    // Hit planes (cg_rt_hits_device, cg_rt_pick).  A hits-only pass of a large scene has buffers of
+    // its own -- the pass's RtTri, scratch, demand read-back -- so it never touches what a frame in
+    // flight on another stream reads, and pool capacities and a sizing state of its own, so frames
+    // and hit planes that alternate do not size the pools again each time.
+    struct HitsSlot {
+        DevBuf tc, big, planes, pick;
+        BigCaps caps{};
+        bool sized = false;
+        long long key = -1;
+        unsigned long long *demand = nullptr;
+        hipEvent_t ev = nullptr;
+        bool ev_live = false;
+    } hits;
     // the scene's box (rt_scene_box, once per cg_rt_set_scene): cg_dist's column
     // window of any camera from it in O(1) per frame -- no per-camera pass over
     // the scene (1M triangles: ~6 ms on the host) and no per-camera cache
@@ -480,6 +499,12 @@ extern "C" void cg_destroy(cg_ctx *c)
         if (x.st) (void)hipStreamDestroy(x.st);
     }
     if (c->bev_start) (void)hipEventDestroy(c->bev_start);
+    if (c->hits.ev) {
+        (void)hipEventSynchronize(c->hits.ev);
+        (void)hipEventDestroy(c->hits.ev);
+    }
+    if (c->hits.demand) (void)hipHostFree(c->hits.demand);
+    c->hits.tc.release(); c->hits.big.release(); c->hits.planes.release(); c->hits.pick.release();
     if (c->aux) (void)hipStreamSynchronize(c->aux);
     for (int k = 0; k < cg_ctx::kRastLanes; ++k) {
         if (c->lanes[k]) cg_destroy(c->lanes[k]);
@@ -596,6 +621,7 @@ extern "C" int cg_rt_set_scene(cg_ctx *c, const cg_tri *tris, int n_tris, const 
     c->gbuild.cells = c->gbuild.entries = c->gbuild.cands = 0;
     c->gbuild.phase_live = 0;
     c->big_sized = false;   // the next large-scene frame sizes the pools
+    c->hits.sized = false;
     if (n_tris > 64) {   // large scene: grid for the shadow-ray blocker search
         std::vector<int> gs, gt;
         RtGrid g{};
@@ -645,6 +671,7 @@ extern "C" int cg_rt_set_scene_device(cg_ctx *c, const cg_tri *d_tris, int n_tri
     c->grid = RtGrid{};
     c->grid_entries = 0;
     c->big_sized = false;
+    c->hits.sized = false;
     c->n_tris = -1;   // no scene until the build below is through
     SceneBounds sb;
     CG_TRY(c, rt_grid_bounds_device(c->gbuild, (const cg_tri *)c->tris.p, n_tris, sb, st), "scene bounds");
@@ -965,6 +992,7 @@ static BigSlot big_slot(cg_ctx *c, int q)
 }
 
 static bool big_observe(cg_ctx *c, bool sizing, int q);
+static bool hits_observe(cg_ctx *c, bool sizing);
 
 // Settle both slots' outstanding pool demand (blocks on their last frames).
 static int big_observe_all(cg_ctx *c)
@@ -976,6 +1004,10 @@ static int big_observe_all(cg_ctx *c)
             big_observe(c, false, q);
         }
     }
+    if (c->hits.ev_live) {   // a hits-only pass reports like a frame
+        CG_TRY(c, hipEventSynchronize(c->hits.ev), "pool demand");
+        hits_observe(c, false);
+    }
     return CG_OK;
 }
 
@@ -986,8 +1018,10 @@ extern "C" int cg_rt_scratch_info(cg_ctx *c, uint64_t *out)
     const unsigned long long *d = c->big_last;
     out[0] = c->big.bytes;
     for (const auto &x : c->xs) out[0] += x.big.bytes;
+    out[0] += c->hits.big.bytes;
     out[1] = d[0] + d[1] + d[2] + d[3];
-    out[2] = (uint64_t)(c->big_caps.sup + c->big_caps.bin + c->big_caps.sbin + c->big_caps.sorted);
+    const BigCaps &caps = c->big_last_hits ? c->hits.caps : c->big_caps;   // the pools the latest pass listed in
+    out[2] = (uint64_t)(caps.sup + caps.bin + caps.sbin + caps.sorted);
     out[3] = (uint64_t)c->big_overflows;
     return CG_OK;
 }
@@ -1039,6 +1073,9 @@ extern "C" int cg_rt_set_pool_caps(cg_ctx *c, long long sup, long long bin, long
     c->big_sized = false;
     c->big_key = -1;
     c->big_overflows = 0;
+    c->hits.caps = BigCaps{};
+    c->hits.sized = false;
+    c->hits.key = -1;
     return CG_OK;
 }
 
@@ -1104,6 +1141,7 @@ static bool big_observe(cg_ctx *c, bool sizing, int q)
     }
     if (!sizing) c->big_overflows += over;
     *b.ev_live = false;
+    c->big_last_hits = false;
     return over;
 }
 
@@ -1241,6 +1279,158 @@ extern "C" int cg_rt_render_device(cg_ctx *c, const cg_light *lights, int n_ligh
     if (rc) return rc;
     if (F.wcols) return CG_E_INVALID;   // windows are for the RGB24 wire format
     return rt_enqueue(c, F, d_out, st);
+}
+
+// ---- hit planes and picking (cg_rt_hits.hip; large scenes: a hits-only pass of cg_rt_big.hip) ----
+extern "C" int cg_rt_pixel_ray(const cg_rt_camera *cam, int x, int y, int sub_ray, cg_vec4 *start, cg_vec4 *dir)
+{
+    if (!cam || !start || !dir || cam->width <= 0 || cam->height <= 0 || sub_ray < 0 || sub_ray > 8 || x < 0 ||
+        x >= cam->width || y < 0 || y >= cam->height)
+        return CG_E_INVALID;
+    rt_pixel_ray(cam, x, y, sub_ray, start, dir);
+    return CG_OK;
+}
+
+// big_observe for the hits slot: its demand becomes the latest reported one, its own capacities grow.
+static bool hits_observe(cg_ctx *c, bool sizing)
+{
+    cg_ctx::HitsSlot &S = c->hits;
+    std::memcpy(c->big_last, S.demand, sizeof(c->big_last));
+    const unsigned long long *d = c->big_last;
+    long long *cap[4] = {&S.caps.sup, &S.caps.bin, &S.caps.sbin, &S.caps.sorted};
+    bool over = false;
+    for (int k = 0; k < 4; ++k) {
+        const long long need = (long long)d[k];
+        over |= need > *cap[k];
+        if (!c->big_fixed && (sizing || need * 5 > *cap[k] * 4))
+            *cap[k] = std::min<long long>(need + need / 4 + 4096, (1ll << 31) - 1);
+    }
+    if (!sizing) c->big_overflows += over;
+    S.ev_live = false;
+    c->big_last_hits = true;
+    return over;
+}
+
+// The hits-only pass of a large scene, sized as rt_big_enqueue sizes a frame: dry passes of the list
+// kernels on the first call of a scene or shape, then growth from the demand each call reports.
+static int rt_hits_big_enqueue(cg_ctx *c, const RtFrame &F, const RtHits &Hs, hipStream_t st)
+{
+    cg_ctx::HitsSlot &S = c->hits;
+    if (!S.demand) {
+        CG_TRY(c, hipHostMalloc((void **)&S.demand, 4 * sizeof(unsigned long long), hipHostMallocDefault),
+               "alloc pool demand");
+        std::memset(S.demand, 0, 4 * sizeof(unsigned long long));
+        CG_TRY(c, hipEventCreateWithFlags(&S.ev, hipEventDisableTiming), "pool event");
+    }
+    CG_TRY(c, S.tc.ensure((size_t)std::max(c->n_tris, 1) * sizeof(RtTri)), "alloc tri constants");
+    if (c->big_fixed) {
+        S.caps = c->big_caps;
+    } else if (S.caps.sup == 0) {   // first guess; the first call corrects it
+        const long long g = 2ll * F.n_tris + 65536;
+        S.caps = BigCaps{g, g, 4096, 2 * g};
+    }
+    const long long key = ((long long)F.W * 65536 + F.rows_out) * 2 + (F.nranks == 1);
+    if (key != S.key) {
+        S.key = key;
+        S.sized = false;
+    }
+    if (c->big_fixed) S.sized = true;
+    if (S.ev_live && hipEventQuery(S.ev) == hipSuccess) hits_observe(c, false);
+    int stage = S.sized ? 0 : 1;
+    KtScope kt(KT_RT_HITS_PASS, st);
+    for (int pass = 0; pass < 8; ++pass) {
+        const int dry = pass == 7 ? 0 : stage;
+        const size_t need = rt_big_scratch_bytes(F, S.caps, true);
+        if ((need > S.big.bytes || need < S.big.bytes / 2) && S.big.p) {
+            CG_TRY(c, hipDeviceSynchronize(), "drain before resizing scratch");
+            S.big.release();
+        }
+        CG_TRY(c, S.big.ensure(need), "alloc hits scratch");
+        CG_TRY(c, launch_rt_big(F, (RtTri *)S.tc.p, (const RtShade *)c->shade.p, (const RtSphere *)c->sph.p, c->grid,
+                                S.big.p, nullptr, st, (const RtGeo *)c->geo.p, (const cg_tri *)c->tris.p, 0, S.caps,
+                                S.demand, dry, &Hs),
+               "rt_big hits launch");
+        CG_TRY(c, hipEventRecord(S.ev, st), "pool event");
+        S.ev_live = true;
+        if (!dry) break;
+        CG_TRY(c, hipEventSynchronize(S.ev), "pool demand");
+        if (hits_observe(c, true)) continue;   // grown: the same stage again
+        S.sized = true;
+        stage = 0;
+    }
+    return CG_OK;
+}
+
+extern "C" int cg_rt_hits_device(cg_ctx *c, const cg_rt_camera *cam, int sub_ray, const cg_rt_shard *shard,
+                                 cg_isect *d_isect, int32_t *d_index, float *d_distance, void *stream)
+{
+    if (!c || !cam || cam->width <= 0 || cam->height <= 0 || sub_ray < 0 || sub_ray > 8 ||
+        (!d_isect && !d_index && !d_distance))
+        return CG_E_INVALID;
+    if (c->n_tris < 0) {
+        c->err = "hits before cg_rt_set_scene";
+        return CG_E_NOSCENE;
+    }
+    RtFrame F;
+    if (int rc = frame_shape(cam, shard, F)) return rc;
+    if (F.wcols) return CG_E_INVALID;   // windows are for the RGB24 wire format
+    F.n_tris = c->n_tris;
+    F.n_sph = c->n_sph;
+    F.nbound = c->nbound;   // no light set: n_lights 0, lights null
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const RtHits Hs{sub_ray, d_isect, d_index, d_distance};
+    if (F.n_tris > 64) return rt_hits_big_enqueue(c, F, Hs, st);
+    CG_TRY(c, launch_rt_hits_small(F, (const cg_tri *)c->tris.p, (const RtSphere *)c->sph.p, Hs, st), "rt_hits launch");
+    return CG_OK;
+}
+
+extern "C" int cg_rt_hits(cg_ctx *c, const cg_rt_camera *cam, int sub_ray, cg_isect *isect, int32_t *index,
+                          float *distance)
+{
+    if (!c || !cam || cam->width <= 0 || cam->height <= 0 || (!isect && !index && !distance)) return CG_E_INVALID;
+    if (sub_ray < 0 || sub_ray > 8) return CG_E_INVALID;
+    if (c->n_tris < 0) return CG_E_NOSCENE;
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    const size_t n = (size_t)cam->width * cam->height;
+    CG_TRY(c, c->hits.planes.ensure(n * (sizeof(cg_isect) + sizeof(int32_t) + sizeof(float))), "alloc hit planes");
+    cg_isect *d_isect = (cg_isect *)c->hits.planes.p;
+    int32_t *d_index = (int32_t *)(d_isect + n);
+    float *d_distance = (float *)(d_index + n);
+    cg_rt_shard whole{0, 1, cam->height, 0, cam->height, 0, 0};   // a band of exactly the frame's rows
+    if (int rc = cg_rt_hits_device(c, cam, sub_ray, &whole, isect ? d_isect : nullptr, index ? d_index : nullptr,
+                                   distance ? d_distance : nullptr, c->stream))
+        return rc;
+    if (isect) CG_TRY(c, hipMemcpyAsync(isect, d_isect, n * sizeof(cg_isect), hipMemcpyDeviceToHost, c->stream), "d2h");
+    if (index) CG_TRY(c, hipMemcpyAsync(index, d_index, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream), "d2h");
+    if (distance)
+        CG_TRY(c, hipMemcpyAsync(distance, d_distance, n * sizeof(float), hipMemcpyDeviceToHost, c->stream), "d2h");
+    CG_TRY(c, hipStreamSynchronize(c->stream), "hits sync");
+    return CG_OK;
+}
+
+extern "C" int cg_rt_pick(cg_ctx *c, const cg_rt_camera *cam, int x, int y, int sub_ray, cg_isect *out, int *hit)
+{
+    if (!c || !out || !hit) return CG_E_INVALID;
+    cg_vec4 start, dir;
+    if (int rc = cg_rt_pixel_ray(cam, x, y, sub_ray, &start, &dir)) return rc;
+    if (c->n_tris < 0) return CG_E_NOSCENE;
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    const size_t part = (rt_pick_scratch_bytes() + 15) & ~(size_t)15;
+    CG_TRY(c, c->hits.pick.ensure(part + sizeof(cg_isect) + sizeof(int)), "alloc pick scratch");
+    char *p = (char *)c->hits.pick.p;
+    cg_isect *d_out = (cg_isect *)(p + part);
+    int *d_hit = (int *)(d_out + 1);
+    RtFrame F;
+    std::memset(&F, 0, sizeof(F));
+    F.n_tris = c->n_tris;
+    F.n_sph = c->n_sph;
+    CG_TRY(c, launch_rt_pick(F, (const cg_tri *)c->tris.p, (const RtSphere *)c->sph.p, start, dir, p, d_out, d_hit,
+                             c->stream), "rt_pick launch");
+    CG_TRY(c, hipMemcpyAsync(out, d_out, sizeof(cg_isect), hipMemcpyDeviceToHost, c->stream), "d2h");
+    CG_TRY(c, hipMemcpyAsync(hit, d_hit, sizeof(int), hipMemcpyDeviceToHost, c->stream), "d2h");
+    CG_TRY(c, hipStreamSynchronize(c->stream), "pick sync");
+    return CG_OK;
 }
 
 // Frames f0 .. f0 + nf - 1 of a batch, one prepare + one lattice launch

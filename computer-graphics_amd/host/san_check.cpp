@@ -184,6 +184,17 @@ int main(int argc, char **argv)
         int c0 = 0, c1 = 0;
         (void)cg_rt_frame_columns(t, n, &sph, 1, &cam, &c0, &c1);
         (void)cg_rt_frame_columns(rnd.data(), 5000, nullptr, 0, &cam, &c0, &c1);
+        // the ray of a pixel's sub-ray (host-only): the frame's corners, every sub-ray, and the rejected arguments
+        for (int s = -1; s <= 9; ++s)
+            for (int x : {-1, 0, 1919, 1920})
+                for (int y : {-1, 0, 1079, 1080}) {
+                    cg_vec4 start{}, dir{};
+                    const bool ok = s >= 0 && s <= 8 && x >= 0 && x < 1920 && y >= 0 && y < 1080;
+                    if (cg_rt_pixel_ray(&cam, x, y, s, &start, &dir) != (ok ? CG_OK : CG_E_INVALID))
+                        fail("cg_rt_pixel_ray", s);
+                    if (ok && (dir.z != 1080.0f || dir.w != 1.0f || start.z != z)) fail("cg_rt_pixel_ray ray", s);
+                }
+        if (cg_rt_pixel_ray(nullptr, 0, 0, 4, nullptr, nullptr) != CG_E_INVALID) fail("cg_rt_pixel_ray null", -1);
         // kernel routes (host-only): identity, a yaw, NaN and huge entries, shards, large scenes
         const cg_rt_shard shards[3] = {{0, 1, 15, 0, 0, 0, 0}, {1, 3, 8, 0, 0, 0, 0}, {0, 1, 15, 135, 270, 0, 0}};
         for (int variant = 0; variant < 4; ++variant) {

@@ -293,6 +293,42 @@ int cg_rt_probe_closest(cg_ctx *ctx, const cg_vec4 *starts, const cg_vec4 *dirs,
                         cg_isect *out, int *hit);
 int cg_rt_probe_direct_light(cg_ctx *ctx, const cg_isect *isects, const cg_light *light, int n,
                              cg_vec3 *out);
+/* ---- per-pixel hit records and picking --------------------------------------
+ * Every sub-ray Draw traces ends in an Intersection (skeleton.cpp:40-45, 263-363); these calls hand
+ * it back instead of a colour.  No light set is involved.  They work for any R, do not disturb
+ * frames in flight (a large scene's hits-only pass has buffers of its own) and leave later renders
+ * on the context unchanged. */
+enum { CG_RT_HIT_NONE = INT32_MIN };   /* d_index: triangle k >= 0, sphere q as -1 - q, else this */
+
+/* Host-only, no device work: the ray Draw traces for pixel (x, y), sub-ray s = 3 (i + 1) + (j + 1)
+ * (skeleton.cpp:126-137; s = 4 is the pixel centre): start = cameraPos, dir = (d.x + 0.5 i,
+ * d.y + 0.5 j, focal, 1) with d = R * (x - W/2, y - H/2, focal, 1), formed with the library's own
+ * matrix product, so that it is the ray every kernel forms.  CG_E_INVALID for sub_ray outside 0..8
+ * or a pixel outside the frame. */
+int cg_rt_pixel_ray(const cg_rt_camera *cam, int x, int y, int sub_ray, cg_vec4 *start, cg_vec4 *dir);
+
+/* ClosestIntersection of sub-ray `sub_ray` (0..8) of every pixel of this shard's rows, enqueued on
+ * `stream`, no synchronisation after the first call of a scene or frame shape (a large scene sizes
+ * its list pools then, as its first frame does).  Any of the three outputs may be NULL, not all
+ * three.  The planes are cg_rt_shard_rows() rows of W, row-major, like cg_rt_render_device's output.
+ * d_isect[p] holds exactly the bytes cg_rt_probe_closest writes for that pixel's ray, the miss record
+ * included (distance FLT_MAX, position 0, both indices 0); d_index[p] is as the enum says;
+ * d_distance[p] is the record's distance.  Padding rows of the last stripe are misses.
+ * Scenes of at most 64 triangles test every triangle per pixel; larger ones run the large-scene
+ * path's certificate and list passes and a walk of one ray per pixel (no shadow or shading pass);
+ * cg_rt_scratch_info / cg_rt_pool_demand report for it, and a pool overflow takes the same fallback
+ * over every triangle.  CG_E_NOSCENE before a scene is set; CG_E_INVALID for sub_ray outside 0..8
+ * or all outputs NULL. */
+int cg_rt_hits_device(cg_ctx *ctx, const cg_rt_camera *cam, int sub_ray, const cg_rt_shard *shard,
+                      cg_isect *d_isect, int32_t *d_index, float *d_distance, void *stream);
+/* Host-memory form, whole frame (H rows of W), synchronous. */
+int cg_rt_hits(cg_ctx *ctx, const cg_rt_camera *cam, int sub_ray, cg_isect *isect, int32_t *index, float *distance);
+/* One pixel, synchronous, without building a frame's lists: every triangle against the one ray,
+ * workgroups striding over the scene, the lexicographic minimum of (distance, index).  *out is the
+ * record cg_rt_hits gives for the pixel, *hit whether anything was hit.  CG_E_INVALID for a pixel
+ * outside the frame. */
+int cg_rt_pick(cg_ctx *ctx, const cg_rt_camera *cam, int x, int y, int sub_ray, cg_isect *out, int *hit);
+
 /* DirectLight's three divides by one area (:412) as the light-set sweep performs
  * them (a shared reciprocal inside a range guard, IEEE x / d outside it), on
  * device arrays: d_q[3i + k] = d_x[3i + k] / d_den[i]; a test that they are
@@ -647,7 +683,9 @@ int cg_image_decode_jpeg_device(cg_ctx *ctx, const uint8_t *data, size_t n, uint
  * rt_lattice_units_kernel, rt_lattice_kernel, rt_lattice_lights_kernel,
  * rt_pixel_kernel, rt_big_primary_kernel, rt_shadow_hints_kernel,
  * rast_fill_kernel and rast_post_kernel, on the stream it runs on, plus
- * "rt_big_frame" (a large scene's whole frame: events recorded around it).  cg_kernel_timing(on)
+ * "rt_big_frame" (a large scene's whole frame: events recorded around it) and, for a large scene's
+ * hits-only pass (cg_rt_hits_device), "rt_hits_pass" (the whole pass), "rt_hits_walk" and
+ * "rt_hits_gather".  cg_kernel_timing(on)
  * resets the totals (process-wide); cg_kernel_time waits for the recorded
  * launches and returns one kernel's summed launch milliseconds, its busy
  * milliseconds (the union of its launches' spans: launches that overlap on
