@@ -126,6 +126,7 @@ _SIGS = {
     "cg_rt_scratch_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
     "cg_rt_pool_demand": (C.c_int, [P, C.POINTER(C.c_uint64)]),
     "cg_rt_tile_masks": (C.c_int, [P, C.c_int, P, P, C.POINTER(C.c_int)]),
+    "cg_rt_lattice_path": (C.c_int, [P, C.POINTER(C.c_int)]),
     "cg_rt_route": (C.c_int, [C.POINTER(RtCamera), C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "cg_rt_set_pool_caps": (C.c_int, [P, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong]),
     "cg_rt_render_brute_device": (C.c_int, [P, C.POINTER(Light), C.c_int, C.POINTER(RtCamera), C.c_int, C.c_int, P, P]),
@@ -839,6 +840,13 @@ class Context:
         self._check(self.lib.cg_rt_tile_masks(self.h, frame, masks.ctypes.data_as(P),
                                               obj.ctypes.data_as(P) if slots else None, info), "cg_rt_tile_masks")
         return masks, obj
+
+    def rt_lattice_path(self):
+        """Diagnostic cg_rt_lattice_path: the latest batched one-light lattice call's (dispatch order,
+        published certificates, forced uncertified, workgroups)."""
+        info = (C.c_int * 4)()
+        self._check(self.lib.cg_rt_lattice_path(self.h, info), "cg_rt_lattice_path")
+        return info[0], bool(info[1]), bool(info[2]), info[3]
 
     def rt_render(self, cam, lights=None, n_lights=None):
         lights = default_lights() if lights is None else lights

@@ -66,15 +66,21 @@ struct LatTile {
     int u0, L0, v0, nu, nv, ax0, ay0, cols, rows;
     bool yaw;   // per-pixel columns
 };
+// ONE: a single rank's rows are contiguous (shard_row's k * stripe_h terms cancel), so the one-
+// light lattice kernel asks for no integer division there; the other kernels keep their code.
+// YAW: 0 / 1 where the caller's launch was chosen by lat_yaw(F) (launch_rt_lattice_frames; a
+// sequence's run is one route), so R is not read for it.
+template <bool ONE = false, int YAW = -1>
 __device__ __forceinline__ LatTile lat_tile(const RtFrame &F, int bx, int by)
 {
     LatTile G;
     G.u0 = bx * kLatTileW;
     G.L0 = by * kLatTileH;
-    G.v0 = shard_row(F, G.L0);   // the tile's rows v0 .. v0 + 14 lie in one stripe
+    // the tile's rows v0 .. v0 + 14 lie in one stripe
+    G.v0 = (ONE && F.nranks == 1) ? F.row0 + F.rank * F.stripe_h + G.L0 : shard_row(F, G.L0);
     G.nu = min(kLatTileW, F.W - G.u0);
     G.nv = max(0, min(min(kLatTileH, F.rows_out - G.L0), F.H - G.v0));
-    G.yaw = lat_yaw(F);
+    G.yaw = YAW < 0 ? lat_yaw(F) : YAW != 0;
     G.ax0 = 2 * (G.u0 - F.W / 2) - 1;
     G.ay0 = 2 * (G.v0 - F.H / 2) - 1;
     G.cols = G.yaw ? 3 * G.nu : 2 * G.nu + 1;
@@ -120,9 +126,11 @@ __host__ __device__ __forceinline__ int lat_tiles_x(const RtFrame &F) { return (
 // scripts/wg_timing.py.  Record: {kind << 56 | z << 40 | y << 20 | x, t0, t1, t2, t3, hardware
 // slot << 24 | blockIdx.x}; kind 1
 // (certificates) in the first half of the buffer, kind 2 (lattice) in the second, unused
-// slots zero.
+// slots zero.  Lattice records: t1 = t2 = the end, t3 = the end of the workgroup's head (s_wgt_head,
+// scripts/wg_head.py).
 __device__ unsigned long long *g_wgt;
 __device__ unsigned int g_wgt_n, g_wgt_cap;
+__shared__ unsigned long long s_wgt_head;   // thread 0: the workgroup's head is done (masks in registers; 0: it left before)
 __device__ __forceinline__ void wgt_record(unsigned long long kind, unsigned long long t0, unsigned long long t1,
                                            unsigned long long t2, unsigned long long t3)
 {
@@ -1472,8 +1480,7 @@ __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__r
     // per 20-frame launch, more VGPRs and SGPRs; the yawed form 0.7 % faster; profiles/r05_ab_walk.json)
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int by = S.by, bx = F.tx0 + S.bx;
-    LatTile G = lat_tile(F, bx, by);
-    G.yaw = PITCH != kLatW;   // the launch's choice (lat_yaw), a constant here
+    const LatTile G = lat_tile<true, PITCH != kLatW>(F, bx, by);   // yaw: the launch's choice (lat_yaw), a constant here
     lat_store_outside(F, G, o, S.bx);
     const int rows = G.rows;
     // per lattice point: .w = the hit object's table slot (enc; the zero slot: no hit);
@@ -1489,7 +1496,7 @@ __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__r
     __shared__ alignas(16) float s_z[kSoA ? PITCH * kLatH : 1];
     __shared__ int8_t s_h[kSoA ? PITCH * kLatH : 1];
     __shared__ Tab s_tab;
-    s_tab.load(F, shade, sph);
+    // (s_tab is loaded after the first closest-hit step, below)
     // the needed points, walked row-major at the full pitch; wave w takes the
     // w-th quarter
     const int npts = PITCH * rows;
@@ -1553,6 +1560,10 @@ __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__r
     const unsigned long long all = ((1ull << F.n_tris) - 1ull) | (F.n_sph > 0 ? (1ull << 63) : 0ull);
     const unsigned long long m0 = certified ? uniform_u64(lat_masks[2 * tix]) : all;
     const unsigned long long s0 = certified ? uniform_u64(lat_masks[2 * tix + 1]) : all;
+    if (m0 == 0ull) {                      // before anything else is loaded or computed
+        lat_store_black(F, G, o);
+        return;                            // the whole workgroup (m0 is uniform), ahead of its one barrier
+    }
     const unsigned long long mask = m0 & ~(3ull << 62), smask = s0 & ~(1ull << 63);
     const bool covered = (m0 >> 62) & 1ull;
     RtFrame Fp = F;                        // closest hit: spheres only where one may be hit
@@ -1565,11 +1576,6 @@ __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__r
     // lane j < kObjSlots holds slot j, every other lane the tile's mask (candidates past the last
     // slot): one vector load ahead of the steps instead of dependent scalar loads inside the shading
     const unsigned long long vobj = (objt && lane < kObjSlots) ? objt[lane] : s0;
-    if (m0 == 0ull) {
-        lat_store_black(F, G, o);
-        return;                            // the whole workgroup (m0 is uniform)
-    }
-    __syncthreads();                       // s_tab
     using Hit = HitSlot<Tab::kEnc>;
     // One pass per point.  A step of the wave finds the closest hits (:140) of its NP chunks of
     // 64 points as lat_closest does, then shades the chunks in ascending order (:151-153) from
@@ -1622,17 +1628,39 @@ __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__r
             }
         }
     };
-    for (int p0 = p_lo; p0 < p_hi; p0 += step1) {
+    // The table's load and its barrier stand after the first step's closest hits, which need
+    // nothing of it: no wave waits for the table or for the other waves before it has done that
+    // work (plain C2 +2.7 .. 3.0 %, f256 +6 %; profiles/r11_ab_head.json).  The loads are issued
+    // after the step, not held across it (held: 70 VGPRs at pitch 33, seven workgroups per CU).  Every
+    // wave takes the first turn of the loop, a wave without a point too (a 16 x 1 frame), so each
+    // reaches the barrier exactly once; the returns above are workgroup-uniform and come before it.
+    // Shared columns: one step is the wave's whole tile (33 x 31 points < 1024 = step1).
+    static_assert(!kNP4 || kLatW * kLatH <= 1024, "a wave of the shared-column form takes one step");
+    auto turn = [&](int p0, auto with_table) {
         float X[kNP], Y[kNP], t[kNP];
         bool live[kNP];
         int pp[kNP], hit[kNP];
-        lat_closest_step<PITCH, kNP, Hit>(Fp, tc, sph, mask, covered, G, p0, p_hi, lane, kStride, true, pp, live, X, Y,
-                                          t, hit);
+        const bool any = p0 < p_hi;   // wave-uniform
+        if (any)
+            lat_closest_step<PITCH, kNP, Hit>(Fp, tc, sph, mask, covered, G, p0, p_hi, lane, kStride, true, pp, live, X,
+                                              Y, t, hit);
+        if constexpr (decltype(with_table)::value) {
+            s_tab.load(F, shade, sph);
+            __syncthreads();               // s_tab
+        }
+        if (any) {
 #pragma unroll
-        for (int n = 0; n < kNP; ++n)
-            if (p0 + kStride * n < p_hi)   // a chunk past the tile's points has no live lane
-                shade_pt(pp[n], live[n], X[n], Y[n], t[n], hit[n]);
-    }
+            for (int n = 0; n < kNP; ++n)
+                if (p0 + kStride * n < p_hi)   // a chunk past the tile's points has no live lane
+                    shade_pt(pp[n], live[n], X[n], Y[n], t[n], hit[n]);
+        }
+    };
+#ifdef CG_WG_TIMING
+    if (threadIdx.x == 0) s_wgt_head = wall_clock64();
+#endif
+    turn(p_lo, std::true_type{});
+    if constexpr (!kNP4)
+        for (int p0 = p_lo + step1; p0 < p_hi; p0 += step1) turn(p0, std::false_type{});
     __syncthreads();
     // Pixels: the nine contributions in the reference's order (:134-166).  Every point a pixel
     // reads holds (DirectLight, slot) -- a miss (0, 0, 0) and the zero slot -- so the sums test
@@ -2152,6 +2180,7 @@ __global__ __launch_bounds__(kRtThreads, kRtMinWaves) void rt_lattice_kernel(RtF
 {
 #ifdef CG_WG_TIMING
     const unsigned long long wt0 = wall_clock64();
+    if (threadIdx.x == 0) s_wgt_head = 0ull;
 #endif
     const unsigned long long t_start = wall_clock64();
     const LatSlot S = lat_slot_of(O);
@@ -2162,7 +2191,7 @@ __global__ __launch_bounds__(kRtThreads, kRtMinWaves) void rt_lattice_kernel(RtF
     lat_signal(frame_done, S.frame);
 #ifdef CG_WG_TIMING
     WGT_STAMP(wt3);
-    wgt_record(2, wt0, wt3, wt3, wt3);
+    wgt_record(2, wt0, wt3, wt3, threadIdx.x == 0 ? s_wgt_head : 0ull);
 #endif
 }
 

@@ -217,6 +217,8 @@ struct cg_ctx {
         int col0 = 0, col1 = 0;   // the tile columns the call certified (a windowed launch: its super-tiles')
         hipStream_t st = nullptr;
     } last_masks;
+    // how the latest batched lattice call was launched, for cg_rt_lattice_path
+    int last_path[4] = {0, 0, 0, 0};   // measured order, published certificates, forced uncertified, workgroups
     // Batched lattice launches pipeline their certificate kernels on `aux`:
     // call j+1's certificates run beside call j's lattice kernel, each call
     // with its own slot of buffers (rt_enqueue_lattice_batch).
@@ -1056,6 +1058,13 @@ extern "C" int cg_rt_tile_masks(cg_ctx *c, int frame, uint64_t *masks, uint64_t 
     return CG_OK;
 }
 
+extern "C" int cg_rt_lattice_path(cg_ctx *c, int *info)
+{
+    if (!c || !info) return CG_E_INVALID;
+    for (int k = 0; k < 4; ++k) info[k] = c->last_path[k];
+    return CG_OK;
+}
+
 extern "C" int cg_rt_pool_demand(cg_ctx *c, uint64_t *out)
 {
     if (!c || !out) return CG_E_INVALID;
@@ -1695,6 +1704,10 @@ static int rt_enqueue_lattice_batch(cg_ctx *c, const RtFrame &F0, const cg_rt_ca
                                        d_done, ordered ? &order : nullptr, ready.flags ? &ready : nullptr, obj,
                                        d_recs),
            "rt_lattice launch");
+    c->last_path[0] = ordered ? (order.ngroups < 0 ? 1 : 2) : 0;
+    c->last_path[1] = ready.flags != nullptr;
+    c->last_path[2] = ready.flags != nullptr && ready.force;
+    c->last_path[3] = (int)std::min<long long>((long long)gx * gy * nf, INT_MAX);
     c->last_masks.lat = lat;
     c->last_masks.obj = obj;
     c->last_masks.tiles_x = lat_tiles_x_host(F);

@@ -359,6 +359,15 @@ int cg_rt_pool_demand(cg_ctx *ctx, uint64_t *out);
  * for hits on the j-th set triangle of the primary mask, the last word for
  * hits on a sphere.  With both null only info is filled. */
 int cg_rt_tile_masks(cg_ctx *ctx, int frame, uint64_t *masks, uint64_t *obj_masks, int *info);
+/* Diagnostic: how the latest batched one-light lattice call on this context
+ * (cg_rt_render_frames_device and the calls built on it) launched its lattice
+ * kernel.  info[0] = the dispatch order (0 default, 1 frame-major measured,
+ * 2 interleaved measured), info[1] = 1 when its workgroups waited for
+ * certificates published beside the launch (CG_CERT_CONC=1 on a call in the
+ * default order), info[2] = 1 when every workgroup was forced onto the
+ * uncertified path (CG_LAT_FORCE_UNCERT=1), info[3] = its workgroups.  All 0
+ * before any such call. */
+int cg_rt_lattice_path(cg_ctx *ctx, int *info);
 /* Test hook: pin the large-scene pool capacities (entries: super-bin, bin,
  * many-light shadow and bucketed lists; all 0 = automatic sizing).  Lists past a capacity take the fallback over every triangle; the
  * image is the same. */
