@@ -94,6 +94,34 @@ class RastTextures(C.Structure):   # cg_rast_textures
     _fields_ = [(n, C.c_void_p) for n in TEXTURE_MAPS]
 
 
+# cg_rast_buffers: the planes of a buffers call, (name, numpy dtype, values per pixel) in the
+# structure's order; a null pointer = not asked for
+RAST_PLANES = (("argb", np.uint32, 1), ("depth", np.float32, 1), ("shadow", np.int32, 1),
+               ("screen", np.float32, 3), ("low", np.float32, 3), ("high", np.float32, 3),
+               ("clip", np.int32, 1), ("tri", np.int32, 1), ("pos", np.float32, 4))
+RAST_OWNER_NONE = -1
+
+
+class RastBuffers(C.Structure):    # cg_rast_buffers
+    _fields_ = [(n, C.c_void_p) for n, _, _ in RAST_PLANES]
+
+
+def rast_buffers_planes(params, want):
+    """Host planes of a buffers call (no device work): (RastBuffers, {name: array}) for the plane
+    names in `want`, each W * H rows of its values (RAST_PLANES)."""
+    names = [n for n, _, _ in RAST_PLANES]
+    bad = [w for w in want if w not in names]
+    if bad:
+        raise ValueError(f"no such rasteriser plane: {bad} (one of {names})")
+    npx = params.width * params.height
+    out, b = {}, RastBuffers()
+    for n, dt, k in RAST_PLANES:
+        if n in want:
+            out[n] = np.zeros(npx if k == 1 else (npx, k), dt)
+            setattr(b, n, out[n].ctypes.data)
+    return b, out
+
+
 _SIGS = {
     "cg_create": (C.c_int, [C.c_int, C.POINTER(P)]),
     "cg_destroy": (None, [P]),
@@ -187,6 +215,15 @@ _SIGS = {
     "cg_rast_row_blocks": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "cg_rast_random_scene": (C.c_int, [C.c_uint64, C.c_int, C.c_float, C.POINTER(RTri)]),
     "cg_glibc_rand_device": (C.c_int, [P, P, C.c_int, P, P]),
+    "cg_rast_draw_buffers_device": (C.c_int, [P, C.POINTER(RastParams), C.POINTER(RastBuffers), P]),
+    "cg_rast_draw_buffers": (C.c_int, [P, C.POINTER(RastParams), C.POINTER(RastBuffers), C.POINTER(Stats)]),
+    "cg_rast_render_buffers_device": (C.c_int, [P, P, C.c_int, C.POINTER(RastParams), Vec4,
+                                                C.POINTER(RastBuffers), P]),
+    "cg_rast_render_buffers": (C.c_int, [P, C.POINTER(RTri), C.c_int, C.POINTER(RastParams), Vec4,
+                                         C.POINTER(RastBuffers), C.POINTER(Stats)]),
+    "cg_rast_pick": (C.c_int, [P, C.POINTER(RastParams), C.c_int, C.c_int, C.POINTER(C.c_int32),
+                               C.POINTER(C.c_int32), C.POINTER(Vec4), C.POINTER(C.c_int)]),
+    "cg_rast_state_bytes": (C.c_int, [P]),
     "cg_dist_unique_id": (C.c_int, [P]),
     "cg_dist_create": (C.c_int, [P, C.c_int, C.c_int, P, C.POINTER(P)]),
     "cg_dist_create_timed": (C.c_int, [P, C.c_int, C.c_int, P, C.c_int, C.POINTER(P)]),
@@ -1155,6 +1192,61 @@ class Context:
             depth.ctypes.data_as(P) if depth is not None else None,
             shadow.ctypes.data_as(P) if shadow is not None else None, C.byref(st)), "cg_rast_draw")
         return argb, depth, shadow, st
+
+    ALL_RAST_PLANES = tuple(n for n, _, _ in RAST_PLANES)
+
+    def rast_draw_buffers(self, params, want=ALL_RAST_PLANES, stats=None):
+        """cg_rast_draw_buffers: the Draw of rast_draw with the planes named in `want` (RAST_PLANES:
+        argb, depth, shadow, the HDR triple screen / low / high, the owner's clip / tri / pos) as a
+        dict of numpy arrays."""
+        b, out = rast_buffers_planes(params, want)
+        self._check(self.lib.cg_rast_draw_buffers(self.h, C.byref(params), C.byref(b),
+                                                  C.byref(stats) if stats is not None else None),
+                    "cg_rast_draw_buffers")
+        return out
+
+    def rast_render_buffers(self, tris, n, params, light, want=ALL_RAST_PLANES, stats=None):
+        """cg_rast_render_buffers: rast_render's frame of a clipped list with the planes in `want`
+        (tri = clip: the caller's list is the clipped list)."""
+        b, out = rast_buffers_planes(params, want)
+        self._check(self.lib.cg_rast_render_buffers(self.h, tris, n, C.byref(params), light, C.byref(b),
+                                                    C.byref(stats) if stats is not None else None),
+                    "cg_rast_render_buffers")
+        return out
+
+    @staticmethod
+    def _rast_buffers_device(planes):
+        b = RastBuffers()
+        for name, ptr in planes.items():
+            if name not in Context.ALL_RAST_PLANES:
+                raise ValueError(f"no such rasteriser plane: {name}")
+            setattr(b, name, ptr if ptr else None)
+        return b
+
+    def rast_draw_buffers_device(self, params, stream=None, **planes):
+        """cg_rast_draw_buffers_device: planes by name (argb=, depth=, ..., pos=) as device addresses."""
+        b = self._rast_buffers_device(planes)
+        self._check(self.lib.cg_rast_draw_buffers_device(self.h, C.byref(params), C.byref(b),
+                                                         P(stream) if stream else None),
+                    "cg_rast_draw_buffers_device")
+
+    def rast_render_buffers_device(self, d_tris, n, params, light, stream=None, **planes):
+        """cg_rast_render_buffers_device: as rast_draw_buffers_device over a device list."""
+        b = self._rast_buffers_device(planes)
+        self._check(self.lib.cg_rast_render_buffers_device(self.h, P(d_tris), n, C.byref(params), light, C.byref(b),
+                                                           P(stream) if stream else None),
+                    "cg_rast_render_buffers_device")
+
+    def rast_pick(self, params, x, y):
+        """cg_rast_pick: (tri, clip, pos float32[4], hit) of the fragment that owns pixel (x, y)."""
+        tri, clip, pos, hit = C.c_int32(), C.c_int32(), Vec4(), C.c_int()
+        self._check(self.lib.cg_rast_pick(self.h, C.byref(params), x, y, C.byref(tri), C.byref(clip), C.byref(pos),
+                                          C.byref(hit)), "cg_rast_pick")
+        return tri.value, clip.value, np.array([pos.x, pos.y, pos.z, pos.w], np.float32), bool(hit.value)
+
+    def rast_state_bytes(self):
+        """cg_rast_state_bytes: 2 or 4, the state word the latest frame's fill left per pixel (0: no frame)."""
+        return self.lib.cg_rast_state_bytes(self.h)
 
     def rast_draw_device(self, params, d_argb, d_depth=None, d_shadow=None, stream=None):
         self._check(self.lib.cg_rast_draw_device(self.h, C.byref(params), P(d_argb), P(d_depth) if d_depth else None,

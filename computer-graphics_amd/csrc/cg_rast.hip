@@ -814,6 +814,7 @@ static int rast_pipeline(cg_ctx *c, cg_rtri *d_tris, int n, int *n_dev, const cg
                        first_tri, recs, count);
     if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "rast_rows launch");
     const int post_grid = xcd_grid(H, (W + kPostTW - 1) / kPostTW);
+    void *words = state;   // the ordered z-buffer's state words (RastFrame)
     if (p->colour_mode != 0) {
         long long ns = -1;
         const int rc = seq ? rast_seq_colour_fill(c, A, p, recs, count, hdr, n_dev, nn, (float4 *)state, d_depth,
@@ -822,9 +823,20 @@ static int rast_pipeline(cg_ctx *c, cg_rtri *d_tris, int n, int *n_dev, const cg
                                               st, &ns);
         if (rc) return rc;
         if (stats) stats->n_shaded = ns;
-        hipLaunchKernelGGL((rast_post_kernel<true, false>), dim3(post_grid), dim3(256), 0, st, d_tris, A,
-                           (const void *)state, (const RowRec *)recs, shadow, d_argb,
-                           seq ? (const int32_t *)&seq->info->status : (const int32_t *)nullptr);
+        if (d_argb)   // null: a buffers call that asks for no picture
+            hipLaunchKernelGGL((rast_post_kernel<true, false>), dim3(post_grid), dim3(256), 0, st, d_tris, A,
+                               (const void *)state, (const RowRec *)recs, shadow, d_argb,
+                               seq ? (const int32_t *)&seq->info->status : (const int32_t *)nullptr);
+        if (ctx_rast_want_owner(c)) {
+            // the owner of a pixel is the ordered z-buffer's last writer whatever the colour mode
+            // (modes 1-2 ignore textures, :604): the mode-0 fill's walk into words of its own
+            words = ctx_buf(c, kBufOwner, npx * sizeof(uint32_t), &e);
+            if (!words) return ctx_fail(c, e, "alloc owner state");
+            A.state16 = nn < 32768;
+            const int fgrid = xcd_grid(H, ((W + kFillPx - 1) / kFillPx * kXcdRows + 3) / 4);
+            hipLaunchKernelGGL(rast_fill_kernel<false>, dim3(fgrid), dim3(256), 0, st, A, (const RowRec *)recs,
+                               (const int *)count, (uint32_t *)words, (float *)nullptr, (int32_t *)nullptr);
+        }
     } else {
         const int fgrid = xcd_grid(H, ((W + kFillPx - 1) / kFillPx * kXcdRows + 3) / 4);
         {
@@ -837,7 +849,9 @@ static int rast_pipeline(cg_ctx *c, cg_rtri *d_tris, int n, int *n_dev, const cg
                                    (uint32_t *)state, d_depth, d_shadow);
         }
         const int kt_id = KT_RAST_POST;
-        if (A.textured)
+        if (!d_argb) {
+            // a buffers call that asks for no picture
+        } else if (A.textured)
             kt_launch(kt_id, (rast_post_kernel<false, true>), dim3(post_grid), dim3(256), 0, st, d_tris, A,
                                (const void *)state, (const RowRec *)recs, (const int32_t *)nullptr, d_argb,
                                (const int32_t *)nullptr);
@@ -858,6 +872,19 @@ static int rast_pipeline(cg_ctx *c, cg_rtri *d_tris, int n, int *n_dev, const cg
         stats->n_spans = 0;
     }
     *ctx_rast_last(c) = RastLast{CG_RAST_ROUTE_DENSE, n_dev ? -1ll : (long long)n, 0, -1, n_dev, count, H, st};
+    RastFrame &fr = *ctx_rast_frame(c);
+    fr = RastFrame{};
+    fr.valid = p->colour_mode == 0 || words != state;
+    fr.route = CG_RAST_ROUTE_DENSE;
+    fr.mode = p->colour_mode;
+    fr.A = A;
+    fr.words = words;
+    fr.direct = p->colour_mode != 0 ? (const float4 *)state : nullptr;
+    fr.recs = recs;
+    fr.rec_cap = (unsigned long long)H * (unsigned long long)nn;
+    fr.counts = sg.stage ? sg.counts : nullptr;
+    fr.n_in = sg.n_in;
+    fr.st = st;
     return CG_OK;
 }
 

@@ -904,7 +904,7 @@ int big_colour(cg_ctx *c, const RastArgs &A, const cg_rast_params *p, const RowR
                            p->colour_mode, state, d_depth, shadow);
         if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "rast_big_shade launch");
     }
-    {
+    if (d_argb) {   // null: a buffers call that asks for no picture
         KtScope kt(KT_RAST_BIG_POST, st);
         launch_rast_post_direct(A, state, shadow, d_argb, st);
         if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "rast_post launch");
@@ -1032,10 +1032,23 @@ int big_pipeline(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *
         if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "rast_big_rows launch");
     }
     long long n_shaded = -1;
+    void *words = state;   // the ordered z-buffer's state words (RastFrame)
     if (colour) {
         const int rc = big_colour(c, A, p, recs, row_off, count, n_recs, rec_ent, n_ent, (float4 *)state, d_argb, d_depth,
                                   d_shadow, st, seq, &n_shaded);
         if (rc) return rc;
+        if (ctx_rast_want_owner(c)) {
+            // the owner of a pixel is the ordered z-buffer's last writer whatever the colour mode
+            // (modes 1-2 ignore textures, :604): the mode-0 fill's walk into words of its own
+            words = ctx_buf(c, kBufOwner, npx * sizeof(uint32_t), &e);
+            if (!words) return ctx_fail(c, e, "alloc owner state");
+            A.state16 = tot[1] < 32768;
+            const int fgrid = xcd_grid(H, ((W + kFillPx - 1) / kFillPx * kXcdRows + 3) / 4);
+            hipLaunchKernelGGL(rast_big_fill_kernel<false>, dim3(fgrid), dim3(256), 0, st, A, (const RowRec *)recs,
+                               (const u64 *)row_off, (const int *)count, n_recs, (uint32_t *)words, (float *)nullptr,
+                               (int32_t *)nullptr);
+            if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "rast_big_fill launch");
+        }
     } else {
         // -- fill and post
         {
@@ -1049,7 +1062,7 @@ int big_pipeline(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *
                                    (const u64 *)row_off, (const int *)count, n_recs, (uint32_t *)state, d_depth, d_shadow);
             if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "rast_big_fill launch");
         }
-        {
+        if (d_argb) {   // null: a buffers call that asks for no picture
             KtScope kt(KT_RAST_BIG_POST, st);
             const int post_grid = xcd_grid(H, (W + kPostTW - 1) / kPostTW);
             if (A.textured)
@@ -1073,6 +1086,18 @@ int big_pipeline(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *
     }
     *ctx_rast_last(c) = RastLast{CG_RAST_ROUTE_COMPACT, (long long)n, (long long)n_spans, (long long)n_recs, nullptr,
                                  nullptr, H, st};
+    RastFrame &fr = *ctx_rast_frame(c);
+    fr = RastFrame{};
+    fr.valid = !colour || words != state;
+    fr.route = CG_RAST_ROUTE_COMPACT;
+    fr.mode = p->colour_mode;
+    fr.A = A;
+    fr.words = words;
+    fr.direct = colour ? (const float4 *)state : nullptr;
+    fr.recs = recs;
+    fr.row_off = row_off;
+    fr.rec_cap = n_recs;
+    fr.st = st;
     return CG_OK;
 }
 
@@ -1131,8 +1156,15 @@ int rast_big_draw(cg_ctx *c, const cg_rtri *d_room, int n_room, const cg_rtri *d
         if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "rast_big_gather launch");
     }
     if (n_out) *n_out = (int *)(pre + n_in);   // little-endian: the count's low word
-    return big_pipeline(c, tris, n, p, cg_vec4{0, 0, 0, 1}, (const cg_vec4 *)(geo + 4), d_argb, d_depth, d_shadow, st,
-                        stats, true, n_in > 0, tex_mask, seq);
+    const int rc = big_pipeline(c, tris, n, p, cg_vec4{0, 0, 0, 1}, (const cg_vec4 *)(geo + 4), d_argb, d_depth, d_shadow,
+                                st, stats, true, n_in > 0, tex_mask, seq);
+    if (rc == CG_OK) {   // clipped triangle -> input triangle: the counts and the prefix the gather used
+        RastFrame &fr = *ctx_rast_frame(c);
+        fr.counts = geo + 16;
+        fr.pre = pre;
+        fr.n_in = n_in;
+    }
+    return rc;
 }
 
 }  // namespace cg

@@ -82,6 +82,30 @@ struct RastLast {
     hipStream_t st = nullptr;
 };
 RastLast *ctx_rast_last(cg_ctx *c);
+struct RowRec;
+// What the latest frame left in context scratch, for the buffers kernel (cg_rast_buffers.hip):
+// the ordered z-buffer's state words and the row records they name.  Host bookkeeping only.
+struct RastFrame {
+    bool valid = false;
+    int route = 0, mode = 0;
+    RastArgs A;                          // as the fill saw them (state16: the form of `words`)
+    const void *words = nullptr;         // record + 1 | shadow mark in the top bit, per pixel
+    const float4 *direct = nullptr;      // colour modes 1-2: the colour fill's state
+    const RowRec *recs = nullptr;
+    const unsigned long long *row_off = nullptr;   // compact route; null: row y's records at y * A.n
+    unsigned long long rec_cap = 0;
+    // cg_rast_draw*: the clip's per-input counts and (compact route) their prefix; null: the
+    // caller's list is the clipped list
+    const int *counts = nullptr;
+    const unsigned long long *pre = nullptr;
+    int n_in = 0;
+    hipStream_t st = nullptr;
+};
+RastFrame *ctx_rast_frame(cg_ctx *c);
+// A buffers call is running the frame (cg_rast_draw_buffers*, cg_rast_pick): colour modes 1-2
+// also run the ordered z-buffer's fill for the state words, which they otherwise never make.
+bool ctx_rast_want_owner(cg_ctx *c);
+enum { kBufOwner = 40, kBufClipPre, kBufScreen, kBufLow, kBufHigh, kBufClipId, kBufTriId, kBufPos, kBufPick };
 // cg_rast_set_route(ctx, 1) holds: the A/B hook's compact frames are colour mode 0 only
 bool ctx_rast_forced_compact(cg_ctx *c);
 int rast_big_render(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *p, cg_vec4 light, uint32_t *d_argb,

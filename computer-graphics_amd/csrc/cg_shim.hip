@@ -308,6 +308,11 @@ struct cg_ctx {
     int rast_route = -1;                 // cg_rast_set_route: -1 automatic, else the forced route
     long long route_limit = 0;           // cg_rast_set_route_limit: 0 = cg_rast_route's 131072
     RastLast rlast;                      // the latest rasteriser frame (cg_rast_scratch_info)
+    // cg_rast_draw_buffers*, cg_rast_pick (cg_rast_buffers.hip): what the latest frame left in
+    // scratch, whether a buffers call is running it, and the calls' own buffers (kBufOwner ..)
+    RastFrame rframe;
+    bool rast_want_owner = false;
+    DevBuf rbuf[9];
     // cg_rast_draw_sequence_device: the generator's tables (windows, seed words, J_b for
     // rseq_chunks chunks) and the stream's capacity in fragments (0: 4 * W * H)
     DevBuf rseq;
@@ -380,6 +385,10 @@ void *ctx_buf(cg_ctx *c, int which, size_t bytes, hipError_t *e)
             b = &c->rbig[which - 20];
             break;
         }
+        if (which >= kBufOwner && which < kBufOwner + (int)(sizeof(c->rbuf) / sizeof(c->rbuf[0]))) {
+            b = &c->rbuf[which - kBufOwner];
+            break;
+        }
         *e = hipErrorInvalidValue;
         return nullptr;
     }
@@ -412,6 +421,8 @@ void rast_release(cg_ctx *c)
     c->rpc.release(); c->rtl.release(); c->rrnd.release(); c->rjt.release();
     c->rseq.release();
     for (DevBuf &b : c->rbig) b.release();
+    for (DevBuf &b : c->rbuf) b.release();
+    c->rframe = RastFrame{};
     c->sstars.release(); c->sframe.release();
     c->tmarble.release(); c->tnoise.release(); c->twoven.release(); c->twoven_ao.release();
     c->twoven_op.release(); c->twoven_nrm.release(); c->tgrill.release(); c->tgrill_op.release();
@@ -425,6 +436,8 @@ int ctx_rast_route(cg_ctx *c, long long cap)
 }
 bool ctx_rast_forced_compact(cg_ctx *c) { return c->rast_route == CG_RAST_ROUTE_COMPACT; }
 RastLast *ctx_rast_last(cg_ctx *c) { return &c->rlast; }
+RastFrame *ctx_rast_frame(cg_ctx *c) { return &c->rframe; }
+bool ctx_rast_want_owner(cg_ctx *c) { return c->rast_want_owner; }
 // the device texture maps and which textures are renderable (bit k: texture k)
 int rast_tex_maps(cg_ctx *c, RastTexMaps *m)
 {
@@ -2455,6 +2468,7 @@ extern "C" int cg_rast_scratch_info(cg_ctx *c, uint64_t out[5])
         size_t b = x->rtris.bytes + x->rhdr.bytes + x->rspan.bytes + x->rpix.bytes + x->rcount.bytes + x->rrecs.bytes +
                    x->rgeo.bytes;
         for (const DevBuf &d : x->rbig) b += d.bytes;
+        b += x->rbuf[kBufOwner - kBufOwner].bytes + x->rbuf[kBufClipPre - kBufOwner].bytes;   // a buffers call's scratch
         return b;
     };
     out[0] = held(c);
@@ -2824,6 +2838,157 @@ extern "C" int cg_rast_draw(cg_ctx *c, const cg_rast_params *p, uint32_t *argb, 
     }
     return CG_OK;
 }
+
+// ---- HDR shade buffers, owner ids, picking (kernels in cg_rast_buffers.hip) ----
+namespace cg {
+int rast_buffers_device(cg_ctx *c, const cg_rast_buffers *d, int n_room, hipStream_t st);
+int rast_pick_device(cg_ctx *c, int n_room, int x, int y, hipStream_t st, int *out8);
+int rast_frame_state_bytes(cg_ctx *c);
+}
+
+static bool rast_buffers_any(const cg_rast_buffers *b)
+{
+    return b && (b->argb || b->depth || b->shadow || b->screen || b->low || b->high || b->clip || b->tri || b->pos);
+}
+
+// The frame of cg_rast_draw_device (tris == nullptr) or cg_rast_render_device, told to leave
+// the owner's state words in every colour mode, then the buffers kernel.
+static int rast_buffers_frame(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *p, cg_vec4 light,
+                              const cg_rast_buffers *d, hipStream_t st, cg_stats *stats, int **n_out, int tex_mask)
+{
+    c->rast_want_owner = true;
+    c->rframe.valid = false;
+    const int rc = d_tris || n >= 0
+                       ? rast_render_device(c, d_tris, n, p, light, d->argb, d->depth, d->shadow, st, stats, tex_mask)
+                       : rast_draw_device(c, (const cg_rtri *)c->rroom.p, c->n_room, (const cg_rtri *)c->rboxes.p,
+                                          c->n_boxes, p, d->argb, d->depth, d->shadow, st, stats, n_out, tex_mask);
+    c->rast_want_owner = false;
+    if (rc) return rc;
+    return rast_buffers_device(c, d, n >= 0 ? -1 : c->n_room, st);
+}
+
+extern "C" int cg_rast_draw_buffers_device(cg_ctx *c, const cg_rast_params *p, const cg_rast_buffers *d, void *stream)
+{
+    if (!c || !p || !rast_buffers_any(d)) return CG_E_INVALID;
+    if (c->n_room < 0) {
+        c->err = "draw before cg_rast_set_scene";
+        return CG_E_NOSCENE;
+    }
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    return rast_buffers_frame(c, nullptr, -1, p, cg_vec4{0, 0, 0, 1}, d, stream ? (hipStream_t)stream : c->stream, nullptr,
+                              nullptr, c->scene_tex);
+}
+
+extern "C" int cg_rast_render_buffers_device(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *p,
+                                             cg_vec4 light, const cg_rast_buffers *d, void *stream)
+{
+    if (!c || !p || !rast_buffers_any(d) || n < 0 || (n && !d_tris)) return CG_E_INVALID;
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    // device lists are not inspected: textures run if any maps are loaded
+    return rast_buffers_frame(c, d_tris, n, p, light, d, stream ? (hipStream_t)stream : c->stream, nullptr, nullptr,
+                              c->tex_loaded);
+}
+
+// Host planes: device planes for those asked for, the frame, the downloads.  tris == nullptr
+// with n < 0: the context's scene (cg_rast_draw_buffers).
+static int rast_buffers_host(cg_ctx *c, const cg_rtri *tris, int n, const cg_rast_params *p, cg_vec4 light,
+                             const cg_rast_buffers *h, cg_stats *stats)
+{
+    auto t0 = std::chrono::steady_clock::now();
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    const size_t npx = (size_t)p->width * p->height;
+    hipError_t e;
+    cg_rast_buffers d = {};
+    struct Plane { void *host; void **dev; int slot; size_t bytes; };
+    const Plane planes[] = {
+        {h->argb, (void **)&d.argb, 4, npx * 4},          {h->depth, (void **)&d.depth, 5, npx * 4},
+        {h->shadow, (void **)&d.shadow, 6, npx * 4},      {h->screen, (void **)&d.screen, kBufScreen, npx * 12},
+        {h->low, (void **)&d.low, kBufLow, npx * 12},     {h->high, (void **)&d.high, kBufHigh, npx * 12},
+        {h->clip, (void **)&d.clip, kBufClipId, npx * 4}, {h->tri, (void **)&d.tri, kBufTriId, npx * 4},
+        {h->pos, (void **)&d.pos, kBufPos, npx * 16},
+    };
+    for (const Plane &pl : planes)
+        if (pl.host && !(*pl.dev = ctx_buf(c, pl.slot, pl.bytes, &e))) return ctx_fail(c, e, "alloc buffers plane");
+    cg_rtri *d_tris = nullptr;
+    if (n >= 0) {
+        d_tris = (cg_rtri *)ctx_buf(c, 0, (size_t)(n > 0 ? n : 1) * sizeof(cg_rtri), &e);
+        if (!d_tris) return ctx_fail(c, e, "alloc rast tris");
+        if (n) CG_TRY(c, hipMemcpyAsync(d_tris, tris, (size_t)n * sizeof(cg_rtri), hipMemcpyHostToDevice, c->stream), "upload tris");
+    }
+    int *d_n = nullptr;
+    const int rc = rast_buffers_frame(c, d_tris, n, p, light, &d, c->stream, stats, &d_n,
+                                      n >= 0 ? rast_tex_mask(tris, n) : c->scene_tex);
+    if (rc) return rc;
+    int nt = n;
+    if (n < 0) CG_TRY(c, hipMemcpyAsync(&nt, d_n, sizeof(int), hipMemcpyDeviceToHost, c->stream), "d2h count");
+    for (const Plane &pl : planes)
+        if (pl.host) CG_TRY(c, hipMemcpyAsync(pl.host, *pl.dev, pl.bytes, hipMemcpyDeviceToHost, c->stream), "d2h plane");
+    CG_TRY(c, hipStreamSynchronize(c->stream), "rast frame");
+    if (stats) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
+        stats->kernel_ms = ms;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->n_tris = nt;
+    }
+    return CG_OK;
+}
+
+extern "C" int cg_rast_draw_buffers(cg_ctx *c, const cg_rast_params *p, const cg_rast_buffers *h, cg_stats *stats)
+{
+    if (!c || !p || !rast_buffers_any(h) || p->width <= 2 || p->height <= 2) return CG_E_INVALID;
+    if (c->n_room < 0) {
+        c->err = "draw before cg_rast_set_scene";
+        return CG_E_NOSCENE;
+    }
+    return rast_buffers_host(c, nullptr, -1, p, cg_vec4{0, 0, 0, 1}, h, stats);
+}
+
+extern "C" int cg_rast_render_buffers(cg_ctx *c, const cg_rtri *tris, int n, const cg_rast_params *p, cg_vec4 light,
+                                      const cg_rast_buffers *h, cg_stats *stats)
+{
+    if (!c || !p || !rast_buffers_any(h) || n < 0 || (n && !tris) || p->width <= 2 || p->height <= 2 ||
+        p->height > kRastMaxH)
+        return CG_E_INVALID;
+    return rast_buffers_host(c, tris, n, p, light, h, stats);
+}
+
+extern "C" int cg_rast_pick(cg_ctx *c, const cg_rast_params *p, int x, int y, int32_t *tri, int32_t *clip, cg_vec4 *pos,
+                            int *hit)
+{
+    if (!c || !p || !hit) return CG_E_INVALID;
+    if (c->n_room < 0) {
+        c->err = "draw before cg_rast_set_scene";
+        return CG_E_NOSCENE;
+    }
+    if (x < 0 || y < 0 || x >= p->width || y >= p->height) return CG_E_INVALID;
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    // Setup, row records and the ordered z-buffer's fill, nothing else: no picture, no depth or
+    // shadow plane.  Colour modes 1-2 never look at textures (:604), so their owner is what the
+    // mode-0 walk over the untextured list decides, without a rand() stream.
+    cg_rast_params q = *p;
+    int tex = c->scene_tex;
+    if (q.colour_mode != 0) {
+        q.colour_mode = 0;
+        tex = 0;
+    }
+    const cg_rast_buffers none = {};
+    c->rast_want_owner = true;
+    c->rframe.valid = false;
+    const int rc = rast_draw_device(c, (const cg_rtri *)c->rroom.p, c->n_room, (const cg_rtri *)c->rboxes.p, c->n_boxes,
+                                    &q, none.argb, none.depth, none.shadow, c->stream, nullptr, nullptr, tex);
+    c->rast_want_owner = false;
+    if (rc) return rc;
+    int out[8] = {};
+    if (const int rc2 = rast_pick_device(c, c->n_room, x, y, c->stream, out)) return rc2;
+    *hit = out[0];
+    if (clip) *clip = out[1];
+    if (tri) *tri = out[2];
+    if (pos) std::memcpy(pos, out + 4, sizeof(cg_vec4));
+    return CG_OK;
+}
+
+extern "C" int cg_rast_state_bytes(cg_ctx *c) { return c ? rast_frame_state_bytes(c) : CG_E_INVALID; }
 
 // The latest frame's counts on the host (what cg_rast_scratch_info would read), so that they
 // outlive other frames run through the same scratch.

@@ -520,6 +520,51 @@ int cg_rast_draw(cg_ctx *ctx, const cg_rast_params *p, uint32_t *argb, float *de
 int cg_rast_draw_device(cg_ctx *ctx, const cg_rast_params *p, uint32_t *d_argb, float *d_depth,
                         int32_t *d_shadow, void *stream);
 
+/* The buffers Draw leaves behind besides the picture (skeleton.cpp:243-307), and what lies
+ * under each pixel.  screen / low / high: the float vec3 globals screenBuffer, lowLightBuffer,
+ * highLightBuffer as they stand when Draw returns -- `screen` with the post-pass darkening
+ * (:286-303, interior pixels, subtracted once); colour modes 1-2 leave low and high at 0 (the
+ * reference only clears them); a pixel no fragment wrote is 0, or -dk on `screen` where a
+ * shadow mark darkened the background.  The owner of a pixel is the fragment that last wrote
+ * screenBuffer[y][x] in drawing order (:574-661): a shadow-volume triangle never owns, and a
+ * fragment of texture 2/3 on a transparent texel sets the depth to 0 without owning (the
+ * earlier owner stays, so depth is not always the owner's zinv).  clip: the owner's index in
+ * the frame's clipped list (cg_rast_prepare's order); tri: its input triangle for the draw
+ * entries (room k -> k, boxes[k] -> n_room + k; the render entries' list is the clipped list:
+ * tri = clip); pos: the owner fragment's pos3d as Interpolate leaves it (:546-549),
+ * (X / zinv, Y / zinv, 1 / zinv, 1).  Without an owner clip = tri = CG_RAST_OWNER_NONE and
+ * pos = 0.  Every plane is W * H entries, row-major; any may be NULL, not all. */
+enum { CG_RAST_OWNER_NONE = -1 };
+typedef struct {
+    uint32_t *argb; float *depth; int32_t *shadow;   /* as cg_rast_draw's; each may be NULL */
+    float *screen, *low, *high;   /* 3 floats per pixel (x, y, z of the vec3), row-major, W*H*3 */
+    int32_t *clip;                /* owner: index in the frame's clipped list (cg_rast_prepare's order) */
+    int32_t *tri;                 /* owner: input triangle -- room k -> k, boxes[k] -> n_room + k */
+    cg_vec4 *pos;                 /* owner fragment's pos3d as Interpolate leaves it (:546-549) */
+} cg_rast_buffers;                /* at least one pointer non-NULL */
+/* A call runs the frame cg_rast_draw_device / cg_rast_render_device would run for the same
+ * parameters (route, colour modes, rand_offset, indirect_first, textures, what waits on which
+ * route, n_shaded, cg_rast_scratch_info afterwards; without argb the post-pass is skipped), then
+ * one more kernel on the same stream that fills the other planes from the frame's scratch.  In
+ * colour modes 1-2 the ordered z-buffer's fill runs once more for the owner.  kernel_ms in the
+ * stats covers the frame's own kernels.  CG_E_INVALID when every pointer is NULL. */
+int cg_rast_draw_buffers_device(cg_ctx *ctx, const cg_rast_params *p, const cg_rast_buffers *d, void *stream);
+int cg_rast_draw_buffers(cg_ctx *ctx, const cg_rast_params *p, const cg_rast_buffers *h, cg_stats *stats);
+int cg_rast_render_buffers_device(cg_ctx *ctx, const cg_rtri *d_tris, int n, const cg_rast_params *p, cg_vec4 light,
+                                  const cg_rast_buffers *d, void *stream);
+int cg_rast_render_buffers(cg_ctx *ctx, const cg_rtri *tris, int n, const cg_rast_params *p, cg_vec4 light,
+                           const cg_rast_buffers *h, cg_stats *stats);
+/* Synchronous: the tri / clip / pos the planes hold at (x, y) (each may be NULL), *hit = 0
+ * without an owner.  Runs the frame's passes through the fill into context scratch (no
+ * post-pass; a colour mode 1-2 pick draws nothing from the rand() stream) and gathers the one
+ * pixel: no output plane is allocated or written for it.  CG_E_INVALID for a pixel outside the
+ * frame, CG_E_NOSCENE before cg_rast_set_scene. */
+int cg_rast_pick(cg_ctx *ctx, const cg_rast_params *p, int x, int y, int32_t *tri, int32_t *clip, cg_vec4 *pos,
+                 int *hit);
+/* Host-only: the bytes of the state word the latest frame's ordered z-buffer left per pixel
+ * for the buffers kernel (2 below 32768 records a row, else 4; 0 before a frame). */
+int cg_rast_state_bytes(cg_ctx *ctx);
+
 /* Two routes render the same Draw, every plane bit for bit the same.  DENSE:
  * spans and row records sized at list capacity x H, the kernels of the
  * coursework scene.  COMPACT (large scenes): scratch and work follow what the
