@@ -56,7 +56,7 @@ class RtShard(C.Structure):
                 ("rows", C.c_int), ("col0", C.c_int), ("cols", C.c_int)]
 
 
-PIX_ARGB8888, PIX_RGB24 = 0, 1   # cg_render.h CG_PIX_*
+PIX_ARGB8888, PIX_RGB24, PIX_RGBA_F32 = 0, 1, 2   # cg_render.h CG_PIX_*
 
 
 class RTri(C.Structure):       # rasteriser Triangle, 84 B
@@ -169,6 +169,9 @@ _SIGS = {
                                              C.POINTER(RtShard), P, C.c_size_t, C.c_int, P]),
     "cg_rt_render_sequence_device": (C.c_int, [P, C.POINTER(Light), C.c_int, C.POINTER(RtCamera), C.c_int,
                                                C.POINTER(RtShard), P, C.c_size_t, C.c_int, P]),
+    "cg_pix_bytes": (C.c_int, [C.c_int]),
+    "cg_rt_render_radiance": (C.c_int, [P, C.POINTER(Light), C.c_int, C.POINTER(RtCamera), P, C.POINTER(Stats)]),
+    "cg_rt_pack_radiance_device": (C.c_int, [P, P, C.c_size_t, C.c_float, P, P]),
     "cg_rt_render_sequence": (C.c_int, [P, C.POINTER(Light), C.c_int, C.POINTER(RtCamera), C.c_int, P,
                                         C.c_size_t, C.c_int, C.POINTER(Stats)]),
     "cg_rt_sequence_runs": (C.c_int, [C.POINTER(RtCamera), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RtShard),
@@ -290,6 +293,14 @@ def yaw_matrix(yaw: float):
     m[0 * 4 + 0], m[0 * 4 + 2] = float(c), float(-s)
     m[2 * 4 + 0], m[2 * 4 + 2] = float(s), float(c)
     return (C.c_float * 16)(*m)
+
+
+def pix_bytes(pix_format):
+    """cg_pix_bytes: bytes per pixel of a PIX_* format (host-only; no GPU needed)."""
+    n = load().cg_pix_bytes(pix_format)
+    if n < 0:
+        raise ValueError(f"pix_format {pix_format}")
+    return n
 
 
 ROUTES = ("pixel", "lattice", "lattice_yaw", "lights", "lights_yaw", "big_pixel", "big_lattice", "big_lattice_yaw")
@@ -893,6 +904,22 @@ class Context:
         self._check(self.lib.cg_rt_render(self.h, lights, n_lights, C.byref(cam),
                                           out.ctypes.data_as(P), C.byref(st)), "cg_rt_render")
         return out, st
+
+    def rt_render_radiance(self, cam, lights=None):
+        """cg_rt_render_radiance: the frame before PutPixelSDL, float32[H, W, 4] -- x, y, z the
+        pixel's sum / 9, w the number of its nine sub-rays that hit (PIX_RGBA_F32)."""
+        lights = default_lights() if lights is None else lights
+        out = np.zeros((cam.height, cam.width, 4), np.float32)
+        st = Stats()
+        self._check(self.lib.cg_rt_render_radiance(self.h, lights, len(lights), C.byref(cam), out.ctypes.data_as(P),
+                                                   C.byref(st)), "cg_rt_render_radiance")
+        return out, st
+
+    def rt_pack_radiance_device(self, d_rgba, n_pixels, d_argb, scale=1.0, stream=None):
+        """cg_rt_pack_radiance_device: d_argb[p] = PutPixelSDL(scale * xyz of d_rgba[p])."""
+        self._check(self.lib.cg_rt_pack_radiance_device(self.h, P(d_rgba), n_pixels, scale, P(d_argb),
+                                                        P(stream) if stream else None),
+                    "cg_rt_pack_radiance_device")
 
     def rt_render_frames(self, cams, out=None, chunk=0, lights=None, frame_stride=0):
         """cg_rt_render_frames: len(cams) frames into host memory `out` at f * frame_stride pixels

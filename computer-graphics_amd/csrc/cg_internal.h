@@ -190,7 +190,8 @@ struct RtFrame {
     int n_tris, n_sph, n_lights;
     int rank, nranks, stripe_h, rows_out;
     int row0;      // first global row (band shards; 0 for stripes): v = row0 + stripe map of L
-    int out_fmt;   // CG_PIX_ARGB8888 (uint32 per pixel) or CG_PIX_RGB24 (3 bytes: B, G, R)
+    int out_fmt;   // CG_PIX_ARGB8888 (uint32 per pixel), CG_PIX_RGB24 (3 bytes: B, G, R) or
+                   // CG_PIX_RGBA_F32 (float4: sum / 9 and hit count; the host launches the *_f32 kernels)
     int wcol0, wcols;   // RGB24 output window: columns wcol0 .. wcol0 + wcols - 1 (wcols 0: all)
     int cull_primary, cull_shadow;   // certificates on (always, except inside the probes)
     const RtLight *lights;           // n_lights entries, device memory

@@ -880,99 +880,20 @@ constexpr int kRtMinWaves = CG_LAT_WAVES;
 // The pixel kernel (rotations other than a yaw; no bench configuration) at 5
 // waves per SIMD: 96 VGPRs and no scratch -- 6 spilled 52 B per lane for ~1 %.
 constexpr int kRtPixelWaves = 5;
-template <bool CULL>
-__global__ __launch_bounds__(kRtThreads, kRtPixelWaves) void rt_pixel_kernel(RtFrame F, const RtTri *__restrict__ tc,
-                                                              const RtShade *__restrict__ shade,
-                                                              const RtSphere *__restrict__ sph,
-                                                              uint32_t *__restrict__ out)
-{
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int u = blockIdx.x * kRtTileW + wave * 8 + (lane & 7);
-    const int L = blockIdx.y * kRtTileH + (lane >> 3);
-    const bool inside = u < F.W && L < F.rows_out;
-    const int v = inside ? shard_row(F, L) : 0;
-    const bool active = inside && v < F.H;
-    vec4 dir = v4((float)(u - F.W / 2), (float)(v - F.H / 2), F.focal, 1.0f);        // :126
-    dir = mat4_mul(F.R, dir);                                                         // :128
-    unsigned long long mask = ~0ull;
-    if (CULL) {
-        // exact float extremes of the wave's sub-ray directions (:137): newDir.x =
-        // fl(dir.x + 0.5 i) is monotone in dir.x, so the bundle lies in this box
-        float ax = active ? dir.x : __int_as_float(0x7fc00000), ay = active ? dir.y : __int_as_float(0x7fc00000);
-        float x0 = wave_min(active ? ax : FLT_MAX), x1 = wave_max(active ? ax : -FLT_MAX);
-        float y0 = wave_min(active ? ay : FLT_MAX), y1 = wave_max(active ? ay : -FLT_MAX);
-        x0 = x0 - 0.5f; x1 = x1 + 0.5f; y0 = y0 - 0.5f; y1 = y1 + 0.5f;
-        bool keep = true;
-        if (lane < F.n_tris && x0 <= x1 && y0 <= y1) keep = !cull_primary(tc[lane], x0, x1, y0, y1, F.focal);
-        mask = __ballot(keep && lane < F.n_tris);
-    }
-    // every lane stays to the end: the certificates' wave reductions read all 64
-    uint32_t px = 0u;
-    // Pass 1: the 9 primary rays (:134-140); hits staged in LDS (bi, t) so one
-    // shadow certificate covers the whole wave's hits and all lights at once.
-    __shared__ int s_bi[9][kRtThreads];
-    __shared__ float s_t[9][kRtThreads];
-    const float m = 0.5f;
-    if (active) {
-        // sub-ray k = 3 (i + 1) + (j + 1): d = (dir.x + m i, dir.y + m j, focal)  (:137),
-        // walked in three groups sharing d.y (closest_primary_group)
-        float dx[3], dy[3];
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            dx[q] = dir.x + (m * (float)(q - 1));
-            dy[q] = dir.y + (m * (float)(q - 1));
-        }
-#pragma unroll
-        for (int jj = 0; jj < 3; ++jj) {
-            int bi[3];
-            float t[3];
-            const float dyj[1] = {dy[jj]};
-            closest_primary_group<CULL, 3, 1>(F, tc, sph, dx, dyj, mask, bi, t);         // :140
-#pragma unroll
-            for (int ii = 0; ii < 3; ++ii) {
-                s_bi[3 * ii + jj][threadIdx.x] = bi[ii];
-                s_t[3 * ii + jj][threadIdx.x] = t[ii];
-            }
-        }
-    }
-    // one mask for every light of the set (the mask walk must stop at n_tris)
-    unsigned long long smask = F.n_tris >= 64 ? ~0ull : ((1ull << F.n_tris) - 1ull);
-    if (CULL && F.cull_shadow && F.n_lights > 0) {
-        LanePosBox pb;
-        pb.init();
-        if (active)
-            for (int k = 0; k < 9; ++k) {
-                const int bi = s_bi[k][threadIdx.x];
-                if (bi == INT_MIN) continue;
-                const float t = s_t[k][threadIdx.x];
-                const int i = k / 3 - 1, j = k % 3 - 1;
-                vec3 nd = v3(dir.x + (m * (float)i), dir.y + (m * (float)j), F.focal);
-                pb.add(v3(F.cam[0] + t * nd.x, F.cam[1] + t * nd.y, F.cam[2] + t * nd.z));   // :326/:345
-            }
-        smask = shadow_mask_box(F, tc, shadow_box_of_positions(F, pb), lane);
-    }
-    if (active) {
-        // Pass 2: shading in the reference's order (:143-157)
-        vec3 pc = v3(0.0f, 0.0f, 0.0f);
-        bool valid = false;
-        const vec3 ind = v3(F.indirect, F.indirect, F.indirect);
-        for (int k = 0; k < 9; ++k) {
-            const int i = k / 3 - 1, j = k % 3 - 1;
-            const int bi = s_bi[k][threadIdx.x];
-            if (bi == INT_MIN) continue;
-            const float t = s_t[k][threadIdx.x];
-            vec3 nd = v3(dir.x + (m * (float)i), dir.y + (m * (float)j), F.focal);
-            vec3 pos = v3(F.cam[0] + t * nd.x, F.cam[1] + t * nd.y, F.cam[2] + t * nd.z);  // :326/:345
-            valid = true;
-            vec3 oc = object_colour(shade, sph, bi);
-            for (int l = 0; l < F.n_lights; ++l)                                          // :151-153
-                pc = pc + direct_light<CULL>(F, tc, shade, sph, bi, pos, oc, l, smask);
-            pc = pc + (oc * ind);                                                         // :156
-        }
-        px = valid ? put_pixel(div_const(pc, 9.0f, 1.0f / 9.0f)) : put_pixel(v3(0.0f, 0.0f, 0.0f));             // :160-166
-    }
-    if (inside) out[(size_t)L * F.W + u] = px;
-}
+#define CG_RT_PIXEL_NAME rt_pixel_kernel
+#define CG_RT_PIXEL_F32 0
+#define CG_RT_PIXEL_OUT uint32_t
+#include "cg_rt_pixel_kernel.inc"
+#undef CG_RT_PIXEL_NAME
+#undef CG_RT_PIXEL_F32
+#undef CG_RT_PIXEL_OUT
+#define CG_RT_PIXEL_NAME rt_pixel_f32_kernel
+#define CG_RT_PIXEL_F32 1
+#define CG_RT_PIXEL_OUT float4
+#include "cg_rt_pixel_kernel.inc"
+#undef CG_RT_PIXEL_NAME
+#undef CG_RT_PIXEL_F32
+#undef CG_RT_PIXEL_OUT
 
 // ---------------------------------------------------------------------------
 // Lattice form of Draw (skeleton.cpp:104-169) for one light -- the C2
@@ -1171,16 +1092,27 @@ struct LatOut {
     uint8_t *out8;
     int pitch, wc0;
 };
+// F32 (the *_f32 kernels, CG_PIX_RGBA_F32): o.out is the frame's float4 pixels (lat_put_f32); the
+// format has no window, so pitch and wc0 below are the frame's.
+template <bool F32 = false>
 __device__ __forceinline__ LatOut lat_out(const RtFrame &F, int frame, size_t out_stride, uint32_t *out)
 {
     LatOut o;
     o.out8 = (uint8_t *)out + (size_t)frame * out_stride * 3;   // CG_PIX_RGB24
-    o.out = out + (size_t)frame * out_stride;
+    if constexpr (F32)
+        o.out = (uint32_t *)((float4 *)out + (size_t)frame * out_stride);
+    else
+        o.out = out + (size_t)frame * out_stride;
     // RGB24 window (a caller's contract: the columns outside are black);
     // windows are 16-pixel aligned
     o.pitch = (F.out_fmt == CG_PIX_RGB24 && F.wcols) ? F.wcols : F.W;
     o.wc0 = (F.out_fmt == CG_PIX_RGB24 && F.wcols) ? F.wcol0 : 0;
     return o;
+}
+// CG_PIX_RGBA_F32: pixel (row, col) of the frame lat_out<true> addressed, one 16-byte store
+__device__ __forceinline__ void lat_put_f32(const RtFrame &F, const LatOut &o, int row, int col, float4 v)
+{
+    ((float4 *)o.out)[(size_t)row * F.W + col] = v;
 }
 __device__ __forceinline__ void lat_store(const RtFrame &F, const LatTile &G, const LatOut &o, uint32_t px, int tx,
                                           int ty, uint32_t *s_px)
@@ -1309,10 +1241,16 @@ __device__ __forceinline__ void lat_closest_step(const RtFrame &Fp, const RtTri 
 
 // A tile no ray of which can hit anything (certified): every pixel is
 // PutPixelSDL(0, 0, 0) = 0x80000000 (:160-166).
+// (F32: no sub-ray hit, so radiance +0 and coverage 0: a zero float4.)
+template <bool F32 = false>
 __device__ __forceinline__ void lat_store_black(const RtFrame &F, const LatTile &G, const LatOut &o)
 {
     const int tx = threadIdx.x % kLatTileW, ty = threadIdx.x / kLatTileW;
     if (tx < G.nu && ty < G.nv) {
+        if constexpr (F32) {
+            lat_put_f32(F, o, G.L0 + ty, G.u0 + tx, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+            return;
+        }
         const uint32_t px = put_pixel(v3(0.0f, 0.0f, 0.0f));
         if (F.out_fmt == CG_PIX_ARGB8888) {
             o.out[(size_t)(G.L0 + ty) * F.W + G.u0 + tx] = px;
@@ -1325,13 +1263,49 @@ __device__ __forceinline__ void lat_store_black(const RtFrame &F, const LatTile 
     }
 }
 
+// CG_PIX_RGBA_F32: a shard's padding rows (output rows whose frame row is past the frame) are zero
+// bytes.  The tile row's output rows, and the tile's own columns of those past its nv pixel rows:
+__device__ __forceinline__ int lat_pad_rows(const RtFrame &F, const LatTile &G)
+{
+    return max(0, min(kLatTileH, F.rows_out - G.L0));
+}
+__device__ __forceinline__ void lat_zero_padding(const RtFrame &F, const LatTile &G, const LatOut &o)
+{
+    const int n = (lat_pad_rows(F, G) - G.nv) * G.nu;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int r = i / G.nu;
+        lat_put_f32(F, o, G.L0 + G.nv + r, G.u0 + (i - r * G.nu), make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    }
+}
+
 // A windowed launch (RtFrame::txn > 0): the first and last workgroup of each
 // tile row also store the output's columns left / right of the window black
 // -- no ray there can hit the scene's box (rt_box_columns), so those pixels
 // are PutPixelSDL(0, 0, 0) -- instead of a workgroup per black tile.
+// F32: a black pixel and a padding row's pixel are both zero bytes, so the edge workgroups store
+// the outside columns of all the tile row's output rows (lat_pad_rows), padding rows included.
+template <bool F32 = false>
 __device__ __forceinline__ void lat_store_outside(const RtFrame &F, const LatTile &G, const LatOut &o,
                                                   int bxw = -1)
 {
+    if constexpr (F32) {
+        if (F.txn <= 0) return;
+        if (bxw < 0) bxw = (int)blockIdx.x;
+        const bool left = bxw == 0, right = bxw == (int)gridDim.x - 1;
+        const int nr = lat_pad_rows(F, G);
+        for (int side = 0; side < 2; ++side) {
+            if (!(side ? right : left)) continue;
+            const int c0 = side ? max(0, (F.tx0 + F.txn) * kLatTileW) : 0;
+            const int c1 = side ? F.W : min(F.W, F.tx0 * kLatTileW);
+            const int w = c1 - c0;
+            if (w <= 0) continue;
+            for (int i = threadIdx.x; i < w * nr; i += blockDim.x) {
+                const int r = i / w;
+                lat_put_f32(F, o, G.L0 + r, c0 + (i - r * w), make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+            }
+        }
+        return;
+    }
     if (F.txn <= 0 || G.nv <= 0) return;
     if (bxw < 0) bxw = (int)blockIdx.x;   // the workgroup's column within the launch's window
     const bool left = bxw == 0, right = bxw == (int)gridDim.x - 1;
@@ -1459,7 +1433,9 @@ __device__ __forceinline__ void lat_flatten(const LatFlatten &Z)
 // out + frame * out_stride.
 // PITCH: the LDS row pitch of the lattice, kLatW (shared columns) or kLatWY
 // (per-pixel columns; rt_lattice_ok).
-template <int PITCH, class FT>
+// F32: the *_f32 kernels' compile-time output policy (CG_PIX_RGBA_F32) -- every store of the tile
+// is a float4 (sum / 9, hit count) instead of put_pixel's word; nothing else differs.
+template <int PITCH, bool F32 = false, class FT>
 __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__restrict__ tc,
                                              const RtShade *__restrict__ shade, const RtSphere *__restrict__ sph,
                                              const unsigned long long *__restrict__ lat_masks, const FT &cams,
@@ -1475,13 +1451,14 @@ __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__r
     tc += (size_t)frame * F.n_tris;
     lat_masks += (size_t)frame * lat_tiles_x(F) * gridDim.y * 2;
     if (obj_masks) obj_masks += (size_t)frame * lat_tiles_x(F) * gridDim.y * kObjSlots;
-    const LatOut o = lat_out(F, frame, out_stride, out);
+    const LatOut o = lat_out<F32>(F, frame, out_stride, out);
     // (wave as a uniform SGPR value -- readfirstlane -- measured 5 % slower here: 0.913 -> 0.960 ms
     // per 20-frame launch, more VGPRs and SGPRs; the yawed form 0.7 % faster; profiles/r05_ab_walk.json)
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int by = S.by, bx = F.tx0 + S.bx;
     const LatTile G = lat_tile<true, PITCH != kLatW>(F, bx, by);   // yaw: the launch's choice (lat_yaw), a constant here
-    lat_store_outside(F, G, o, S.bx);
+    lat_store_outside<F32>(F, G, o, S.bx);
+    if constexpr (F32) lat_zero_padding(F, G, o);
     const int rows = G.rows;
     // per lattice point: .w = the hit object's table slot (enc; the zero slot: no hit);
     // .xyz = DirectLight (one ds_read_b128 per sample).
@@ -1561,7 +1538,7 @@ __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__r
     const unsigned long long m0 = certified ? uniform_u64(lat_masks[2 * tix]) : all;
     const unsigned long long s0 = certified ? uniform_u64(lat_masks[2 * tix + 1]) : all;
     if (m0 == 0ull) {                      // before anything else is loaded or computed
-        lat_store_black(F, G, o);
+        lat_store_black<F32>(F, G, o);
         return;                            // the whole workgroup (m0 is uniform), ahead of its one barrier
     }
     const unsigned long long mask = m0 & ~(3ull << 62), smask = s0 & ~(1ull << 63);
@@ -1677,6 +1654,7 @@ __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__r
         typedef float f2 __attribute__((ext_vector_type(2)));
         f2 pxy = {0.0f, 0.0f};
         float pz = 0.0f;
+        [[maybe_unused]] int nhit = 0;   // F32: the pixel's points whose slot is not the miss slot
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
             const int i = k / 3 - 1, j = k % 3 - 1;
@@ -1693,15 +1671,21 @@ __device__ __forceinline__ void lattice_body(const RtFrame &F0, const RtTri *__r
                 dl = v3(q.x, q.y, q.z);
             }
             const vec3 am = Tab::at(s_tab.amb, enc);
+            if constexpr (F32) nhit += enc != kNoHit;
             pxy = pxy + f2{dl.x, dl.y};                                                   // :151-153
             pz = pz + dl.z;
             pxy = pxy + f2{am.x, am.y};                                                   // :156
             pz = pz + am.z;
         }
         const vec3 pc = v3(pxy.x, pxy.y, pz);
-        px = put_pixel(div_const(pc, 9.0f, 1.0f / 9.0f));                                 // :160-166
+        if constexpr (F32) {
+            const vec3 q = div_const(pc, 9.0f, 1.0f / 9.0f);                              // :160-163
+            lat_put_f32(F, o, G.L0 + ty, G.u0 + tx, make_float4(q.x, q.y, q.z, (float)nhit));
+        } else {
+            px = put_pixel(div_const(pc, 9.0f, 1.0f / 9.0f));                             // :160-166
+        }
     }
-    lat_store(F, G, o, px, tx, ty, s_tab.px);
+    if constexpr (!F32) lat_store(F, G, o, px, tx, ty, s_tab.px);
 }
 
 // ---------------------------------------------------------------------------
@@ -1779,7 +1763,7 @@ struct LatLightsTile {
     size_t tix;
     int nhalf;
 };
-template <int PITCH, class FT>
+template <int PITCH, bool F32 = false, class FT>
 __device__ __forceinline__ bool lat_lights_tile(const RtFrame &F0, const RtTri *__restrict__ &tc,
                                                 const RtShade *__restrict__ shade, const RtSphere *__restrict__ sph,
                                                 const unsigned long long *__restrict__ lat_masks,
@@ -1796,13 +1780,14 @@ __device__ __forceinline__ bool lat_lights_tile(const RtFrame &F0, const RtTri *
     frame_install(cams, frame, F);
     tc += (size_t)frame * F.n_tris;
     lat_masks += (size_t)frame * lat_tiles_x(F) * gridDim.y * 2;
-    T.o = lat_out(F, frame, out_stride, out);
+    T.o = lat_out<F32>(F, frame, out_stride, out);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int by = lat_tile_row(), bx = lat_tile_col(F);
     LatTile &G = T.G;
     G = lat_tile(F, bx, by);
     G.yaw = PITCH != kLatW;   // the launch's choice (lat_yaw), a constant here
-    if (store_black) lat_store_outside(F, G, T.o);
+    if (store_black) lat_store_outside<F32>(F, G, T.o);
+    if constexpr (F32) lat_zero_padding(F, G, T.o);
     lat_load_objs(s_obj, shade, sph, F.n_tris, F.n_sph);
     const int npts = PITCH * G.rows;
     const int q = (npts + 3) / 4, p_lo = min(npts, wave * q), p_hi = min(npts, p_lo + q);
@@ -1819,7 +1804,7 @@ __device__ __forceinline__ bool lat_lights_tile(const RtFrame &F0, const RtTri *
     if (!(s0 >> 63)) T.Fs.n_sph = 0;
     T.nhalf = (G.nv + kLatHalfH - 1) / kLatHalfH;
     if (m0 == 0ull) {
-        if (store_black) lat_store_black(F, G, T.o);
+        if (store_black) lat_store_black<F32>(F, G, T.o);
         return false;
     }
     __syncthreads();                       // s_obj
@@ -1988,7 +1973,9 @@ __device__ __forceinline__ void lattice_units_body(const RtFrame &F0, const RtTr
     }
 }
 
-template <int PITCH, class FT>
+// F32 (CG_PIX_RGBA_F32, the *_f32 kernels): s_valid counts the pixel's hit points instead of
+// flagging them, and a part's pixels go to the frame as float4 when the part is resolved.
+template <int PITCH, bool F32 = false, class FT>
 __device__ __forceinline__ void lattice_lights_body(const RtFrame &F0, const RtTri *__restrict__ tc,
                                                     const RtShade *__restrict__ shade,
                                                     const RtSphere *__restrict__ sph,
@@ -2013,7 +2000,8 @@ __device__ __forceinline__ void lattice_lights_body(const RtFrame &F0, const RtT
     __shared__ unsigned long long s_umask[kLatParts][PITCH];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     LatLightsTile T;
-    if (!lat_lights_tile<PITCH>(F0, tc, shade, sph, lat_masks, cams, out_stride, out, true, s_t, s_bi, s_obj, T)) return;
+    if (!lat_lights_tile<PITCH, F32>(F0, tc, shade, sph, lat_masks, cams, out_stride, out, true, s_t, s_bi, s_obj, T))
+        return;
     const RtFrame &F = T.F, &Fs = T.Fs;
     const LatTile &G = T.G;
     const int ay0 = G.ay0, cols = G.cols;
@@ -2104,12 +2092,14 @@ __device__ __forceinline__ void lattice_lights_body(const RtFrame &F0, const RtT
                     const int ty = fpr;   // row of the part
                     float pc = s_pc[ty][tx][fcomp];
                     bool valid = false;
+                    [[maybe_unused]] int nhit = 0;
                     const float *buf = &s_dl[cx & 1][0][0][0];
                     for (int j = 0; j < 3; ++j) {
                         const int r = 2 * fpr + j;
                         const int bi = s_bi[(lr0 + r) * PITCH + cx];
                         if (bi == kLatNoHit) continue;
                         valid = true;
+                        if constexpr (F32) ++nhit;
                         const float *b = buf + (r * 3 + fcomp) * kLatMaxLights;
                         const int sw = lat_swz(r, fcomp);
                         int l = 0;
@@ -2126,7 +2116,11 @@ __device__ __forceinline__ void lattice_lights_body(const RtFrame &F0, const RtT
                         pc = pc + (a * ind);                                      // :156
                     }
                     s_pc[ty][tx][fcomp] = pc;
-                    if (valid && fcomp == 0) s_valid[ty][tx] = 1;
+                    if constexpr (F32) {   // this column's hits of the pixel (its three columns: at most 9)
+                        if (fcomp == 0) s_valid[ty][tx] = (uint8_t)(s_valid[ty][tx] + nhit);
+                    } else {
+                        if (valid && fcomp == 0) s_valid[ty][tx] = 1;
+                    }
                 }
             }
             __syncthreads();
@@ -2137,8 +2131,14 @@ __device__ __forceinline__ void lattice_lights_body(const RtFrame &F0, const RtT
         if (ty < kLatHalfH) {
             if (ty < npr) {
                 const vec3 pc = v3(s_pc[ty][tx][0], s_pc[ty][tx][1], s_pc[ty][tx][2]);
-                s_px[(pr0 + ty) * kLatTileW + tx] =
-                    s_valid[ty][tx] ? put_pixel(div_const(pc, 9.0f, 1.0f / 9.0f)) : put_pixel(v3(0.0f, 0.0f, 0.0f));
+                if constexpr (F32) {
+                    const vec3 q = s_valid[ty][tx] ? div_const(pc, 9.0f, 1.0f / 9.0f) : v3(0.0f, 0.0f, 0.0f);
+                    if (tx < G.nu)
+                        lat_put_f32(F, T.o, G.L0 + pr0 + ty, G.u0 + tx, make_float4(q.x, q.y, q.z, (float)s_valid[ty][tx]));
+                } else {
+                    s_px[(pr0 + ty) * kLatTileW + tx] =
+                        s_valid[ty][tx] ? put_pixel(div_const(pc, 9.0f, 1.0f / 9.0f)) : put_pixel(v3(0.0f, 0.0f, 0.0f));
+                }
             }
             s_pc[ty][tx][0] = s_pc[ty][tx][1] = s_pc[ty][tx][2] = 0.0f;
             s_valid[ty][tx] = 0;
@@ -2148,6 +2148,7 @@ __device__ __forceinline__ void lattice_lights_body(const RtFrame &F0, const RtT
     if (threadIdx.x == 0 && blockIdx.z == 0 && blockIdx.x % 24 == 0 && blockIdx.y % 24 == 0)
         printf("LIGHTS bx %d by %d units %d cand %d sph %d\n", blockIdx.x, blockIdx.y, st_units, st_cand, st_sph);
 #endif
+    if constexpr (F32) return;   // stored part by part above
     __syncthreads();
     const int tx = threadIdx.x % kLatTileW, ty = threadIdx.x / kLatTileW;
     const uint32_t px = (tx < G.nu && ty < G.nv) ? s_px[ty * kLatTileW + tx] : 0u;
@@ -2255,6 +2256,65 @@ __global__ __launch_bounds__(kRtThreads, 6) void rt_lattice_lights_seq_kernel(
 {
     lattice_lights_body<PITCH>(F0, tc, shade, sph, lat_masks, umask, cams, out_stride, out);
     lat_signal(frame_done, blockIdx.z);
+}
+
+// CG_PIX_RGBA_F32: the same bodies with the float output policy, as kernels of their own names
+// (the ARGB / RGB24 kernels above keep their machine code; codeobj.kernel_sha256 is per name).
+// `out` holds float4 pixels, frame f at out + f * out_stride.
+template <int PITCH>
+__global__ __launch_bounds__(kRtThreads, kRtMinWaves) void rt_lattice_f32_kernel(
+    RtFrame F0, const RtTri *__restrict__ tc, const RtShade *__restrict__ shade, const RtSphere *__restrict__ sph,
+    const unsigned long long *__restrict__ lat_masks, RtFrameCams cams, size_t out_stride, float4 *__restrict__ out,
+    uint32_t *frame_done, LatOrder O, LatReady R, const unsigned long long *__restrict__ obj_masks)
+{
+    const unsigned long long t_start = wall_clock64();
+    const LatSlot S = lat_slot_of(O);
+    lattice_body<PITCH, true>(F0, tc, shade, sph, lat_masks, cams, out_stride, (uint32_t *)out, S, R, obj_masks);
+    if (O.cost && S.frame == 0 && threadIdx.x == 0)
+        O.cost[S.by * (int)gridDim.x + S.bx] = (uint8_t)lat_cost_class(wall_clock64() - t_start);
+    lat_signal(frame_done, S.frame);
+}
+template <int PITCH>
+__global__ __launch_bounds__(kRtThreads, kRtMinWaves) void rt_lattice_f32_seq_kernel(
+    RtFrame F0, const RtTri *__restrict__ tc, const RtShade *__restrict__ shade, const RtSphere *__restrict__ sph,
+    const unsigned long long *__restrict__ lat_masks, RtFrameSeq cams, size_t out_stride, float4 *__restrict__ out,
+    uint32_t *frame_done, LatOrder O, const unsigned long long *__restrict__ obj_masks)
+{
+    const unsigned long long t_start = wall_clock64();
+    const LatSlot S = lat_slot_of(O);
+    lattice_body<PITCH, true>(F0, tc, shade, sph, lat_masks, cams, out_stride, (uint32_t *)out, S, LatReady{}, obj_masks);
+    if (O.cost && S.frame == 0 && threadIdx.x == 0)
+        O.cost[S.by * (int)gridDim.x + S.bx] = (uint8_t)lat_cost_class(wall_clock64() - t_start);
+    lat_signal(frame_done, S.frame);
+}
+template <int PITCH>
+__global__ __launch_bounds__(kRtThreads, 6) void rt_lattice_lights_f32_kernel(
+    RtFrame F0, const RtTri *__restrict__ tc, const RtShade *__restrict__ shade, const RtSphere *__restrict__ sph,
+    const unsigned long long *__restrict__ lat_masks, const unsigned long long *__restrict__ umask, RtFrameCams cams,
+    size_t out_stride, float4 *__restrict__ out, uint32_t *frame_done)
+{
+    lattice_lights_body<PITCH, true>(F0, tc, shade, sph, lat_masks, umask, cams, out_stride, (uint32_t *)out);
+    lat_signal(frame_done, blockIdx.z);
+}
+template <int PITCH>
+__global__ __launch_bounds__(kRtThreads, 6) void rt_lattice_lights_f32_seq_kernel(
+    RtFrame F0, const RtTri *__restrict__ tc, const RtShade *__restrict__ shade, const RtSphere *__restrict__ sph,
+    const unsigned long long *__restrict__ lat_masks, const unsigned long long *__restrict__ umask, RtFrameSeq cams,
+    size_t out_stride, float4 *__restrict__ out, uint32_t *frame_done)
+{
+    lattice_lights_body<PITCH, true>(F0, tc, shade, sph, lat_masks, umask, cams, out_stride, (uint32_t *)out);
+    lat_signal(frame_done, blockIdx.z);
+}
+
+// CG_PIX_RGBA_F32 -> ARGB8888 (cg_rt_pack_radiance_device): PutPixelSDL of scale * (x, y, z), one
+// pixel a lane -- 16 bytes in, 4 out.  scale 1: x * 1.0f is x, so the kernels' own ARGB word.
+__global__ __launch_bounds__(256) void rt_pack_radiance_kernel(const float4 *__restrict__ src, size_t n, float scale,
+                                                               uint32_t *__restrict__ dst)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 p = src[i];
+    dst[i] = put_pixel(v3(p.x * scale, p.y * scale, p.z * scale));
 }
 
 // ARGB8888 -> RGB24 wire format (kernels without a fused RGB24 store): rows
@@ -2659,6 +2719,37 @@ hipError_t launch_rt_lattice_frames(const RtFrame &F, const RtTri *d_tc, const R
     if (F.n_lights > 1 && !d_umask) return hipErrorInvalidValue;
     if (F.txn && (F.tx0 < 0 || F.tx0 + F.txn > lat_tiles_x(F))) return hipErrorInvalidValue;
     const int kt_id = F.n_lights == 1 ? KT_RT_LATTICE : KT_RT_LATTICE_LIGHTS;
+    if (F.out_fmt == CG_PIX_RGBA_F32) {   // the float kernels: the same launches, float4 pixels
+        if (F.wcols) return hipErrorInvalidValue;
+        float4 *d_rad = (float4 *)d_out;
+        const RtFrameSeq seq{recs};
+        if (recs && R.flags) return hipErrorInvalidValue;
+        if (recs && F.n_lights == 1 && lat_yaw(F))
+            kt_launch(kt_id, rt_lattice_f32_seq_kernel<kLatWY>, grid, dim3(kRtThreads), 0, st, F, d_tc, d_shade, d_sph,
+                      d_lat_masks, seq, out_stride, d_rad, d_done, O, d_obj_masks);
+        else if (recs && F.n_lights == 1)
+            kt_launch(kt_id, rt_lattice_f32_seq_kernel<kLatW>, grid, dim3(kRtThreads), 0, st, F, d_tc, d_shade, d_sph,
+                      d_lat_masks, seq, out_stride, d_rad, d_done, O, d_obj_masks);
+        else if (recs && lat_yaw(F))
+            kt_launch(kt_id, rt_lattice_lights_f32_seq_kernel<kLatWY>, grid, dim3(kRtThreads), 0, st, F, d_tc, d_shade,
+                      d_sph, d_lat_masks, d_umask, seq, out_stride, d_rad, d_done);
+        else if (recs)
+            kt_launch(kt_id, rt_lattice_lights_f32_seq_kernel<kLatW>, grid, dim3(kRtThreads), 0, st, F, d_tc, d_shade,
+                      d_sph, d_lat_masks, d_umask, seq, out_stride, d_rad, d_done);
+        else if (F.n_lights == 1 && lat_yaw(F))
+            kt_launch(kt_id, rt_lattice_f32_kernel<kLatWY>, grid, dim3(kRtThreads), 0, st, F, d_tc, d_shade, d_sph,
+                      d_lat_masks, cams, out_stride, d_rad, d_done, O, R, d_obj_masks);
+        else if (F.n_lights == 1)
+            kt_launch(kt_id, rt_lattice_f32_kernel<kLatW>, grid, dim3(kRtThreads), 0, st, F, d_tc, d_shade, d_sph,
+                      d_lat_masks, cams, out_stride, d_rad, d_done, O, R, d_obj_masks);
+        else if (lat_yaw(F))
+            kt_launch(kt_id, rt_lattice_lights_f32_kernel<kLatWY>, grid, dim3(kRtThreads), 0, st, F, d_tc, d_shade, d_sph,
+                      d_lat_masks, d_umask, cams, out_stride, d_rad, d_done);
+        else
+            kt_launch(kt_id, rt_lattice_lights_f32_kernel<kLatW>, grid, dim3(kRtThreads), 0, st, F, d_tc, d_shade, d_sph,
+                      d_lat_masks, d_umask, cams, out_stride, d_rad, d_done);
+        return hipGetLastError();
+    }
     if (recs) {   // frame sequences: per-frame records, certificates first
         const RtFrameSeq seq{recs};
         if (R.flags) return hipErrorInvalidValue;
@@ -2706,6 +2797,13 @@ hipError_t launch_rt_pixels(const RtFrame &F, const RtTri *d_tc, const RtShade *
                                         nullptr, nullptr, nullptr, d_obj_masks, nullptr);
     }
     const int kt_id = KT_RT_PIXEL;
+    if (F.out_fmt == CG_PIX_RGBA_F32) {
+        // (frames always come with the certificates on: the uncertified form has no float variant)
+        if (!(F.n_tris <= 64 && F.cull_primary)) return hipErrorInvalidValue;
+        kt_launch(kt_id, rt_pixel_f32_kernel<true>, grid, dim3(kRtThreads), 0, st, F, d_tc, d_shade, d_sph,
+                  (float4 *)d_out);
+        return hipGetLastError();
+    }
     if (F.n_tris <= 64 && F.cull_primary)
         kt_launch(kt_id, rt_pixel_kernel<true>, grid, dim3(kRtThreads), 0, st, F, d_tc, d_shade,
                            d_sph, d_out);
@@ -2721,6 +2819,14 @@ hipError_t launch_rt_pack_rgb24(const uint32_t *d_src, int W, int rows, int wcol
     if (rows <= 0 || wcols <= 0) return hipSuccess;
     hipLaunchKernelGGL(rt_pack_rgb24_kernel, dim3(((wcols + 3) / 4 + 255) / 256, rows), dim3(256), 0, st, d_src, W,
                        rows, wcol0, wcols, d_dst);
+    return hipGetLastError();
+}
+
+hipError_t launch_rt_pack_radiance(const float *d_rgba, size_t n, float scale, uint32_t *d_argb, hipStream_t st)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(rt_pack_radiance_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                       (const float4 *)d_rgba, n, scale, d_argb);
     return hipGetLastError();
 }
 

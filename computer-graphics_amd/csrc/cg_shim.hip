@@ -65,6 +65,7 @@ bool rt_grid_build(const cg_tri *, int, RtGrid &, std::vector<int> &, std::vecto
 size_t rt_big_scratch_bytes(const RtFrame &, const BigCaps &, bool hits = false);
 hipError_t launch_rt_unstripe(const uint32_t *, int, int, int, int, int, int, uint32_t *, hipStream_t);
 hipError_t launch_rt_pack_rgb24(const uint32_t *, int, int, int, int, uint8_t *, hipStream_t);
+hipError_t launch_rt_pack_radiance(const float *, size_t, float, uint32_t *, hipStream_t);
 hipError_t launch_rt_assemble(const uint8_t *, const RtBlocks &, int, uint32_t *, size_t, hipStream_t);
 hipError_t launch_rt_probe_closest(const RtFrame &, const cg_tri *, const RtSphere *,
                                    const cg_vec4 *, const cg_vec4 *, int, cg_isect *, int *,
@@ -1746,7 +1747,15 @@ static int big_slots()
     return n;
 }
 
-static size_t pix_bytes(int fmt) { return fmt == CG_PIX_RGB24 ? 3 : 4; }
+extern "C" int cg_pix_bytes(int pix_format)
+{
+    switch (pix_format) {
+    case CG_PIX_ARGB8888: return 4;
+    case CG_PIX_RGB24: return 3;
+    case CG_PIX_RGBA_F32: return 16;
+    default: return CG_E_INVALID;
+    }
+}
 
 namespace cg {
 int rt_render_frames(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams, int n_frames,
@@ -1934,7 +1943,8 @@ int rt_render_frames(cg_ctx *c, const cg_light *lights, int n_lights, const cg_r
                      uint32_t *d_done, uint32_t *target, const int *group_starts, int ngroups, int light_stride)
 {
     if (!c || !d_out || n_frames < 0 || (n_frames && !cams)) return CG_E_INVALID;
-    if (pix_format != CG_PIX_ARGB8888 && pix_format != CG_PIX_RGB24) return CG_E_INVALID;
+    if (cg_pix_bytes(pix_format) < 0) return CG_E_INVALID;
+    if (pix_format == CG_PIX_RGBA_F32 && ((uintptr_t)d_out & 15)) return CG_E_INVALID;
     if (n_frames == 0) return CG_OK;
     for (int f = 1; f < n_frames; ++f)
         if (cams[f].width != cams[0].width || cams[f].height != cams[0].height) return CG_E_INVALID;
@@ -1948,7 +1958,7 @@ int rt_render_frames(cg_ctx *c, const cg_light *lights, int n_lights, const cg_r
     const size_t stride = frame_stride ? frame_stride : px;   // pixels
     if (stride < px) return CG_E_INVALID;
     uint8_t *out = (uint8_t *)d_out;
-    const size_t fbytes = stride * pix_bytes(pix_format);
+    const size_t fbytes = stride * (size_t)cg_pix_bytes(pix_format);
     // light_stride != 0: frame f has its own lights, lights[f * n_lights ..] (cg_rt_render_sequence_device)
     if (light_stride) return rt_enqueue_sequence(c, F, lights, n_lights, cams, n_frames, shard, out, stride, fbytes,
                                                  pix_format, st);
@@ -2012,7 +2022,7 @@ extern "C" int cg_rt_assemble_device(cg_ctx *c, const void *d_src, int pix_forma
     B.n = n_blocks;
     B.W = width;
     B.H = height;
-    B.bpp = (int)pix_bytes(pix_format);
+    B.bpp = cg_pix_bytes(pix_format);
     B.wcol0 = col0;
     B.wcols = cols;
     B.cum[0] = 0;
@@ -2026,6 +2036,50 @@ extern "C" int cg_rt_assemble_device(cg_ctx *c, const void *d_src, int pix_forma
     CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
     CG_TRY(c, launch_rt_assemble((const uint8_t *)d_src, B, n_frames, d_frames, frame_stride,
                                  stream ? (hipStream_t)stream : c->stream), "assemble launch");
+    return CG_OK;
+}
+
+extern "C" int cg_rt_pack_radiance_device(cg_ctx *c, const float *d_rgba, size_t n_pixels, float scale,
+                                          uint32_t *d_argb, void *stream)
+{
+    if (!c || (n_pixels && (!d_rgba || !d_argb)) || ((uintptr_t)d_rgba & 15) || n_pixels > ((size_t)1 << 39))
+        return CG_E_INVALID;
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    CG_TRY(c, launch_rt_pack_radiance(d_rgba, n_pixels, scale, d_argb, stream ? (hipStream_t)stream : c->stream),
+           "pack radiance launch");
+    return CG_OK;
+}
+
+// Host-memory form of a CG_PIX_RGBA_F32 frame: one frame call into the context's scratch frame,
+// then a download.
+extern "C" int cg_rt_render_radiance(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cam,
+                                     float *rgba, cg_stats *stats)
+{
+    if (!c || !rgba || !cam || cam->width <= 0 || cam->height <= 0) return CG_E_INVALID;
+    if (c->n_tris < 0) {
+        c->err = "render before cg_rt_set_scene";
+        return CG_E_NOSCENE;
+    }
+    auto t0 = std::chrono::steady_clock::now();
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    const size_t bytes = (size_t)cam->width * cam->height * 16;
+    CG_TRY(c, c->frame.ensure(bytes), "alloc frame");
+    CG_TRY(c, hipEventRecord(c->ev0, c->stream), "event");
+    cg_rt_shard whole{0, 1, cam->height, 0, cam->height, 0, 0};   // a band of exactly the frame's rows
+    if (int rc = cg_rt_render_frames_device(c, lights, n_lights, cam, 1, &whole, c->frame.p, 0, CG_PIX_RGBA_F32,
+                                            c->stream))
+        return rc;
+    CG_TRY(c, hipEventRecord(c->ev1, c->stream), "event");
+    CG_TRY(c, hipMemcpyAsync(rgba, c->frame.p, bytes, hipMemcpyDeviceToHost, c->stream), "download frame");
+    CG_TRY(c, hipStreamSynchronize(c->stream), "rt frame");
+    if (stats) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
+        stats->kernel_ms = ms;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->n_tris = c->n_tris;
+        stats->n_spans = 0;
+    }
     return CG_OK;
 }
 

@@ -8,14 +8,18 @@
 // arrows, n m = yaw, i o = focal, x = ESC).  The per-pixel loop runs on the
 // GPU through the C-ABI (include/cg_render.h).
 //
-//   raytracer [--width W] [--height H] [--focal F] [--keys KEYS] [--out FILE] [--batch]
+//   raytracer [--width W] [--height H] [--focal F] [--keys KEYS] [--out FILE] [--batch] [--pfm FILE]
 //
 // --batch: Update() runs over the whole key script first, each frame's globals
 // are recorded, and one cg_rt_render_sequence call renders every frame; the
 // screenshot is the last frame, as without the flag.
+// --pfm FILE: the last frame's pixelColour / 9.0f before PutPixelSDL clamps it
+// (cg_rt_render_radiance), as a little-endian colour PFM: "PF", the size, "-1.0",
+// then rows bottom-up of three floats a pixel.
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <fstream>
 #include <string>
 #include <vector>
 
@@ -105,6 +109,30 @@ void Draw(screen *screen)
     if (rc) die(rc, "cg_rt_render");
 }
 
+// --pfm: the frame Draw would render from the current globals, unclamped
+static void SaveRadiancePFM(const screen *screen, const char *path)
+{
+    UploadScene();
+    const cg_rt_camera cam = CurrentCamera(screen);
+    const size_t px = (size_t)cam.width * cam.height;
+    vector<float> rgba(px * 4);
+    int rc = cg_rt_render_radiance(g_ctx, reinterpret_cast<const cg_light *>(lights.data()), (int)lights.size(), &cam,
+                                   rgba.data(), nullptr);
+    if (rc) die(rc, "cg_rt_render_radiance");
+    ofstream f(path, ios::binary);
+    f << "PF\n" << cam.width << " " << cam.height << "\n-1.0\n";
+    vector<float> row((size_t)cam.width * 3);
+    for (int y = cam.height - 1; y >= 0; --y) {   // bottom row first
+        for (int x = 0; x < cam.width; ++x)
+            memcpy(&row[3 * x], &rgba[((size_t)y * cam.width + x) * 4], 3 * sizeof(float));
+        f.write(reinterpret_cast<const char *>(row.data()), row.size() * sizeof(float));
+    }
+    if (!f) {
+        cerr << "cannot write " << path << endl;
+        exit(1);
+    }
+}
+
 // skeleton.cpp:172-260 with scripted keys
 bool Update()
 {
@@ -144,7 +172,7 @@ bool Update()
 
 int main(int argc, char *argv[])
 {
-    string out = "screenshot.bmp";
+    string out = "screenshot.bmp", pfm;
     bool batch = false;
     for (int i = 1; i < argc; i += 2) {
         string a = argv[i];
@@ -159,6 +187,7 @@ int main(int argc, char *argv[])
         else if (a == "--focal") focalLength = (float)atof(argv[i + 1]);
         else if (a == "--keys") g_keys = argv[i + 1];
         else if (a == "--out") out = argv[i + 1];
+        else if (a == "--pfm") pfm = argv[i + 1];
     }
     int rc = cg_create(0, &g_ctx);
     if (rc) die(rc, "cg_create");
@@ -167,6 +196,7 @@ int main(int argc, char *argv[])
     light1.position = vec4(0, -0.5, -0.7, 1.0);
     light1.colour = 14.f * vec3(1, 1, 1);
     lights.push_back(light1);
+    size_t drawn = 0;
     if (batch) {
         // the main loop's frames in one call: each Update()'s globals recorded, then every Draw()
         vector<cg_rt_camera> cams;
@@ -185,13 +215,17 @@ int main(int argc, char *argv[])
             memcpy(screen->buffer, frames.data() + (cams.size() - 1) * px, px * sizeof(uint32_t));
             SDL_Renderframe(screen);
         }
+        drawn = cams.size();
     } else {
         while (Update()) {
             Draw(screen);
             SDL_Renderframe(screen);
+            ++drawn;
         }
     }
     SDL_SaveImage(screen, out.c_str());
+    // Update() changes nothing on the turn it ends the loop: the globals are the last frame's
+    if (!pfm.empty() && drawn > 0) SaveRadiancePFM(screen, pfm.c_str());
     KillSDL(screen);
     cg_destroy(g_ctx);
     return 0;

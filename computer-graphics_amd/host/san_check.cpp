@@ -274,6 +274,9 @@ int main(int argc, char **argv)
     for (int k = 0; k < 100; ++k) cg_starfield_update(stars.data(), 1000, 16.0f);
     cg_rt_shard sh{1, 3, 15, 0, 0, 0, 0};
     (void)cg_rt_shard_rows(1080, &sh);
+    if (cg_pix_bytes(CG_PIX_ARGB8888) != 4 || cg_pix_bytes(CG_PIX_RGB24) != 3 || cg_pix_bytes(CG_PIX_RGBA_F32) != 16 ||
+        cg_pix_bytes(3) != CG_E_INVALID || cg_pix_bytes(-1) != CG_E_INVALID)
+        fail("cg_pix_bytes", -1);
     const int malformed = malformed_jpegs();
     printf("sanitized host code: %d JPEGs, %d malformed JPEGs rejected, %ld clipped triangles, clean\n", checked,
            malformed, tris);

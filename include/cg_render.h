@@ -77,9 +77,18 @@ typedef struct { int rank, nranks, stripe_h; int row0, rows; int col0, cols; } c
  * (SDLauxiliary.h:149-161).  RGB24 is its wire form for transfers between
  * GPUs: the low three bytes (B, G, R) of each pixel, 3 bytes per pixel --
  * PutPixelSDL's alpha is always 128, so cg_rt_assemble_device restores the
- * exact uint32. */
+ * exact uint32.  RGBA_F32 is what Draw holds before PutPixelSDL clamps it
+ * (raytracer/Source/skeleton.cpp:160-165): four floats per pixel, 16 bytes,
+ * 16-byte aligned -- x, y, z = pixelColour / 9.0f, the vec3 PutPixelSDL is
+ * given (+0 in all three for a pixel none of whose sub-rays hit), and w = the
+ * number of the pixel's nine sub-rays for which ClosestIntersection returned
+ * true (0 .. 9; the reference keeps only validRay = w > 0).  Raytracer frame
+ * calls only (cg_rt_render_frames_device, cg_rt_render_sequence_device). */
 #define CG_PIX_ARGB8888 0
 #define CG_PIX_RGB24 1
+#define CG_PIX_RGBA_F32 2
+/* Host-only: bytes per pixel of a format (4, 3, 16), or CG_E_INVALID. */
+int cg_pix_bytes(int pix_format);
 
 /* rasteriser/Source/TestModelH.h:13-42 `Triangle` (84 B). */
 typedef struct { cg_vec4 v0, v1, v2, normal; cg_vec3 color; int texture; int index; } cg_rtri;
@@ -200,7 +209,10 @@ int cg_rt_render_device(cg_ctx *ctx, const cg_light *lights, int n_lights, const
  * camera, Draw() renders, raytracer/Source/skeleton.cpp:91-94 + :104-169),
  * frame f with camera cams[f] into d_out + f * frame_stride pixels
  * (frame_stride 0 = cg_rt_shard_rows() * W) in pix_format (CG_PIX_*; for
- * RGB24, d_out is a byte buffer and pixel offsets count 3 bytes).  All
+ * RGB24, d_out is a byte buffer and pixel offsets count 3 bytes; for
+ * RGBA_F32, d_out is 16-byte aligned and pixel offsets count 16 bytes --
+ * every route's kernel stores the float sums it holds, no ARGB frame in
+ * between; padding rows are zero bytes; a column window is CG_E_INVALID).  All
  * cameras share width and height; lights and the shard are common.  Frames of
  * the unrotated one-light camera that differ only in cameraPos are rendered up
  * to 32 per kernel launch (a whole GPU's worth of tiles even for a small
@@ -209,13 +221,26 @@ int cg_rt_render_device(cg_ctx *ctx, const cg_light *lights, int n_lights, const
 int cg_rt_render_frames_device(cg_ctx *ctx, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
                                int n_frames, const cg_rt_shard *shard, void *d_out, size_t frame_stride,
                                int pix_format, void *stream);
+/* Draw's float radiance and coverage, whole frame, synchronous: one
+ * cg_rt_render_frames_device of a single CG_PIX_RGBA_F32 frame into context
+ * scratch, then a download into the caller-owned host buffer rgba (W*H*4
+ * floats, row-major, top row first).  CG_E_NOSCENE before a scene is set. */
+int cg_rt_render_radiance(cg_ctx *ctx, const cg_light *lights, int n_lights, const cg_rt_camera *cam,
+                          float *rgba, cg_stats *stats);
+/* d_argb[p] = PutPixelSDL(scale * (x, y, z) of d_rgba[p]) for n_pixels
+ * CG_PIX_RGBA_F32 pixels (d_rgba 16-byte aligned), enqueued on `stream`, no
+ * synchronisation.  scale 1.0f gives cg_rt_render_device's frame bit for bit
+ * (x * 1.0f is exact); any other scale is the caller's exposure. */
+int cg_rt_pack_radiance_device(cg_ctx *ctx, const float *d_rgba, size_t n_pixels, float scale,
+                               uint32_t *d_argb, void *stream);
 /* Frame assembly after a transfer of band shards: d_src holds n_blocks row
  * blocks in order, block b = n_frames x rows[b] rows of `width` pixels in
  * pix_format, landing at frame rows row0[b] .. row0[b] + rows[b] - 1 (rows
  * outside the frame are skipped) of frame f = d_frames + f * frame_stride
  * pixels (ARGB8888).  With cols > 0 the source rows hold only the window
  * columns col0 .. col0 + cols - 1 (4-aligned) and the rest of each row is set
- * to 0x80000000.  row0 / rows are host arrays, n_blocks <= 64. */
+ * to 0x80000000.  row0 / rows are host arrays, n_blocks <= 64.
+ * CG_PIX_RGBA_F32 is CG_E_INVALID here (no multi-GPU transfer of float frames). */
 int cg_rt_assemble_device(cg_ctx *ctx, const void *d_src, int pix_format, const int *row0, const int *rows,
                           int n_blocks, int width, int height, int n_frames, uint32_t *d_frames,
                           size_t frame_stride, int col0, int cols, void *stream);
