@@ -57,6 +57,26 @@ class RtShard(C.Structure):
 
 
 PIX_ARGB8888, PIX_RGB24, PIX_RGBA_F32 = 0, 1, 2   # cg_render.h CG_PIX_*
+TONE_LINEAR, TONE_REINHARD, TONE_REINHARD_WHITE = 0, 1, 2   # cg_render.h CG_TONE_*
+HDR_BINS = 256
+
+
+class HdrStats(C.Structure):           # cg_hdr_stats, 32 B
+    _fields_ = [("n_counted", C.c_uint32), ("n_dark", C.c_uint32), ("n_uncovered", C.c_uint32),
+                ("max_bits", C.c_uint32), ("min_bits", C.c_uint32), ("pad", C.c_uint32 * 3)]
+
+
+HDR_STATS_DTYPE = np.dtype([("n_counted", "<u4"), ("n_dark", "<u4"), ("n_uncovered", "<u4"), ("max_bits", "<u4"),
+                            ("min_bits", "<u4"), ("pad", "<u4", 3)])
+
+
+class HdrExposureParams(C.Structure):  # cg_hdr_exposure_params
+    _fields_ = [("permille", C.c_int), ("target", C.c_float), ("scale_min", C.c_float), ("scale_max", C.c_float),
+                ("rate", C.c_float)]
+
+
+def hdr_params(permille=990, target=1.0, scale_min=2.0 ** -16, scale_max=2.0 ** 16, rate=1.0):
+    return HdrExposureParams(permille, target, scale_min, scale_max, rate)
 
 
 class RTri(C.Structure):       # rasteriser Triangle, 84 B
@@ -172,6 +192,21 @@ _SIGS = {
     "cg_pix_bytes": (C.c_int, [C.c_int]),
     "cg_rt_render_radiance": (C.c_int, [P, C.POINTER(Light), C.c_int, C.POINTER(RtCamera), P, C.POINTER(Stats)]),
     "cg_rt_pack_radiance_device": (C.c_int, [P, P, C.c_size_t, C.c_float, P, P]),
+    "cg_hdr_luminance": (C.c_float, [C.c_float, C.c_float, C.c_float]),
+    "cg_hdr_bin": (C.c_int, [C.c_float]),
+    "cg_hdr_bin_edge": (C.c_float, [C.c_int]),
+    "cg_hdr_exposure": (C.c_int, [P, C.c_int, C.POINTER(HdrExposureParams), P, P]),
+    "cg_hdr_tone": (C.c_float, [C.c_int, C.c_float, C.c_float]),
+    "cg_hdr_histogram_device": (C.c_int, [P, P, C.c_int, C.c_size_t, C.c_int, C.c_size_t, P, P, P]),
+    "cg_hdr_exposure_device": (C.c_int, [P, P, C.c_int, C.POINTER(HdrExposureParams), P, P, P]),
+    "cg_rt_tonemap_pack_device": (C.c_int, [P, P, C.c_size_t, C.c_int, C.c_size_t, P, C.c_int, C.c_float, P,
+                                            C.c_size_t, P]),
+    "cg_rt_render_exposed_device": (C.c_int, [P, C.POINTER(Light), C.c_int, C.POINTER(RtCamera), C.c_int, C.c_int,
+                                              C.POINTER(HdrExposureParams), P, C.c_int, C.c_float, P, C.c_size_t, P,
+                                              P]),
+    "cg_rt_render_exposed": (C.c_int, [P, C.POINTER(Light), C.c_int, C.POINTER(RtCamera), C.c_int, C.c_int,
+                                       C.POINTER(HdrExposureParams), P, C.c_int, C.c_float, P, C.c_size_t, P,
+                                       C.POINTER(Stats)]),
     "cg_rt_render_sequence": (C.c_int, [P, C.POINTER(Light), C.c_int, C.POINTER(RtCamera), C.c_int, P,
                                         C.c_size_t, C.c_int, C.POINTER(Stats)]),
     "cg_rt_sequence_runs": (C.c_int, [C.POINTER(RtCamera), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RtShard),
@@ -301,6 +336,68 @@ def pix_bytes(pix_format):
     if n < 0:
         raise ValueError(f"pix_format {pix_format}")
     return n
+
+
+def hdr_luminance(x, y, z):
+    """cg_hdr_luminance elementwise: (0.2126 x + 0.7152 y) + 0.0722 z in float32 (host-only; no GPU needed)."""
+    lib = load()
+    x, y, z = np.broadcast_arrays(np.asarray(x, np.float32), np.asarray(y, np.float32), np.asarray(z, np.float32))
+    out = np.empty(x.shape, np.float32)
+    for i, (a, b, c) in enumerate(zip(x.ravel().tolist(), y.ravel().tolist(), z.ravel().tolist())):
+        out.flat[i] = lib.cg_hdr_luminance(a, b, c)
+    return out
+
+
+def _f32_arg(bits):
+    """A float32 bit pattern as a ctypes argument: through c_float's buffer, so that a NaN keeps its payload."""
+    return C.c_float.from_buffer_copy(np.uint32(bits).tobytes())
+
+
+def hdr_bin(L):
+    """cg_hdr_bin elementwise: the histogram bin of a luminance, -1 when it is not counted."""
+    lib = load()
+    L = np.asarray(L, np.float32)
+    out = np.empty(L.shape, np.int32)
+    for i, b in enumerate(L.ravel().view(np.uint32).tolist()):
+        out.flat[i] = lib.cg_hdr_bin(_f32_arg(b))
+    return out
+
+
+def hdr_bin_edge(b):
+    """cg_hdr_bin_edge elementwise: the upper edge of bins 0 .. 255."""
+    lib = load()
+    b = np.asarray(b, np.int32)
+    if ((b < 0) | (b >= HDR_BINS)).any():
+        raise ValueError("bin outside 0..255")
+    out = np.empty(b.shape, np.float32)
+    for i, v in enumerate(b.ravel().tolist()):
+        out.flat[i] = lib.cg_hdr_bin_edge(v)
+    return out
+
+
+def hdr_tone(op, v, white2=1.0):
+    """cg_hdr_tone elementwise."""
+    lib = load()
+    v = np.asarray(v, np.float32)
+    out = np.empty(v.shape, np.float32)
+    for i, b in enumerate(v.ravel().view(np.uint32).tolist()):
+        out.flat[i] = lib.cg_hdr_tone(op, _f32_arg(b), white2)
+    return out
+
+
+def hdr_exposure(hist, params=None, prev=None, **kw):
+    """cg_hdr_exposure: the scales s_f of histograms uint32[n, 256] (params: HdrExposureParams, or
+    hdr_params' keywords; prev: the previous scale or None)."""
+    lib = load()
+    params = hdr_params(**kw) if params is None else params
+    hist = np.ascontiguousarray(hist, np.uint32).reshape(-1, HDR_BINS)
+    scales = np.zeros(len(hist), np.float32)
+    pv = None if prev is None else np.array([prev], np.float32)
+    rc = lib.cg_hdr_exposure(hist.ctypes.data_as(P), len(hist), C.byref(params),
+                             pv.ctypes.data_as(P) if pv is not None else None, scales.ctypes.data_as(P))
+    if rc:
+        raise ValueError(f"cg_hdr_exposure: {rc}")
+    return scales
 
 
 ROUTES = ("pixel", "lattice", "lattice_yaw", "lights", "lights_yaw", "big_pixel", "big_lattice", "big_lattice_yaw")
@@ -920,6 +1017,66 @@ class Context:
         self._check(self.lib.cg_rt_pack_radiance_device(self.h, P(d_rgba), n_pixels, scale, P(d_argb),
                                                         P(stream) if stream else None),
                     "cg_rt_pack_radiance_device")
+
+    def hdr_histogram_device(self, d_pixels, channels, n_pixels, n_frames, d_hist, d_stats=None, frame_stride=0,
+                             stream=None):
+        """cg_hdr_histogram_device: d_hist[f * 256 + b] and d_stats[f] of n_frames planes."""
+        self._check(self.lib.cg_hdr_histogram_device(self.h, P(d_pixels), channels, n_pixels, n_frames, frame_stride,
+                                                     P(d_hist), P(d_stats) if d_stats else None,
+                                                     P(stream) if stream else None), "cg_hdr_histogram_device")
+
+    def hdr_exposure_device(self, d_hist, n_frames, params, d_scales, d_prev=None, stream=None):
+        """cg_hdr_exposure_device: d_scales[f] = s_f (d_prev: a device float or None)."""
+        self._check(self.lib.cg_hdr_exposure_device(self.h, P(d_hist), n_frames, C.byref(params),
+                                                    P(d_prev) if d_prev else None, P(d_scales),
+                                                    P(stream) if stream else None), "cg_hdr_exposure_device")
+
+    def rt_tonemap_pack_device(self, d_rgba, n_pixels, n_frames, d_scales, d_argb, op=TONE_LINEAR, white2=1.0,
+                               src_stride=0, dst_stride=0, stream=None):
+        """cg_rt_tonemap_pack_device: d_argb = PutPixelSDL(tone(op, c * d_scales[f])) per frame."""
+        self._check(self.lib.cg_rt_tonemap_pack_device(self.h, P(d_rgba), n_pixels, n_frames, src_stride, P(d_scales),
+                                                       op, white2, P(d_argb), dst_stride,
+                                                       P(stream) if stream else None), "cg_rt_tonemap_pack_device")
+
+    @staticmethod
+    def _exposed_lights(cams, lights, per_frame_lights):
+        if per_frame_lights:
+            if len(lights) != len(cams):
+                raise ValueError("one light list per frame")
+            return sequence_lights(lights)
+        lights = default_lights() if lights is None else lights
+        return lights, len(lights)
+
+    def rt_render_exposed_device(self, cams, d_argb, d_scales, params, lights=None, per_frame_lights=False,
+                                 d_prev=None, op=TONE_LINEAR, white2=1.0, frame_stride=0, stream=None):
+        """cg_rt_render_exposed_device: len(cams) frames rendered, exposed and packed into d_argb +
+        f * frame_stride pixels, their scales into d_scales (device memory, no host wait)."""
+        larr, n = self._exposed_lights(cams, lights, per_frame_lights)
+        arr = (RtCamera * max(len(cams), 1))(*cams)
+        self._check(self.lib.cg_rt_render_exposed_device(self.h, larr, n, arr, len(cams), int(bool(per_frame_lights)),
+                                                         C.byref(params), P(d_prev) if d_prev else None, op, white2,
+                                                         P(d_argb), frame_stride, P(d_scales),
+                                                         P(stream) if stream else None),
+                    "cg_rt_render_exposed_device")
+
+    def rt_render_exposed(self, cams, lights=None, per_frame_lights=False, permille=990, target=1.0,
+                          scale_min=2.0 ** -16, scale_max=2.0 ** 16, rate=1.0, prev=None, op=TONE_LINEAR, white2=1.0):
+        """cg_rt_render_exposed: (frames uint32[n, H, W], scales float32[n]) in host memory."""
+        n = len(cams)
+        if n == 0:
+            return np.zeros((0, 0, 0), np.uint32), np.zeros(0, np.float32)
+        larr, nl = self._exposed_lights(cams, lights, per_frame_lights)
+        arr = (RtCamera * n)(*cams)
+        params = hdr_params(permille, target, scale_min, scale_max, rate)
+        out = np.zeros((n, cams[0].height, cams[0].width), np.uint32)
+        scales = np.zeros(n, np.float32)
+        pv = None if prev is None else np.array([prev], np.float32)
+        st = Stats()
+        self._check(self.lib.cg_rt_render_exposed(self.h, larr, nl, arr, n, int(bool(per_frame_lights)),
+                                                  C.byref(params), pv.ctypes.data_as(P) if pv is not None else None,
+                                                  op, white2, out.ctypes.data_as(P), 0, scales.ctypes.data_as(P),
+                                                  C.byref(st)), "cg_rt_render_exposed")
+        return out, scales
 
     def rt_render_frames(self, cams, out=None, chunk=0, lights=None, frame_stride=0):
         """cg_rt_render_frames: len(cams) frames into host memory `out` at f * frame_stride pixels

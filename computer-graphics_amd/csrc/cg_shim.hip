@@ -16,6 +16,7 @@
 #include <thread>
 #include <vector>
 
+#include "cg_hdr.h"
 #include "cg_internal.h"
 #include "cg_rast_dev.h"
 #include "cg_rt_grid.h"
@@ -67,6 +68,11 @@ hipError_t launch_rt_unstripe(const uint32_t *, int, int, int, int, int, int, ui
 hipError_t launch_rt_pack_rgb24(const uint32_t *, int, int, int, int, uint8_t *, hipStream_t);
 hipError_t launch_rt_pack_radiance(const float *, size_t, float, uint32_t *, hipStream_t);
 hipError_t launch_rt_assemble(const uint8_t *, const RtBlocks &, int, uint32_t *, size_t, hipStream_t);
+hipError_t launch_hdr_histogram(const float *, int, size_t, int, size_t, uint32_t *, cg_hdr_stats *, hipStream_t);
+hipError_t launch_hdr_exposure(const uint32_t *, int, const cg_hdr_exposure_params &, const float *, float *,
+                               hipStream_t);
+hipError_t launch_rt_tonemap_pack(const float *, size_t, int, size_t, const float *, int, float, uint32_t *, size_t,
+                                  hipStream_t);
 hipError_t launch_rt_probe_closest(const RtFrame &, const cg_tri *, const RtSphere *,
                                    const cg_vec4 *, const cg_vec4 *, int, cg_isect *, int *,
                                    hipStream_t);
@@ -240,6 +246,9 @@ struct cg_ctx {
     hipStream_t xfer = nullptr;
     hipEvent_t ev_rdone[2] = {nullptr, nullptr}, ev_cdone[2] = {nullptr, nullptr};
     DevBuf hslot[2];
+    // cg_rt_render_exposed_device: a chunk's CG_PIX_RGBA_F32 frames and histograms; the host form's
+    // chunk of ARGB frames, its scales and previous scale
+    DevBuf hdr_rgba, hdr_hist, hdr_argb, hdr_scales;
     std::unique_ptr<HostFill> hfill;    // their black columns (created on first use)
     RtGrid grid{};                      // large scenes only (n_tris > 64)
     GridBuild gbuild;                   // cg_rt_set_scene_device: the device builder's scratch and counts
@@ -542,6 +551,7 @@ extern "C" void cg_destroy(cg_ctx *c)
         if (c->ev_cdone[k]) (void)hipEventDestroy(c->ev_cdone[k]);
     }
     if (c->xfer) (void)hipStreamDestroy(c->xfer);
+    c->hdr_rgba.release(); c->hdr_hist.release(); c->hdr_argb.release(); c->hdr_scales.release();
     c->rs_info.release();
     for (int k = 0; k < cg_ctx::kRastHostSlots; ++k) {
         c->rs_argb[k].release(); c->rs_depth[k].release(); c->rs_shadow[k].release();
@@ -2161,6 +2171,168 @@ static hipError_t download_frames(uint32_t *dst, size_t stride, const uint32_t *
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// ---- auto-exposure and tone mapping (kernels: cg_hdr.hip; arithmetic: cg_hdr.h) ----
+extern "C" int cg_hdr_histogram_device(cg_ctx *c, const float *d_pixels, int channels, size_t n_pixels, int n_frames,
+                                       size_t frame_stride, uint32_t *d_hist, cg_hdr_stats *d_stats, void *stream)
+{
+    if (!c || n_frames < 0 || (channels != 3 && channels != 4) || n_pixels >= ((size_t)1 << 32)) return CG_E_INVALID;
+    if (n_frames == 0) return CG_OK;
+    const size_t stride = frame_stride ? frame_stride : n_pixels;
+    if (!d_hist || ((uintptr_t)d_hist & 15) || ((uintptr_t)d_stats & 3) || (n_pixels && !d_pixels) ||
+        ((uintptr_t)d_pixels & (channels == 4 ? 15 : 3)) || stride < n_pixels)
+        return CG_E_INVALID;
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    CG_TRY(c, launch_hdr_histogram(d_pixels, channels, n_pixels, n_frames, stride, d_hist, d_stats,
+                                   stream ? (hipStream_t)stream : c->stream),
+           "histogram launch");
+    return CG_OK;
+}
+
+extern "C" int cg_hdr_exposure_device(cg_ctx *c, const uint32_t *d_hist, int n_frames,
+                                      const cg_hdr_exposure_params *params, const float *d_prev, float *d_scales,
+                                      void *stream)
+{
+    if (!c || n_frames < 0 || !hdr_params_ok(params)) return CG_E_INVALID;
+    if (n_frames == 0) return CG_OK;
+    if (!d_hist || ((uintptr_t)d_hist & 15) || !d_scales || ((uintptr_t)d_scales & 3) || ((uintptr_t)d_prev & 3))
+        return CG_E_INVALID;
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    CG_TRY(c, launch_hdr_exposure(d_hist, n_frames, *params, d_prev, d_scales, stream ? (hipStream_t)stream : c->stream),
+           "exposure launch");
+    return CG_OK;
+}
+
+extern "C" int cg_rt_tonemap_pack_device(cg_ctx *c, const float *d_rgba, size_t n_pixels, int n_frames,
+                                         size_t src_stride, const float *d_scales, int op, float white2,
+                                         uint32_t *d_argb, size_t dst_stride, void *stream)
+{
+    if (!c || n_frames < 0 || !hdr_tone_ok(op, white2) || n_pixels >= ((size_t)1 << 32)) return CG_E_INVALID;
+    if (n_frames == 0) return CG_OK;
+    const size_t ss = src_stride ? src_stride : n_pixels, ds = dst_stride ? dst_stride : n_pixels;
+    if (!d_scales || ((uintptr_t)d_scales & 3) || (n_pixels && (!d_rgba || !d_argb)) || ((uintptr_t)d_rgba & 15) ||
+        ((uintptr_t)d_argb & 3) || ss < n_pixels || ds < n_pixels)
+        return CG_E_INVALID;
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    CG_TRY(c, launch_rt_tonemap_pack(d_rgba, n_pixels, n_frames, ss, d_scales, op, white2, d_argb, ds,
+                                     stream ? (hipStream_t)stream : c->stream),
+           "tonemap pack launch");
+    return CG_OK;
+}
+
+constexpr int kHdrChunkFrames = 8;   // frames of cg_rt_render_exposed_device's scratch
+
+// what both forms of cg_rt_render_exposed check before anything is enqueued
+static int rt_exposed_check(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams, int n_frames,
+                            const cg_hdr_exposure_params *params, int op, float white2, size_t frame_stride)
+{
+    if (!c || n_frames < 0 || (n_frames && !cams) || !hdr_params_ok(params) || !hdr_tone_ok(op, white2) ||
+        n_lights < 0 || n_lights > kMaxLights || (n_lights && !lights))
+        return CG_E_INVALID;
+    if (n_frames == 0) return CG_OK;
+    const int W = cams[0].width, H = cams[0].height;
+    if (W <= 0 || H <= 0 || (size_t)W * H >= ((size_t)1 << 32)) return CG_E_INVALID;
+    for (int f = 1; f < n_frames; ++f)
+        if (cams[f].width != W || cams[f].height != H) return CG_E_INVALID;
+    if (frame_stride && frame_stride < (size_t)W * H) return CG_E_INVALID;
+    if (c->n_tris < 0) {
+        c->err = "render before cg_rt_set_scene";
+        return CG_E_NOSCENE;
+    }
+    return CG_OK;
+}
+
+// Frames f0 .. f0 + nf - 1 (nf <= kHdrChunkFrames) of an exposed call: rendered as CG_PIX_RGBA_F32
+// into the context's scratch, then histogram, exposure (previous scale *d_prev) and pack, all on st.
+static int rt_exposed_chunk(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams, int f0, int nf,
+                            int per_frame_lights, const cg_hdr_exposure_params &params, const float *d_prev, int op,
+                            float white2, uint32_t *d_argb, size_t stride, float *d_scales, hipStream_t st)
+{
+    const int H = cams[0].height;
+    const size_t px = (size_t)cams[0].width * H;
+    CG_TRY(c, c->hdr_rgba.ensure(kHdrChunkFrames * px * 16), "alloc exposure frames");
+    CG_TRY(c, c->hdr_hist.ensure(kHdrChunkFrames * CG_HDR_BINS * sizeof(uint32_t)), "alloc exposure histograms");
+    cg_rt_shard whole{0, 1, H, 0, H, 0, 0};   // a band of exactly the frame's rows
+    const int rc = per_frame_lights
+        ? cg_rt_render_sequence_device(c, lights + (size_t)f0 * n_lights, n_lights, cams + f0, nf, &whole,
+                                       c->hdr_rgba.p, px, CG_PIX_RGBA_F32, st)
+        : cg_rt_render_frames_device(c, lights, n_lights, cams + f0, nf, &whole, c->hdr_rgba.p, px, CG_PIX_RGBA_F32, st);
+    if (rc) return rc;
+    const float *rgba = (const float *)c->hdr_rgba.p;
+    uint32_t *hist = (uint32_t *)c->hdr_hist.p;
+    CG_TRY(c, launch_hdr_histogram(rgba, 4, px, nf, px, hist, nullptr, st), "histogram launch");
+    CG_TRY(c, launch_hdr_exposure(hist, nf, params, d_prev, d_scales, st), "exposure launch");
+    CG_TRY(c, launch_rt_tonemap_pack(rgba, px, nf, px, d_scales, op, white2, d_argb, stride, st), "tonemap pack launch");
+    return CG_OK;
+}
+
+extern "C" int cg_rt_render_exposed_device(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
+                                           int n_frames, int per_frame_lights, const cg_hdr_exposure_params *params,
+                                           const float *d_prev, int op, float white2, uint32_t *d_argb,
+                                           size_t frame_stride, float *d_scales, void *stream)
+{
+    if (int rc = rt_exposed_check(c, lights, n_lights, cams, n_frames, params, op, white2, frame_stride)) return rc;
+    if (n_frames == 0) return CG_OK;
+    if (!d_argb || ((uintptr_t)d_argb & 3) || !d_scales || ((uintptr_t)d_scales & 3) || ((uintptr_t)d_prev & 3))
+        return CG_E_INVALID;
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const size_t stride = frame_stride ? frame_stride : (size_t)cams[0].width * cams[0].height;
+    for (int f0 = 0; f0 < n_frames; f0 += kHdrChunkFrames) {
+        const int nf = std::min(kHdrChunkFrames, n_frames - f0);
+        if (int rc = rt_exposed_chunk(c, lights, n_lights, cams, f0, nf, per_frame_lights, *params,
+                                      f0 ? d_scales + f0 - 1 : d_prev, op, white2, d_argb + (size_t)f0 * stride, stride,
+                                      d_scales + f0, st))
+            return rc;
+    }
+    return CG_OK;
+}
+
+// Host-memory form: the device form's chunks into context scratch, each chunk's frames downloaded
+// after its render; the scales (and the caller's previous scale) live in one device array,
+// [0] the previous scale, [1 + f] frame f's.
+extern "C" int cg_rt_render_exposed(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
+                                    int n_frames, int per_frame_lights, const cg_hdr_exposure_params *params,
+                                    const float *prev, int op, float white2, uint32_t *argb, size_t frame_stride,
+                                    float *scales, cg_stats *stats)
+{
+    if (int rc = rt_exposed_check(c, lights, n_lights, cams, n_frames, params, op, white2, frame_stride)) return rc;
+    if (n_frames == 0) return CG_OK;
+    if (!argb || !scales) return CG_E_INVALID;
+    auto t0 = std::chrono::steady_clock::now();
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    const size_t px = (size_t)cams[0].width * cams[0].height;
+    const size_t stride = frame_stride ? frame_stride : px;
+    CG_TRY(c, c->hdr_argb.ensure(kHdrChunkFrames * px * sizeof(uint32_t)), "alloc exposed frames");
+    CG_TRY(c, c->hdr_scales.ensure(((size_t)n_frames + 1) * sizeof(float)), "alloc scales");
+    float *d_s = (float *)c->hdr_scales.p;
+    uint32_t *d_a = (uint32_t *)c->hdr_argb.p;
+    if (prev) CG_TRY(c, hipMemcpyAsync(d_s, prev, sizeof(float), hipMemcpyHostToDevice, c->stream), "upload scale");
+    float ms_sum = 0.f;
+    for (int f0 = 0; f0 < n_frames; f0 += kHdrChunkFrames) {
+        const int nf = std::min(kHdrChunkFrames, n_frames - f0);
+        CG_TRY(c, hipEventRecord(c->ev0, c->stream), "event");
+        if (int rc = rt_exposed_chunk(c, lights, n_lights, cams, f0, nf, per_frame_lights, *params,
+                                      f0 || prev ? d_s + f0 : nullptr, op, white2, d_a, px, d_s + 1 + f0, c->stream))
+            return rc;
+        CG_TRY(c, hipEventRecord(c->ev1, c->stream), "event");
+        CG_TRY(c, download_frames(argb + (size_t)f0 * stride, stride, d_a, cams[0].width, cams[0].height, nf, 0,
+                                  cams[0].width, false, c->stream),
+               "download frames");
+        CG_TRY(c, hipStreamSynchronize(c->stream), "exposed frames");
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
+        ms_sum += ms;
+    }
+    CG_TRY(c, hipMemcpy(scales, d_s + 1, (size_t)n_frames * sizeof(float), hipMemcpyDeviceToHost), "download scales");
+    if (stats) {
+        stats->kernel_ms = ms_sum;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->n_tris = c->n_tris;
+        stats->n_spans = 0;
+    }
+    return CG_OK;
 }
 
 extern "C" int cg_rt_render(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cam,

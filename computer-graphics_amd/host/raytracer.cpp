@@ -9,6 +9,7 @@
 // GPU through the C-ABI (include/cg_render.h).
 //
 //   raytracer [--width W] [--height H] [--focal F] [--keys KEYS] [--out FILE] [--batch] [--pfm FILE]
+//             [--auto-exposure PERMILLE[,TARGET]] [--tonemap linear|reinhard|reinhard-white:W]
 //
 // --batch: Update() runs over the whole key script first, each frame's globals
 // are recorded, and one cg_rt_render_sequence call renders every frame; the
@@ -16,6 +17,12 @@
 // --pfm FILE: the last frame's pixelColour / 9.0f before PutPixelSDL clamps it
 // (cg_rt_render_radiance), as a little-endian colour PFM: "PF", the size, "-1.0",
 // then rows bottom-up of three floats a pixel.
+// --auto-exposure PERMILLE[,TARGET]: the run's frames go through one cg_rt_render_exposed call
+// (as --batch records them): each frame's scale puts the upper edge of the luminance bin that
+// holds its PERMILLE-th thousandth of lit pixels at TARGET (default 1), no adaptation; the
+// screenshot is the last exposed frame and the scale of every frame is printed.
+// --tonemap: the curve between the scaled radiance and PutPixelSDL (default linear; reinhard-white:W
+// maps radiance W to white); with --tonemap alone the scale is 1.
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -173,7 +180,10 @@ bool Update()
 int main(int argc, char *argv[])
 {
     string out = "screenshot.bmp", pfm;
-    bool batch = false;
+    bool batch = false, exposed = false;
+    cg_hdr_exposure_params expo{990, 1.0f, 1.0f, 1.0f, 1.0f};   // --tonemap alone: every scale is 1
+    int tone = CG_TONE_LINEAR;
+    float white2 = 1.0f;
     for (int i = 1; i < argc; i += 2) {
         string a = argv[i];
         if (a == "--batch") {
@@ -188,6 +198,28 @@ int main(int argc, char *argv[])
         else if (a == "--keys") g_keys = argv[i + 1];
         else if (a == "--out") out = argv[i + 1];
         else if (a == "--pfm") pfm = argv[i + 1];
+        else if (a == "--auto-exposure") {
+            const string v = argv[i + 1];
+            const size_t comma = v.find(',');
+            expo.permille = atoi(v.substr(0, comma).c_str());
+            expo.target = comma == string::npos ? 1.0f : (float)atof(v.substr(comma + 1).c_str());
+            expo.scale_min = 1.0f / 65536.0f;
+            expo.scale_max = 65536.0f;
+            exposed = true;
+        } else if (a == "--tonemap") {
+            const string v = argv[i + 1];
+            if (v == "linear") tone = CG_TONE_LINEAR;
+            else if (v == "reinhard") tone = CG_TONE_REINHARD;
+            else if (v.rfind("reinhard-white:", 0) == 0) {
+                const float w = (float)atof(v.c_str() + 15);
+                tone = CG_TONE_REINHARD_WHITE;
+                white2 = w * w;
+            } else {
+                cerr << "--tonemap linear|reinhard|reinhard-white:W" << endl;
+                return 1;
+            }
+            exposed = true;
+        }
     }
     int rc = cg_create(0, &g_ctx);
     if (rc) die(rc, "cg_create");
@@ -197,7 +229,7 @@ int main(int argc, char *argv[])
     light1.colour = 14.f * vec3(1, 1, 1);
     lights.push_back(light1);
     size_t drawn = 0;
-    if (batch) {
+    if (batch || exposed) {
         // the main loop's frames in one call: each Update()'s globals recorded, then every Draw()
         vector<cg_rt_camera> cams;
         vector<Light> seq;   // frame-major, lights.size() per frame
@@ -209,9 +241,18 @@ int main(int argc, char *argv[])
             UploadScene();
             const size_t px = (size_t)screen->width * screen->height;
             vector<uint32_t> frames(cams.size() * px);
-            rc = cg_rt_render_sequence(g_ctx, reinterpret_cast<const cg_light *>(seq.data()), (int)lights.size(),
-                                       cams.data(), (int)cams.size(), frames.data(), 0, 0, nullptr);
-            if (rc) die(rc, "cg_rt_render_sequence");
+            if (exposed) {
+                vector<float> scales(cams.size());
+                rc = cg_rt_render_exposed(g_ctx, reinterpret_cast<const cg_light *>(seq.data()), (int)lights.size(),
+                                          cams.data(), (int)cams.size(), 1, &expo, nullptr, tone, white2, frames.data(),
+                                          0, scales.data(), nullptr);
+                if (rc) die(rc, "cg_rt_render_exposed");
+                for (size_t f = 0; f < scales.size(); ++f) cout << "Exposure scale : " << scales[f] << endl;
+            } else {
+                rc = cg_rt_render_sequence(g_ctx, reinterpret_cast<const cg_light *>(seq.data()), (int)lights.size(),
+                                           cams.data(), (int)cams.size(), frames.data(), 0, 0, nullptr);
+                if (rc) die(rc, "cg_rt_render_sequence");
+            }
             memcpy(screen->buffer, frames.data() + (cams.size() - 1) * px, px * sizeof(uint32_t));
             SDL_Renderframe(screen);
         }

@@ -277,6 +277,28 @@ int main(int argc, char **argv)
     if (cg_pix_bytes(CG_PIX_ARGB8888) != 4 || cg_pix_bytes(CG_PIX_RGB24) != 3 || cg_pix_bytes(CG_PIX_RGBA_F32) != 16 ||
         cg_pix_bytes(3) != CG_E_INVALID || cg_pix_bytes(-1) != CG_E_INVALID)
         fail("cg_pix_bytes", -1);
+    // the exposure chain's host-only restatements: every bin, a two-frame chain, the refusals
+    for (int b = 0; b < CG_HDR_BINS; ++b)
+        if (cg_hdr_bin(cg_hdr_bin_edge(b)) != (b < CG_HDR_BINS - 1 ? b + 1 : b)) fail("cg_hdr_bin", b);
+    if (cg_hdr_bin(0.0f) != -1 || cg_hdr_bin_edge(-1) != 0.0f || cg_hdr_bin_edge(CG_HDR_BINS) != 0.0f ||
+        cg_hdr_luminance(1.0f, 1.0f, 1.0f) != 1.0f || cg_hdr_tone(CG_TONE_REINHARD, 1.0f, 1.0f) != 0.5f ||
+        cg_hdr_tone(CG_TONE_REINHARD_WHITE, 1.0f, 4.0f) != 0.625f)
+        fail("cg_hdr helpers", -1);
+    {
+        std::vector<uint32_t> hist(2 * CG_HDR_BINS, 0u);
+        hist[127] = 7u;                    // t = 1
+        hist[CG_HDR_BINS + 135] = 7u;      // t = 0.5
+        cg_hdr_exposure_params ep{990, 1.0f, 1.0f / 65536.0f, 65536.0f, 0.25f};
+        float scales[2] = {0.f, 0.f}, prev = 4.0f;
+        if (cg_hdr_exposure(hist.data(), 2, &ep, nullptr, scales) != CG_OK || scales[0] != 1.0f || scales[1] != 0.875f)
+            fail("cg_hdr_exposure", -1);
+        if (cg_hdr_exposure(hist.data(), 2, &ep, &prev, scales) != CG_OK || scales[0] != 4.0f || scales[1] != 3.125f)
+            fail("cg_hdr_exposure with a previous scale", -1);
+        ep.permille = 1001;
+        if (cg_hdr_exposure(hist.data(), 2, &ep, nullptr, scales) != CG_E_INVALID ||
+            cg_hdr_exposure(hist.data(), 0, nullptr, nullptr, nullptr) != CG_E_INVALID)
+            fail("cg_hdr_exposure refusals", -1);
+    }
     const int malformed = malformed_jpegs();
     printf("sanitized host code: %d JPEGs, %d malformed JPEGs rejected, %ld clipped triangles, clean\n", checked,
            malformed, tris);

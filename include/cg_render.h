@@ -233,6 +233,102 @@ int cg_rt_render_radiance(cg_ctx *ctx, const cg_light *lights, int n_lights, con
  * (x * 1.0f is exact); any other scale is the caller's exposure. */
 int cg_rt_pack_radiance_device(cg_ctx *ctx, const float *d_rgba, size_t n_pixels, float scale,
                                uint32_t *d_argb, void *stream);
+
+/* ---- Auto-exposure and tone mapping (cg_hdr.hip; arithmetic in csrc/cg_hdr.h) ----
+ * Every step is integer arithmetic or single IEEE float32 operations in the
+ * order stated, so kernels and host helpers agree bit for bit.
+ *
+ * Luminance  L = (0.2126f * x + 0.7152f * y) + 0.0722f * z.
+ * Bin        a pixel is counted when L > 0.0f (+inf yes; NaN, +-0, negatives
+ *            no); its bin is clamp((bits(L) >> 20) - 888, 0, 255): eight bins
+ *            an octave from 2^-16 to 2^16, bin 0 also everything smaller, bin
+ *            255 everything from 2^15 * 15/8 up.  The upper edge of bin b is
+ *            the float with bits (888 + b + 1) << 20 (bin 255: 2^16).
+ * Exposure   of frame f from its histogram h[256]: total = sum h,
+ *            k = max(1, (total * permille + 999) / 1000) in 64 bits, b = the
+ *            first bin whose running sum reaches k, t_f = target / edge(b)
+ *            (1.0f when total == 0), then fminf(fmaxf(t_f, scale_min),
+ *            scale_max).  s_0 = the previous scale where the caller gives one,
+ *            else t_0; s_f = s_{f-1} + (t_f - s_{f-1}) * rate for f > 0.
+ * Tone       per channel on v = c * s: LINEAR v; REINHARD v / (1.0f + v);
+ *            REINHARD_WHITE (v * (1.0f + v / white2)) / (1.0f + v).  The
+ *            result goes to PutPixelSDL unchanged. */
+#define CG_HDR_BINS 256
+#define CG_TONE_LINEAR 0
+#define CG_TONE_REINHARD 1
+#define CG_TONE_REINHARD_WHITE 2
+/* Per-frame record beside a histogram, 32 bytes.  A plane has fewer than 2^32
+ * pixels, so no count wraps.  n_dark: covered pixels with !(L > 0);
+ * n_uncovered (4-float pixels only): pixels with !(w > 0.0f), neither counted
+ * nor dark; max_bits / min_bits: over the bits of the counted pixels' L, 0 and
+ * 0xFFFFFFFF when there are none.  All fields are order-independent. */
+typedef struct {
+    uint32_t n_counted, n_dark, n_uncovered, max_bits, min_bits;
+    uint32_t pad[3];
+} cg_hdr_stats;
+/* permille 0..1000, rate in [0, 1] (1 = no adaptation), scale_min <= scale_max. */
+typedef struct { int permille; float target, scale_min, scale_max, rate; } cg_hdr_exposure_params;
+/* Host-only restatements (no device, no context).  cg_hdr_bin: -1 when L is
+ * not counted.  cg_hdr_bin_edge: 0.0f for a bin outside 0..255.
+ * cg_hdr_exposure: scales[f] = s_f for n_frames histograms of 256 counts each
+ * (prev may be NULL); CG_E_INVALID for NULL pointers, n_frames < 0 or bad
+ * parameters.  cg_hdr_tone: an unknown op is treated as LINEAR. */
+float cg_hdr_luminance(float x, float y, float z);
+int cg_hdr_bin(float L);
+float cg_hdr_bin_edge(int bin);
+int cg_hdr_exposure(const uint32_t *hist, int n_frames, const cg_hdr_exposure_params *params, const float *prev,
+                    float *scales);
+float cg_hdr_tone(int op, float v, float white2);
+/* The device entry points below enqueue on `stream` (NULL: the context's) and
+ * do not synchronise.  CG_E_INVALID: NULL or misaligned pointers, channels
+ * outside {3, 4}, a stride below the plane, permille outside 0..1000, rate
+ * outside [0, 1], scale_min > scale_max, an unknown tone op, white2 <= 0 where
+ * it is used.  n_frames == 0 returns CG_OK and touches nothing.
+ *
+ * Histogram and record of n_frames planes of n_pixels pixels of `channels`
+ * floats: 4 = CG_PIX_RGBA_F32 (16-byte aligned, w the coverage), 3 = a 3-float
+ * plane such as the rasteriser's screen (every pixel covered).  Frame f starts
+ * at d_pixels + f * frame_stride pixels (0: n_pixels); the pixels between
+ * frames are never read.  Writes d_hist[f * 256 + b] and d_stats[f] (d_stats
+ * may be NULL); the call clears both itself, on the stream. */
+int cg_hdr_histogram_device(cg_ctx *ctx, const float *d_pixels, int channels, size_t n_pixels, int n_frames,
+                            size_t frame_stride, uint32_t *d_hist, cg_hdr_stats *d_stats, void *stream);
+/* d_scales[f] = s_f of the n_frames histograms at d_hist.  d_prev (a device
+ * float, may be NULL) may point at an element of an earlier call's d_scales,
+ * this call's array included as long as it is not one of its n_frames outputs. */
+int cg_hdr_exposure_device(cg_ctx *ctx, const uint32_t *d_hist, int n_frames, const cg_hdr_exposure_params *params,
+                           const float *d_prev, float *d_scales, void *stream);
+/* d_argb[f * dst_stride + p] = PutPixelSDL(tone(op, c * d_scales[f])) of the
+ * CG_PIX_RGBA_F32 pixel d_rgba[f * src_stride + p], p < n_pixels (strides in
+ * pixels, 0: n_pixels); one launch for all frames, the scale read on the
+ * device.  LINEAR with a scale of exactly 1.0f gives cg_rt_render_device's
+ * frame bit for bit. */
+int cg_rt_tonemap_pack_device(cg_ctx *ctx, const float *d_rgba, size_t n_pixels, int n_frames, size_t src_stride,
+                              const float *d_scales, int op, float white2, uint32_t *d_argb, size_t dst_stride,
+                              void *stream);
+/* n_frames whole frames rendered, exposed and packed without a host wait:
+ * frame f as ARGB8888 at d_argb + f * frame_stride pixels (0: W * H) and its
+ * scale in d_scales[f] (device, n_frames floats, required).
+ * per_frame_lights 0: the frames of cg_rt_render_frames_device; 1: those of
+ * cg_rt_render_sequence_device, frame f lit by lights[f * n_lights ..].  The
+ * frames go in chunks of 8 through those calls as CG_PIX_RGBA_F32 into scratch
+ * the context owns (grow-only, 8 * W * H * 16 bytes), then histogram, exposure
+ * and pack per chunk.  Frame 0 of the call takes d_prev (device, may be NULL)
+ * as its previous scale, frame 0 of a later chunk d_scales[f - 1]: by the
+ * definition above such a frame shows that scale itself, so the chunk of 8 is
+ * part of what the call computes.  After the first call of a size it neither
+ * allocates nor waits for the device.  CG_E_NOSCENE before a scene is set. */
+int cg_rt_render_exposed_device(cg_ctx *ctx, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
+                                int n_frames, int per_frame_lights, const cg_hdr_exposure_params *params,
+                                const float *d_prev, int op, float white2, uint32_t *d_argb, size_t frame_stride,
+                                float *d_scales, void *stream);
+/* Host-memory form, synchronous: the same frames into argb + f * frame_stride
+ * pixels and the same scales into scales[n_frames] (both host memory; prev a
+ * host float or NULL); each chunk's download follows its render. */
+int cg_rt_render_exposed(cg_ctx *ctx, const cg_light *lights, int n_lights, const cg_rt_camera *cams, int n_frames,
+                         int per_frame_lights, const cg_hdr_exposure_params *params, const float *prev, int op,
+                         float white2, uint32_t *argb, size_t frame_stride, float *scales, cg_stats *stats);
+
 /* Frame assembly after a transfer of band shards: d_src holds n_blocks row
  * blocks in order, block b = n_frames x rows[b] rows of `width` pixels in
  * pix_format, landing at frame rows row0[b] .. row0[b] + rows[b] - 1 (rows
