@@ -228,6 +228,7 @@ _SIGS = {
     "cg_rt_probe_direct_light": (C.c_int, [P, C.POINTER(Isect), C.POINTER(Light), C.c_int,
                                            C.POINTER(Vec3)]),
     "cg_rt_probe_div3_device": (C.c_int, [P, P, C.c_int, P, P]),
+    "cg_rt_probe_rmag_device": (C.c_int, [P, C.c_int, P, P]),
     "cg_rast_load_test_model": (C.c_int, [C.POINTER(RTri), C.c_int, C.POINTER(C.c_int),
                                           C.POINTER(RTri), C.c_int, C.POINTER(C.c_int)]),
     "cg_rast_prepare": (C.c_int, [C.POINTER(RastParams), C.POINTER(RTri), C.c_int, C.POINTER(RTri),
@@ -684,6 +685,13 @@ def probe_div3_device(d_x, d_den, n, d_q, stream=None):
     (device pointers; asynchronous on `stream`)."""
     if load().cg_rt_probe_div3_device(P(d_x), P(d_den), n, P(d_q), P(stream) if stream else None) != CG_OK:
         raise RuntimeError("cg_rt_probe_div3_device failed")
+
+
+def probe_rmag_device(d_r, n, d_m, stream=None):
+    """cg_rt_probe_rmag_device: d_m[i] = the FP64 norm of the float triple d_r[3i .. 3i + 2], rounded
+    to float, as the one-light lattice kernels form it (device pointers; asynchronous on `stream`)."""
+    if load().cg_rt_probe_rmag_device(P(d_r), n, P(d_m), P(stream) if stream else None) != CG_OK:
+        raise RuntimeError("cg_rt_probe_rmag_device failed")
 
 
 def kernel_timing(enable: bool):

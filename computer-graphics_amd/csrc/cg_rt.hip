@@ -1057,11 +1057,19 @@ __device__ __forceinline__ vec3 lat_direct_light_tab(const RtFrame &Fs, const Rt
     const vec3 lp = v3(Fs.lights[0].x, Fs.lights[0].y, Fs.lights[0].z);
 #endif
     const vec3 r = lp - pos;                                            // :370
+#if CG_LAT_RMAG_INRANGE
+    const float rmag = light_rmag_inrange(r);                           // :371
+#else
     const float rmag = light_rmag(r);                                   // :371
+#endif
     const vec3 o = Tab::at(T.nrm, enc);                                 // :377-387
     const vec3 normal = enc < kLatSphSlot * Tab::kEnc ? o : normalize(pos - o);
     const vec3 origin = pos + normal * 0.00001f;                        // :394
+#if CG_LAT_ANYHIT_WAVE
+    if (shadowed_wave(Fs, tc, sph, origin, r, rmag, smask)) return v3(0.0f, 0.0f, 0.0f);    // :394-398
+#else
     if (shadowed<true>(Fs, tc, sph, origin, r, rmag, smask)) return v3(0.0f, 0.0f, 0.0f);   // :394-398
+#endif
     return direct_light_lit_chan(r, rmag, normal, Tab::at(T.lit, enc));
 }
 
@@ -2905,7 +2913,24 @@ __global__ void rt_probe_div3_kernel(const float *__restrict__ x, const float *_
     q[3 * i + 1] = r.y;
     q[3 * i + 2] = r.z;
 }
+// light_rmag_inrange on n float triples: the test of the hand-written FP64 root against
+// float(sqrt(double sum)) (tests/test_rt_rmag_gpu.py)
+__global__ void rt_probe_rmag_kernel(const float *__restrict__ r, int n, float *__restrict__ m)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    m[i] = light_rmag_inrange(v3(r[3 * i], r[3 * i + 1], r[3 * i + 2]));
+}
 }  // namespace cg
+
+extern "C" int cg_rt_probe_rmag_device(const float *d_r, int n, float *d_m, void *stream)
+{
+    if (n < 0 || n > INT_MAX / 3 || (n && (!d_r || !d_m))) return CG_E_INVALID;
+    if (n == 0) return CG_OK;
+    hipLaunchKernelGGL(cg::rt_probe_rmag_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_r, n,
+                       d_m);
+    return hipGetLastError() == hipSuccess ? CG_OK : CG_E_HIP;
+}
 
 extern "C" int cg_rt_probe_div3_device(const float *d_x, const float *d_den, int n, float *d_q, void *stream)
 {

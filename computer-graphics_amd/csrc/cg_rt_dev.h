@@ -1025,6 +1025,73 @@ __device__ __forceinline__ bool shadowed(const RtFrame &F, const RtTri *__restri
     return false;
 }
 
+// shadowed<true> for a caller whose candidate mask is wave-uniform (the one-light lattice kernels:
+// a chunk's mask comes from ballots), with wave-uniform control.  shadowed()'s `return true` inside
+// a loop with nested ifs makes the structuriser keep, per iteration, the masks of the lanes that
+// left, that go on and that take each if (27 scalar mask instructions and 4 branches around 81
+// vector ones, counted in rt_lattice_kernel<33>).  Here a lane keeps an `open` flag instead of
+// leaving, the loop is scalar, and each stage runs under one exec mask.  Per candidate k the t stage
+// runs for the lanes still open -- the lanes that are still inside shadowed()'s loop at k, since a
+// lane leaves that loop at its first hit and at nothing else -- and the u, v stage for those of
+// them whose distance passes :394-395's tests, as tri_shadow_hit orders them; the sphere tests
+// follow for the lanes no triangle blocked.  The (lane, candidate) tests, their float operations
+// and operands, and each lane's result are shadowed()'s for every input; the walk ends once no
+// lane is left open, as the other one ends when its last lane returns.  Measured with the FP64
+// root below: C2 +2.5 .. 3.1 %, alone +0.5 .. 1.3 % (profiles/r12_ab_issue.json).
+// Called with the lanes of the chunk that have a hit; the ballots see only those.
+#ifndef CG_LAT_ANYHIT_WAVE
+#define CG_LAT_ANYHIT_WAVE 1   // A/B: 0, the lattice shading calls shadowed<true>
+#endif
+__device__ __forceinline__ bool shadowed_wave(const RtFrame &F, const RtTri *__restrict__ tc,
+                                              const RtSphere *__restrict__ sph, vec3 start, vec3 d,
+                                              float rmag, unsigned long long mask)
+{
+    const vec3 nd = -d;
+    const float len = length(d);
+    cg_work(W_RAY_SH);
+    // a lane's state is an integer in a VGPR: a bool carried round a loop is a lane mask in SGPRs,
+    // merged under exec at every join (what makes the other walk dear)
+    int open = 1;                                      // this lane is not blocked yet
+    bool left = true;                                  // some lane is still open (uniform)
+    while (mask != 0ull) {
+        const RtTri &c = tc[__builtin_ctzll(mask)];
+        mask &= mask - 1ull;
+        if (open) {                                    // tri_shadow_hit's t stage
+            cg_work(W_T_SH);
+            const float sx = start.x - c.v0x, sy = start.y - c.v0y, sz = start.z - c.v0z;   // :296
+            const float Q2 = nd.y * c.e2z - c.e2y * nd.z;
+            const float Q1 = nd.y * c.e1z - c.e1y * nd.z;
+            const float det = (nd.x * c.K1 - c.e1x * Q2) + c.e2x * Q1;
+            const float K2 = sy * c.e2z - c.e2y * sz;
+            const float K4 = sy * c.e1z - c.e1y * sz;
+            const float detT = (sx * c.K1 - c.e1x * K2) + c.e2x * K4;          // det(s, e1, e2)
+            const float t = detT / det;
+            const float distance = t * len;
+            if (!(distance < 0.0f) && !(distance >= rmag || distance > FLT_MAX)) {   // its u, v stage
+                cg_work(W_UV_SH);
+                const float Q3 = nd.y * sz - sy * nd.z;
+                const float K3 = c.e1y * sz - sy * c.e1z;
+                const float detU = (nd.x * K2 - sx * Q2) + c.e2x * Q3;
+                const float detV = (nd.x * K3 - c.e1x * Q3) + sx * Q1;
+                const float u = detU / det;
+                const float v = detV / det;
+                open = ((u >= 0) && (v >= 0) && ((u + v) <= 1)) ? 0 : 1;
+            }
+        }
+        left = __ballot(open != 0) != 0ull;
+        if (!left) mask = 0ull;
+    }
+    for (int k = 0; k < F.n_sph && left; ++k) {
+        if (open) {
+            float t;
+            cg_work(W_SPH_SH);
+            open = (sphere_intersect(sph[k], start, d, t) && t < rmag) ? 0 : 1;
+        }
+        left = __ballot(open != 0) != 0ull;
+    }
+    return open == 0;
+}
+
 // x / d per channel (:412's three numerators over one area), bit for bit.  The
 // compiler's IEEE f32 division is v_div_scale (denominator), v_div_scale
 // (numerator, VCC), v_rcp, two refinement FMAs, v_mul, three FMAs, v_div_fmas,
@@ -1152,6 +1219,42 @@ __device__ __forceinline__ float light_rmag(vec3 r)
     double r0 = (double)r.x * (double)r.x, r1 = (double)r.y * (double)r.y,
            r2 = (double)r.z * (double)r.z;
     return (float)sqrt((r0 + r1) + r2);
+}
+// light_rmag for the one-light lattice kernels, bit for bit, in 18 FP64 instructions instead of
+// 27 (FP64 issues at half rate).  The compiler's sqrt(double) is
+//     s = x < 2^-767;  x' = ldexp(x, s ? 256 : 0);
+//     y = rsq(x'); g = x' * y; h = 0.5 * y; r = fma(-h, g, 0.5); g = fma(g, r, g); h = fma(h, r, h);
+//     d = fma(-g, g, x'); g = fma(d, h, g);  d = fma(-g, g, x'); g = fma(d, h, g);
+//     g = ldexp(g, s ? -128 : 0);  result = class(x', +-0 | +inf) ? x' : g
+// (v_cmp_gt_f64, two v_cndmask, two v_ldexp_f64 and their constants around v_rsq_f64 and the
+// Newton steps, read in this toolchain's listing of light_rmag; the form below compiles to exactly
+// the instructions between them).
+// 1. The scaling acts only for x < 2^-767.  Here x = (r0 + r1) + r2 with each r_k the exact
+//    double square of a float: +0, NaN, +inf, or at least (2^-149)^2 = 2^-298, and at most
+//    3 * 2^256; no sum of such terms lies in (0, 2^-298), so s is false for every input (a NaN
+//    compares false).
+// 2. So both ldexp are by 0, the identity on every double, NaN included: x' = x and g is unscaled.
+// 3. So every remaining instruction and operand is the compiler's -- rsq, the two multiplies, the
+//    seven FMAs and the final select of x itself for +0 and +inf (x is never -0: a sum of
+//    non-negative terms); NaN flows through the FMAs as it does there.
+#ifndef CG_LAT_RMAG_INRANGE
+#define CG_LAT_RMAG_INRANGE 1   // A/B: 0, the lattice shading calls light_rmag
+#endif
+__device__ __forceinline__ float light_rmag_inrange(vec3 r)
+{
+    const double r0 = (double)r.x * (double)r.x, r1 = (double)r.y * (double)r.y,
+                 r2 = (double)r.z * (double)r.z;
+    const double x = (r0 + r1) + r2;
+    const double y = __builtin_amdgcn_rsq(x);
+    double g = x * y, h = 0.5 * y;
+    const double e = __builtin_fma(-h, g, 0.5);
+    g = __builtin_fma(g, e, g);
+    h = __builtin_fma(h, e, h);
+    double d = __builtin_fma(-g, g, x);
+    g = __builtin_fma(d, h, g);
+    d = __builtin_fma(-g, g, x);
+    g = __builtin_fma(d, h, g);
+    return (float)((x == 0.0 || x == __builtin_inf()) ? x : g);
 }
 
 // DirectLight (skeleton.cpp:366-415) for a hit at `pos` on object `bi`.

@@ -455,6 +455,11 @@ int cg_rt_pick(cg_ctx *ctx, const cg_rt_camera *cam, int x, int y, int sub_ray, 
  * device arrays: d_q[3i + k] = d_x[3i + k] / d_den[i]; a test that they are
  * IEEE-exact. */
 int cg_rt_probe_div3_device(const float *d_x, const float *d_den, int n, float *d_q, void *stream);
+/* r_magnitude (:371), the FP64 norm of a float vector rounded to float, as the
+ * one-light lattice kernels form it (the compiler's sqrt(double) without its
+ * range scaling), on device arrays: d_m[i] = |(d_r[3i], d_r[3i + 1], d_r[3i + 2])|;
+ * a test that it is float(sqrt(double sum)) bit for bit. */
+int cg_rt_probe_rmag_device(const float *d_r, int n, float *d_m, void *stream);
 /* Test hook for large scenes (n_tris > 64): capacity of the device queue of
  * shadow rays the blocker hints leave to the certified lit search (0 = the
  * default, 65536).  Rays past the queue are searched per pixel by the shading

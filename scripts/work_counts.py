@@ -32,7 +32,7 @@ WEIGHTS = {"t_pri": 33, "uv_pri": 37, "sph_pri": 29, "ray_pri": 11, "t_sh": 33, 
 # the counters the dominant kernel of each workload owns (bench.py's roofline kernel): the lattice
 # kernels do the whole frame's per-ray work; C5's walk only the primary rays (its shadow rays are
 # the hints', the pending search's and the shading kernel's, its DirectLights the shading kernel's)
-DOMINANT = {"rt": ("rt_lattice_kernel", KINDS), "c4": ("rt_lattice_lights_kernel", KINDS),
+DOMINANT = {"rt": ("rt_lattice_kernel", KINDS), "yaw": ("rt_lattice_kernel", KINDS), "c4": ("rt_lattice_lights_kernel", KINDS),
             "c5": ("rt_big_primary_kernel", ("t_pri", "uv_pri", "sph_pri", "ray_pri"))}
 
 
@@ -73,6 +73,12 @@ def main():
         torch.cuda.synchronize()
         c = {k: v / 20 for k, v in read(lib).items()}
         res["workloads"]["rt"] = {"frames": 20, "counts_per_frame": c}
+        # C2 under bench.py's yaw (per-pixel columns, pitch 48): the same call
+        camy = cgamd.rt_camera(1920, 1080, 1080.0, R=cgamd.yaw_matrix(0.1745))
+        ctx.rt_render_frames_device([camy] * 20, out.data_ptr())
+        torch.cuda.synchronize()
+        c = {k: v / 20 for k, v in read(lib).items()}
+        res["workloads"]["yaw"] = {"frames": 20, "counts_per_frame": c}
         del out
         # C4: 3840x2160, 8x8 area light, one frame
         cam4 = cgamd.rt_camera(3840, 2160, 2160.0)
