@@ -1,0 +1,430 @@
+// cg_api_rt_host.hip -- raytracer frames delivered into host memory (cg_rt_render*, the HostFill
+// threads) and the exposure chain's entry points (cg_hdr_*, cg_rt_render_exposed*).  Host code only.
+#include <chrono>
+#include <cstdlib>
+
+#include "cg_ctx.h"
+#include "cg_hdr.h"
+
+// Host-memory form of a CG_PIX_RGBA_F32 frame: one frame call into the context's scratch frame,
+// then a download.
+extern "C" int cg_rt_render_radiance(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cam,
+                                     float *rgba, cg_stats *stats)
+{
+    if (!c || !rgba || !cam || cam->width <= 0 || cam->height <= 0) return CG_E_INVALID;
+    if (c->n_tris < 0) {
+        c->err = "render before cg_rt_set_scene";
+        return CG_E_NOSCENE;
+    }
+    auto t0 = std::chrono::steady_clock::now();
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    const size_t bytes = (size_t)cam->width * cam->height * 16;
+    CG_TRY(c, c->frame.ensure(bytes), "alloc frame");
+    CG_TRY(c, hipEventRecord(c->ev0, c->stream), "event");
+    cg_rt_shard whole{0, 1, cam->height, 0, cam->height, 0, 0};   // a band of exactly the frame's rows
+    if (int rc = cg_rt_render_frames_device(c, lights, n_lights, cam, 1, &whole, c->frame.p, 0, CG_PIX_RGBA_F32,
+                                            c->stream))
+        return rc;
+    CG_TRY(c, hipEventRecord(c->ev1, c->stream), "event");
+    CG_TRY(c, hipMemcpyAsync(rgba, c->frame.p, bytes, hipMemcpyDeviceToHost, c->stream), "download frame");
+    CG_TRY(c, hipStreamSynchronize(c->stream), "rt frame");
+    if (stats) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
+        stats->kernel_ms = ms;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->n_tris = c->n_tris;
+        stats->n_spans = 0;
+    }
+    return CG_OK;
+}
+
+// Host-buffer delivery of frames (cg_rt_render, cg_rt_render_frames): only the
+// columns the camera can see anything in (cg_rt_frame_columns, from the
+// scene's box) cross PCIe; the columns outside are certainly
+// PutPixelSDL(0, 0, 0) = 0x80000000 (no ray there can hit anything,
+// skeleton.cpp:160-166) and the host stores them itself while the GPU renders
+// and copies.  C2: columns 384-1551, 61 % of the bytes.  CG_DRAW_WINDOW=0:
+// whole rows (A/B runs).
+static bool draw_window_on()
+{
+    static const bool on = [] {
+        const char *e = std::getenv("CG_DRAW_WINDOW");
+        return !(e && e[0] == '0');
+    }();
+    return on;
+}
+// [c0, c1) of frame f's download; false: whole rows
+static bool draw_window(const cg_ctx *c, const cg_rt_camera *cam, int &c0, int &c1)
+{
+    c0 = 0;
+    c1 = cam->width;
+    if (!draw_window_on()) return false;
+    ctx_rt_columns(c, cam, &c0, &c1);
+    if (c1 <= c0) c0 = c1 = 0;   // nothing visible: a black frame, nothing to copy
+    return c0 > 0 || c1 < cam->width;
+}
+// frames of rows x W pixels (row pitch W): columns outside [c0, c1) black, on
+// the context's fill threads (CG_DRAW_THREADS, default min(8, cores / 2));
+// returns at once, HostFill::wait() before the frames are complete
+static HostFill *host_black_outside(cg_ctx *c, std::vector<HostFill::Frame> frames, int W, int rows, int c0, int c1)
+{
+    if (!c->hfill) {
+        const char *e = std::getenv("CG_DRAW_THREADS");
+        const int hw = (int)std::thread::hardware_concurrency();
+        const int n = e && *e ? std::atoi(e) : std::min(8, std::max(1, hw / 2));
+        c->hfill.reset(new HostFill(std::max(0, std::min(n, 64))));
+    }
+    c->hfill->run(std::move(frames), W, rows, c0, c1);
+    return c->hfill.get();
+}
+// D2H of frames [nf frames of W x H at src (pitch W, frame stride px)] into
+// dst (frame stride `stride`): the window's columns only (one pitched copy
+// when the frames are contiguous on both sides), or everything.
+static hipError_t download_frames(uint32_t *dst, size_t stride, const uint32_t *src, int W, int H, int nf, int c0,
+                                  int c1, bool window, hipStream_t st, size_t sstride = 0)
+{
+    // sstride: the source's frame stride in pixels (0 = W * H; more when the frames' rows pad to stripes)
+    const size_t px = sstride ? sstride : (size_t)W * H;
+    if (sstride && sstride != (size_t)W * H) {
+        for (int f = 0; f < nf; ++f) {
+            const hipError_t e = window
+                ? (c1 <= c0 ? hipSuccess
+                            : hipMemcpy2DAsync(dst + (size_t)f * stride + c0, (size_t)W * 4, src + (size_t)f * px + c0,
+                                               (size_t)W * 4, (size_t)(c1 - c0) * 4, H, hipMemcpyDeviceToHost, st))
+                : hipMemcpyAsync(dst + (size_t)f * stride, src + (size_t)f * px, (size_t)W * H * 4,
+                                 hipMemcpyDeviceToHost, st);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+    if (!window) {
+        if (stride == px) return hipMemcpyAsync(dst, src, (size_t)nf * px * 4, hipMemcpyDeviceToHost, st);
+        for (int f = 0; f < nf; ++f) {
+            const hipError_t e = hipMemcpyAsync(dst + (size_t)f * stride, src + (size_t)f * px, px * 4,
+                                                hipMemcpyDeviceToHost, st);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+    if (c1 <= c0) return hipSuccess;
+    if (stride == px)
+        return hipMemcpy2DAsync(dst + c0, (size_t)W * 4, src + c0, (size_t)W * 4, (size_t)(c1 - c0) * 4,
+                                (size_t)nf * H, hipMemcpyDeviceToHost, st);
+    for (int f = 0; f < nf; ++f) {
+        const hipError_t e = hipMemcpy2DAsync(dst + (size_t)f * stride + c0, (size_t)W * 4, src + (size_t)f * px + c0,
+                                              (size_t)W * 4, (size_t)(c1 - c0) * 4, H, hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// ---- auto-exposure and tone mapping (kernels: cg_hdr.hip; arithmetic: cg_hdr.h) ----
+extern "C" int cg_hdr_histogram_device(cg_ctx *c, const float *d_pixels, int channels, size_t n_pixels, int n_frames,
+                                       size_t frame_stride, uint32_t *d_hist, cg_hdr_stats *d_stats, void *stream)
+{
+    if (!c || n_frames < 0 || (channels != 3 && channels != 4) || n_pixels >= ((size_t)1 << 32)) return CG_E_INVALID;
+    if (n_frames == 0) return CG_OK;
+    const size_t stride = frame_stride ? frame_stride : n_pixels;
+    if (!d_hist || ((uintptr_t)d_hist & 15) || ((uintptr_t)d_stats & 3) || (n_pixels && !d_pixels) ||
+        ((uintptr_t)d_pixels & (channels == 4 ? 15 : 3)) || stride < n_pixels)
+        return CG_E_INVALID;
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    CG_TRY(c, launch_hdr_histogram(d_pixels, channels, n_pixels, n_frames, stride, d_hist, d_stats,
+                                   stream ? (hipStream_t)stream : c->stream),
+           "histogram launch");
+    return CG_OK;
+}
+
+extern "C" int cg_hdr_exposure_device(cg_ctx *c, const uint32_t *d_hist, int n_frames,
+                                      const cg_hdr_exposure_params *params, const float *d_prev, float *d_scales,
+                                      void *stream)
+{
+    if (!c || n_frames < 0 || !hdr_params_ok(params)) return CG_E_INVALID;
+    if (n_frames == 0) return CG_OK;
+    if (!d_hist || ((uintptr_t)d_hist & 15) || !d_scales || ((uintptr_t)d_scales & 3) || ((uintptr_t)d_prev & 3))
+        return CG_E_INVALID;
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    CG_TRY(c, launch_hdr_exposure(d_hist, n_frames, *params, d_prev, d_scales, stream ? (hipStream_t)stream : c->stream),
+           "exposure launch");
+    return CG_OK;
+}
+
+extern "C" int cg_rt_tonemap_pack_device(cg_ctx *c, const float *d_rgba, size_t n_pixels, int n_frames,
+                                         size_t src_stride, const float *d_scales, int op, float white2,
+                                         uint32_t *d_argb, size_t dst_stride, void *stream)
+{
+    if (!c || n_frames < 0 || !hdr_tone_ok(op, white2) || n_pixels >= ((size_t)1 << 32)) return CG_E_INVALID;
+    if (n_frames == 0) return CG_OK;
+    const size_t ss = src_stride ? src_stride : n_pixels, ds = dst_stride ? dst_stride : n_pixels;
+    if (!d_scales || ((uintptr_t)d_scales & 3) || (n_pixels && (!d_rgba || !d_argb)) || ((uintptr_t)d_rgba & 15) ||
+        ((uintptr_t)d_argb & 3) || ss < n_pixels || ds < n_pixels)
+        return CG_E_INVALID;
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    CG_TRY(c, launch_rt_tonemap_pack(d_rgba, n_pixels, n_frames, ss, d_scales, op, white2, d_argb, ds,
+                                     stream ? (hipStream_t)stream : c->stream),
+           "tonemap pack launch");
+    return CG_OK;
+}
+
+constexpr int kHdrChunkFrames = 8;   // frames of cg_rt_render_exposed_device's scratch
+
+// what both forms of cg_rt_render_exposed check before anything is enqueued
+static int rt_exposed_check(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams, int n_frames,
+                            const cg_hdr_exposure_params *params, int op, float white2, size_t frame_stride)
+{
+    if (!c || n_frames < 0 || (n_frames && !cams) || !hdr_params_ok(params) || !hdr_tone_ok(op, white2) ||
+        n_lights < 0 || n_lights > kMaxLights || (n_lights && !lights))
+        return CG_E_INVALID;
+    if (n_frames == 0) return CG_OK;
+    const int W = cams[0].width, H = cams[0].height;
+    if (W <= 0 || H <= 0 || (size_t)W * H >= ((size_t)1 << 32)) return CG_E_INVALID;
+    for (int f = 1; f < n_frames; ++f)
+        if (cams[f].width != W || cams[f].height != H) return CG_E_INVALID;
+    if (frame_stride && frame_stride < (size_t)W * H) return CG_E_INVALID;
+    if (c->n_tris < 0) {
+        c->err = "render before cg_rt_set_scene";
+        return CG_E_NOSCENE;
+    }
+    return CG_OK;
+}
+
+// Frames f0 .. f0 + nf - 1 (nf <= kHdrChunkFrames) of an exposed call: rendered as CG_PIX_RGBA_F32
+// into the context's scratch, then histogram, exposure (previous scale *d_prev) and pack, all on st.
+static int rt_exposed_chunk(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams, int f0, int nf,
+                            int per_frame_lights, const cg_hdr_exposure_params &params, const float *d_prev, int op,
+                            float white2, uint32_t *d_argb, size_t stride, float *d_scales, hipStream_t st)
+{
+    const int H = cams[0].height;
+    const size_t px = (size_t)cams[0].width * H;
+    CG_TRY(c, c->hdr_rgba.ensure(kHdrChunkFrames * px * 16), "alloc exposure frames");
+    CG_TRY(c, c->hdr_hist.ensure(kHdrChunkFrames * CG_HDR_BINS * sizeof(uint32_t)), "alloc exposure histograms");
+    cg_rt_shard whole{0, 1, H, 0, H, 0, 0};   // a band of exactly the frame's rows
+    const int rc = per_frame_lights
+        ? cg_rt_render_sequence_device(c, lights + (size_t)f0 * n_lights, n_lights, cams + f0, nf, &whole,
+                                       c->hdr_rgba.p, px, CG_PIX_RGBA_F32, st)
+        : cg_rt_render_frames_device(c, lights, n_lights, cams + f0, nf, &whole, c->hdr_rgba.p, px, CG_PIX_RGBA_F32, st);
+    if (rc) return rc;
+    const float *rgba = (const float *)c->hdr_rgba.p;
+    uint32_t *hist = (uint32_t *)c->hdr_hist.p;
+    CG_TRY(c, launch_hdr_histogram(rgba, 4, px, nf, px, hist, nullptr, st), "histogram launch");
+    CG_TRY(c, launch_hdr_exposure(hist, nf, params, d_prev, d_scales, st), "exposure launch");
+    CG_TRY(c, launch_rt_tonemap_pack(rgba, px, nf, px, d_scales, op, white2, d_argb, stride, st), "tonemap pack launch");
+    return CG_OK;
+}
+
+extern "C" int cg_rt_render_exposed_device(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
+                                           int n_frames, int per_frame_lights, const cg_hdr_exposure_params *params,
+                                           const float *d_prev, int op, float white2, uint32_t *d_argb,
+                                           size_t frame_stride, float *d_scales, void *stream)
+{
+    if (int rc = rt_exposed_check(c, lights, n_lights, cams, n_frames, params, op, white2, frame_stride)) return rc;
+    if (n_frames == 0) return CG_OK;
+    if (!d_argb || ((uintptr_t)d_argb & 3) || !d_scales || ((uintptr_t)d_scales & 3) || ((uintptr_t)d_prev & 3))
+        return CG_E_INVALID;
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const size_t stride = frame_stride ? frame_stride : (size_t)cams[0].width * cams[0].height;
+    for (int f0 = 0; f0 < n_frames; f0 += kHdrChunkFrames) {
+        const int nf = std::min(kHdrChunkFrames, n_frames - f0);
+        if (int rc = rt_exposed_chunk(c, lights, n_lights, cams, f0, nf, per_frame_lights, *params,
+                                      f0 ? d_scales + f0 - 1 : d_prev, op, white2, d_argb + (size_t)f0 * stride, stride,
+                                      d_scales + f0, st))
+            return rc;
+    }
+    return CG_OK;
+}
+
+// Host-memory form: the device form's chunks into context scratch, each chunk's frames downloaded
+// after its render; the scales (and the caller's previous scale) live in one device array,
+// [0] the previous scale, [1 + f] frame f's.
+extern "C" int cg_rt_render_exposed(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
+                                    int n_frames, int per_frame_lights, const cg_hdr_exposure_params *params,
+                                    const float *prev, int op, float white2, uint32_t *argb, size_t frame_stride,
+                                    float *scales, cg_stats *stats)
+{
+    if (int rc = rt_exposed_check(c, lights, n_lights, cams, n_frames, params, op, white2, frame_stride)) return rc;
+    if (n_frames == 0) return CG_OK;
+    if (!argb || !scales) return CG_E_INVALID;
+    auto t0 = std::chrono::steady_clock::now();
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    const size_t px = (size_t)cams[0].width * cams[0].height;
+    const size_t stride = frame_stride ? frame_stride : px;
+    CG_TRY(c, c->hdr_argb.ensure(kHdrChunkFrames * px * sizeof(uint32_t)), "alloc exposed frames");
+    CG_TRY(c, c->hdr_scales.ensure(((size_t)n_frames + 1) * sizeof(float)), "alloc scales");
+    float *d_s = (float *)c->hdr_scales.p;
+    uint32_t *d_a = (uint32_t *)c->hdr_argb.p;
+    if (prev) CG_TRY(c, hipMemcpyAsync(d_s, prev, sizeof(float), hipMemcpyHostToDevice, c->stream), "upload scale");
+    float ms_sum = 0.f;
+    for (int f0 = 0; f0 < n_frames; f0 += kHdrChunkFrames) {
+        const int nf = std::min(kHdrChunkFrames, n_frames - f0);
+        CG_TRY(c, hipEventRecord(c->ev0, c->stream), "event");
+        if (int rc = rt_exposed_chunk(c, lights, n_lights, cams, f0, nf, per_frame_lights, *params,
+                                      f0 || prev ? d_s + f0 : nullptr, op, white2, d_a, px, d_s + 1 + f0, c->stream))
+            return rc;
+        CG_TRY(c, hipEventRecord(c->ev1, c->stream), "event");
+        CG_TRY(c, download_frames(argb + (size_t)f0 * stride, stride, d_a, cams[0].width, cams[0].height, nf, 0,
+                                  cams[0].width, false, c->stream),
+               "download frames");
+        CG_TRY(c, hipStreamSynchronize(c->stream), "exposed frames");
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
+        ms_sum += ms;
+    }
+    CG_TRY(c, hipMemcpy(scales, d_s + 1, (size_t)n_frames * sizeof(float), hipMemcpyDeviceToHost), "download scales");
+    if (stats) {
+        stats->kernel_ms = ms_sum;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->n_tris = c->n_tris;
+        stats->n_spans = 0;
+    }
+    return CG_OK;
+}
+
+extern "C" int cg_rt_render(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cam,
+                            uint32_t *argb, cg_stats *stats)
+{
+    if (!c || !argb) return CG_E_INVALID;
+    auto t0 = std::chrono::steady_clock::now();
+    RtFrame F;
+    int rc = fill_frame(c, lights, n_lights, cam, nullptr, c->stream, F);
+    if (rc) return rc;
+    size_t bytes = (size_t)F.rows_out * F.W * sizeof(uint32_t);
+    CG_TRY(c, c->frame.ensure(bytes), "alloc frame");
+    CG_TRY(c, hipEventRecord(c->ev0, c->stream), "event");
+    rc = rt_enqueue(c, F, (uint32_t *)c->frame.p, c->stream);
+    if (rc) return rc;
+    CG_TRY(c, hipEventRecord(c->ev1, c->stream), "event");
+    int c0, c1;
+    const bool window = draw_window(c, cam, c0, c1);
+    // the black columns beside the render and the copy
+    HostFill *hf = window ? host_black_outside(c, {{argb}}, F.W, F.H, c0, c1) : nullptr;
+    const hipError_t e = download_frames(argb, (size_t)F.W * F.H, (const uint32_t *)c->frame.p, F.W, F.H, 1, c0, c1,
+                                         window, c->stream);
+    if (hf) hf->wait();
+    CG_TRY(c, e, "download frame");
+    CG_TRY(c, hipStreamSynchronize(c->stream), "rt frame");
+    if (stats) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
+        stats->kernel_ms = ms;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->n_tris = c->n_tris;
+        stats->n_spans = 0;
+    }
+    return CG_OK;
+}
+
+// n_frames frames into host memory: chunks of `chunk` frames render through
+// rt_render_frames into two device slots on the context's stream; each
+// chunk's download runs on `xfer` while the next chunk renders.  The download
+// of chunk j is issued after chunk j + 1's render is enqueued: a pageable
+// destination makes hipMemcpyAsync stage through the runtime's pinned buffers
+// and return only when the copy is done, so issued in the other order the
+// host would hold back the next render.
+static int rt_render_frames_host(cg_ctx *c, const cg_light *lights, int n_lights, int light_stride,
+                                 const cg_rt_camera *cams, int n_frames, uint32_t *argb, size_t frame_stride, int chunk,
+                                 cg_stats *stats);
+extern "C" int cg_rt_render_frames(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
+                                   int n_frames, uint32_t *argb, size_t frame_stride, int chunk, cg_stats *stats)
+{
+    return rt_render_frames_host(c, lights, n_lights, 0, cams, n_frames, argb, frame_stride, chunk, stats);
+}
+extern "C" int cg_rt_render_sequence(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
+                                     int n_frames, uint32_t *argb, size_t frame_stride, int chunk, cg_stats *stats)
+{
+    if (n_lights < 0 || n_lights > kMaxLights || (n_lights && !lights)) return CG_E_INVALID;
+    return rt_render_frames_host(c, lights, n_lights, std::max(n_lights, 1), cams, n_frames, argb, frame_stride, chunk,
+                                 stats);
+}
+// light_stride: 0 (common lights), else frame f's lights at lights + f * n_lights
+static int rt_render_frames_host(cg_ctx *c, const cg_light *lights, int n_lights, int light_stride,
+                                 const cg_rt_camera *cams, int n_frames, uint32_t *argb, size_t frame_stride, int chunk,
+                                 cg_stats *stats)
+{
+    if (!c || !argb || n_frames < 0 || (n_frames && !cams) || chunk < 0) return CG_E_INVALID;
+    if (n_frames == 0) return CG_OK;
+    auto t0 = std::chrono::steady_clock::now();
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    const int W = cams[0].width, H = cams[0].height;
+    if (W <= 0 || H <= 0) return CG_E_INVALID;
+    for (int f = 1; f < n_frames; ++f)   // the slots hold chunks of W x H frames
+        if (cams[f].width != W || cams[f].height != H) return CG_E_INVALID;
+    const size_t px = (size_t)W * H;
+    const size_t stride = frame_stride ? frame_stride : px;
+    if (stride < px) return CG_E_INVALID;
+    const int ch = chunk ? std::min(chunk, 64) : 8;
+    if (!c->xfer) {
+        CG_TRY(c, hipStreamCreateWithFlags(&c->xfer, hipStreamNonBlocking), "copy stream");
+        for (int k = 0; k < 2; ++k) {
+            CG_TRY(c, hipEventCreateWithFlags(&c->ev_rdone[k], hipEventDisableTiming), "copy event");
+            CG_TRY(c, hipEventCreateWithFlags(&c->ev_cdone[k], hipEventDisableTiming), "copy event");
+        }
+    }
+    // Every return below, error or not, leaves nothing of this call running:
+    // earlier chunks' downloads may still be writing into argb (asynchronous
+    // when it is pinned), and the stream may wait on their events.
+    struct Drain {
+        cg_ctx *c;
+        ~Drain()
+        {
+            if (c->hfill) c->hfill->wait();   // the host's black columns
+            (void)hipStreamSynchronize(c->xfer);
+            (void)hipStreamSynchronize(c->stream);
+        }
+    } drain_on_exit{c};
+    // a slot's frames: the whole frame's rows in device memory (H padded to its 8-row stripes)
+    const size_t spx = (size_t)cg_rt_shard_rows(H, nullptr) * W;
+    for (int k = 0; k < 2; ++k) CG_TRY(c, c->hslot[k].ensure((size_t)ch * spx * sizeof(uint32_t)), "alloc frame slots");
+    const int nchunks = (n_frames + ch - 1) / ch;
+    auto download = [&](int j) -> int {
+        const int s = j & 1, f0 = j * ch, nf = std::min(ch, n_frames - f0);
+        CG_TRY(c, hipStreamWaitEvent(c->xfer, c->ev_rdone[s], 0), "copy wait");
+        // the chunk's union window (cg_rt_render's delivery, above)
+        int a = W, b = 0;
+        bool window = true;
+        for (int f = f0; f < f0 + nf && window; ++f) {
+            int x0, x1;
+            window = draw_window(c, &cams[f], x0, x1);
+            if (x1 > x0) {
+                a = std::min(a, x0);
+                b = std::max(b, x1);
+            }
+        }
+        if (a >= b) a = b = 0;
+        if (window) {   // the fill threads beside the copy (a pageable copy returns only when done)
+            std::vector<HostFill::Frame> fr;
+            for (int f = f0; f < f0 + nf; ++f) fr.push_back({argb + (size_t)f * stride});
+            host_black_outside(c, std::move(fr), W, H, a, b);
+        }
+        CG_TRY(c, download_frames(argb + (size_t)f0 * stride, stride, (const uint32_t *)c->hslot[s].p, W, H, nf, a, b,
+                                  window, c->xfer, spx), "download frames");
+        CG_TRY(c, hipEventRecord(c->ev_cdone[s], c->xfer), "copy event");
+        return CG_OK;
+    };
+    CG_TRY(c, hipEventRecord(c->ev0, c->stream), "event");
+    for (int j = 0; j < nchunks; ++j) {
+        const int s = j & 1, f0 = j * ch, nf = std::min(ch, n_frames - f0);
+        if (j >= 2) CG_TRY(c, hipStreamWaitEvent(c->stream, c->ev_cdone[s], 0), "slot wait");   // chunk j - 2 downloaded
+        int rc = rt_render_frames(c, lights && light_stride ? lights + (size_t)f0 * n_lights : lights, n_lights,
+                                  cams + f0, nf, nullptr, c->hslot[s].p, spx, CG_PIX_ARGB8888, c->stream, nullptr, nullptr,
+                                  nullptr, 0, light_stride);
+        if (rc) return rc;
+        CG_TRY(c, hipEventRecord(c->ev_rdone[s], c->stream), "render event");
+        if (j >= 1 && (rc = download(j - 1))) return rc;
+    }
+    CG_TRY(c, hipEventRecord(c->ev1, c->stream), "event");
+    if (int rc = download(nchunks - 1)) return rc;
+    CG_TRY(c, hipStreamSynchronize(c->xfer), "download frames");
+    CG_TRY(c, hipStreamSynchronize(c->stream), "rt frames");
+    if (stats) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
+        stats->kernel_ms = ms;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->n_tris = c->n_tris;
+        stats->n_spans = 0;
+        stats->n_shaded = -1;
+    }
+    return CG_OK;
+}

@@ -1,0 +1,282 @@
+// cg_ctx.h -- struct cg_ctx and what it is made of, for cg_ctx.hip and the cg_api_*.hip files
+// alone: kernel files see the context through cg_host.h's accessors.
+#pragma once
+
+#include <algorithm>
+#include <atomic>
+#include <condition_variable>
+#include <memory>
+#include <mutex>
+#include <thread>
+
+#include "cg_host.h"
+#include "cg_rast_dev.h"
+#include "cg_rt_grid.h"
+
+using namespace cg;
+
+// Grow-only device buffer.
+struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    hipError_t ensure(size_t n)
+    {
+        if (n <= bytes) return hipSuccess;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+        hipError_t e = hipMalloc(&p, n);
+        if (e == hipSuccess) bytes = n;
+        return e;
+    }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+};
+
+// Host threads that store the certified-black columns of frames delivered
+// into host memory (cg_rt_render / cg_rt_render_frames): a frame's 3.2 MB of
+// black columns (C2) take one thread longer than the PCIe copy of its
+// window, so the rows are shared by the workers and the caller.  run() hands
+// out a job; wait() helps and returns when every row is stored.
+class HostFill {
+  public:
+    struct Frame {
+        uint32_t *dst;   // W x rows pixels, row pitch W
+    };
+    explicit HostFill(int n)
+    {
+        for (int i = 0; i < n; ++i) th_.emplace_back([this] { loop(); });
+    }
+    ~HostFill()
+    {
+        {
+            std::lock_guard<std::mutex> g(mu_);
+            quit_ = true;
+        }
+        cv_.notify_all();
+        for (auto &t : th_) t.join();
+    }
+    void run(std::vector<Frame> frames, int W, int rows, int c0, int c1)
+    {
+        wait();
+        {
+            std::lock_guard<std::mutex> g(mu_);
+            fr_ = std::move(frames);
+            W_ = W;
+            rows_ = rows;
+            c0_ = c0;
+            c1_ = c1;
+            total_ = (int)fr_.size() * rows;
+            next_.store(0);
+            busy_ = (int)th_.size();
+            ++gen_;
+        }
+        cv_.notify_all();
+    }
+    void wait()
+    {
+        work();
+        std::unique_lock<std::mutex> g(mu_);
+        done_.wait(g, [this] { return busy_ == 0; });
+    }
+
+  private:
+    static constexpr int kRowsPerGrab = 32;
+    void work()
+    {
+        for (;;) {
+            const int r0 = next_.fetch_add(kRowsPerGrab);
+            if (r0 >= total_) return;
+            const int r1 = std::min(total_, r0 + kRowsPerGrab);
+            for (int r = r0; r < r1; ++r) {
+                uint32_t *row = fr_[r / rows_].dst + (size_t)(r % rows_) * W_;
+                std::fill(row, row + c0_, 0x80000000u);   // PutPixelSDL(0, 0, 0)
+                std::fill(row + c1_, row + W_, 0x80000000u);
+            }
+        }
+    }
+    void loop()
+    {
+        unsigned seen = 0;
+        for (;;) {
+            {
+                std::unique_lock<std::mutex> g(mu_);
+                cv_.wait(g, [&] { return quit_ || gen_ != seen; });
+                if (quit_) return;
+                seen = gen_;
+            }
+            work();
+            std::lock_guard<std::mutex> g(mu_);
+            if (--busy_ == 0) done_.notify_all();
+        }
+    }
+    std::vector<std::thread> th_;
+    std::mutex mu_;
+    std::condition_variable cv_, done_;
+    bool quit_ = false;
+    unsigned gen_ = 0;
+    int busy_ = 0;
+    std::vector<Frame> fr_;
+    int W_ = 0, rows_ = 1, c0_ = 0, c1_ = 0, total_ = 0;
+    std::atomic<int> next_{0};
+};
+
+struct cg_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    std::string err;
+    // RT scene
+    int n_tris = -1, n_sph = 0;
+    float nbound = 0.f;   // largest |normal component| of the scene (shadow certificate)
+    DevBuf tris, geo, tc, shade, sph, frame, probe_a, probe_b, probe_c, probe_d, lights, big, gstart, gtris;
+    DevBuf latmask;                     // lattice tiles' certificates (two masks per tile)
+    DevBuf supmask;                     // their super-tiles' certificates (two-level path)
+    DevBuf umask;                       // light sets: the tiles' per-unit shadow masks
+    DevBuf objmask, pobj[2];            // one-light lattice: shadow masks per object (kObjSlots a tile), as latmask / plat
+    // the latest lattice call's certificates, for cg_rt_tile_masks (null: none since the scene changed)
+    struct {
+        const unsigned long long *lat = nullptr, *obj = nullptr;
+        int tiles_x = 0, tiles_y = 0, frames = 0;
+        int col0 = 0, col1 = 0;   // the tile columns the call certified (a windowed launch: its super-tiles')
+        hipStream_t st = nullptr;
+    } last_masks;
+    // how the latest batched lattice call was launched, for cg_rt_lattice_path
+    int last_path[4] = {0, 0, 0, 0};   // measured order, published certificates, forced uncertified, workgroups
+    // Batched lattice launches pipeline their certificate kernels on `aux`:
+    // call j+1's certificates run beside call j's lattice kernel, each call
+    // with its own slot of buffers (rt_enqueue_lattice_batch).
+    hipStream_t aux = nullptr;
+    hipEvent_t ev_cert[2] = {nullptr, nullptr}, ev_lat[2] = {nullptr, nullptr};
+    int slot = 0;
+    DevBuf ptc[2], plat[2], psup[2], pumask[2];
+    // measured lattice order (LatOrder, cg_internal.h): per slot, the recording
+    // of its last lattice launch (class per tile) and the order sorted for it
+    DevBuf lcost[2], lflat[2];
+    int umask_frames = 0;                            // light sets: frames the unit-mask slots are sized for
+    DevBuf pflag[2];                  // published-certificate words per slot (LatPublish / LatReady)
+    uint32_t cert_gen = 0u;           // generation of the latest published call
+    unsigned long long lrec_key[2] = {0ull, 0ull};   // geometry key of the slot's recording (0: none)
+    unsigned rt_scene_gen = 0;                       // cg_rt_set_scene count (part of the key)
+    // cg_rt_render_frames (host output): chunks render into two device slots
+    // and download on `xfer` while the next chunk renders
+    hipStream_t xfer = nullptr;
+    hipEvent_t ev_rdone[2] = {nullptr, nullptr}, ev_cdone[2] = {nullptr, nullptr};
+    DevBuf hslot[2];
+    // cg_rt_render_exposed_device: a chunk's CG_PIX_RGBA_F32 frames and histograms; the host form's
+    // chunk of ARGB frames, its scales and previous scale
+    DevBuf hdr_rgba, hdr_hist, hdr_argb, hdr_scales;
+    std::unique_ptr<HostFill> hfill;    // their black columns (created on first use)
+    RtGrid grid{};                      // large scenes only (n_tris > 64)
+    GridBuild gbuild;                   // cg_rt_set_scene_device: the device builder's scratch and counts
+    uint64_t grid_entries = 0;          // entries of the installed grid (either builder)
+    long long grid_cap_entries = 0, grid_cap_cands = 0;   // cg_rt_set_grid_caps (0 = default)
+    int pend_cap = 0;                   // cg_rt_set_pending_cap (0 = default)
+    // large-scene pools (cg_rt_big.hip): capacities in entries, sized on the
+    // scene's first frame, then grown from the demand later frames report
+    BigCaps big_caps{};
+    bool big_sized = false;
+    long long big_key = -1;                     // frame shape / path the pools were sized for
+    bool big_fixed = false;                     // cg_rt_set_pool_caps: capacities pinned (test hook)
+    unsigned long long *big_demand = nullptr;   // pinned [4]: the latest frame's demand
+    hipEvent_t big_ev = nullptr;
+    bool big_ev_live = false;
+    unsigned long long big_last[4] = {};
+    bool big_last_hits = false;                 // big_last came from a hits-only pass (its own capacities)
+    long long big_overflows = 0;
+    // Large scenes, several frames in flight (rt_render_frames): slots 1 ..
+    // kBigSlots - 1 with their own buffers, stream and demand read-back; slot 0
+    // is tc / shade / big / frame / big_demand / big_ev above.  A frame's list
+    // building and walks are latency-bound phases; independent frames fill
+    // each other's gaps.
+    static constexpr int kBigSlots = 4;
+    struct ExtraSlot {
+        DevBuf tc, big, frame;
+        unsigned long long *demand = nullptr;
+        hipEvent_t ev = nullptr, done = nullptr;
+        bool ev_live = false;
+        hipStream_t st = nullptr;
+    } xs[kBigSlots - 1];
+    hipEvent_t bev_start = nullptr;
+    // Hit planes (cg_rt_hits_device, cg_rt_pick).  A hits-only pass of a large scene has buffers of
+    // its own -- the pass's RtTri, scratch, demand read-back -- so it never touches what a frame in
+    // flight on another stream reads, and pool capacities and a sizing state of its own, so frames
+    // and hit planes that alternate do not size the pools again each time.
+    struct HitsSlot {
+        DevBuf tc, big, planes, pick;
+        BigCaps caps{};
+        bool sized = false;
+        long long key = -1;
+        unsigned long long *demand = nullptr;
+        hipEvent_t ev = nullptr;
+        bool ev_live = false;
+    } hits;
+    // the scene's box (rt_scene_box, once per cg_rt_set_scene): cg_dist's column
+    // window of any camera from it in O(1) per frame -- no per-camera pass over
+    // the scene (1M triangles: ~6 ms on the host) and no per-camera cache
+    double box_lo[3] = {1e300, 1e300, 1e300}, box_hi[3] = {-1e300, -1e300, -1e300};
+    std::vector<RtLight> lights_host;   // what `lights` holds (re-uploaded only on change)
+    // Frame sequences (cg_rt_render_sequence_device): a call's n_frames x n_lights lights and its
+    // RtFrameRec table, uploaded once through pinned staging memory into one of two slots, so that
+    // two calls queued back to back read their own (ev_lat's discipline): `up` after the slot's
+    // upload (the staging memory is free again), `done` after the call's last kernel (the device
+    // copy is).  Both slots grow together, so only the first call of a size allocates.
+    struct SeqSlot {
+        DevBuf dev;
+        void *host = nullptr;
+        size_t host_bytes = 0;
+        hipEvent_t up = nullptr, done = nullptr;
+    } seq[2];
+    int seq_slot = 0;
+    // RAST scratch (owned by cg_rast.hip)
+    DevBuf rtris, rhdr, rspan, rpix, rargb, rdepth, rshadow, rcount, rrecs, rgeo, rroom, rboxes;
+    DevBuf rpc, rtl, rrnd, rjt;          // colour modes 1-2 (cg_rast_colour.hip)
+    DevBuf rbig[15];                     // the compact route's own buffers (cg_rast_big.hip)
+    int rast_route = -1;                 // cg_rast_set_route: -1 automatic, else the forced route
+    long long route_limit = 0;           // cg_rast_set_route_limit: 0 = cg_rast_route's 131072
+    RastLast rlast;                      // the latest rasteriser frame (cg_rast_scratch_info)
+    // cg_rast_draw_buffers*, cg_rast_pick (cg_rast_buffers.hip): what the latest frame left in
+    // scratch, whether a buffers call is running it, and the calls' own buffers (kBufOwner ..)
+    RastFrame rframe;
+    bool rast_want_owner = false;
+    DevBuf rbuf[9];
+    // cg_rast_draw_sequence_device: the generator's tables (windows, seed words, J_b for
+    // rseq_chunks chunks) and the stream's capacity in fragments (0: 4 * W * H)
+    DevBuf rseq;
+    long long rseq_chunks = 0, rand_cap = 0;
+    // cg_rast_draw_sequence (host output): two sets of plane slots of `chunk` frames (downloaded on
+    // `xfer` as hslot is, with events of their own), the call's n_frames + 1 device records, and their
+    // pinned host copy followed by one int for the last frame's clipped count
+    static constexpr int kRastHostSlots = 2;
+    DevBuf rs_argb[kRastHostSlots], rs_depth[kRastHostSlots], rs_shadow[kRastHostSlots], rs_info;
+    hipEvent_t rs_rdone[kRastHostSlots] = {}, rs_cdone[kRastHostSlots] = {};
+    void *rs_host = nullptr;
+    size_t rs_host_bytes = 0;
+    DevBuf sstars, sframe;               // starfield (cg_starfield.hip)
+    StarState star;                      // resident stars and frame runs (cg_starfield.hip)
+    DevBuf iscratch;                     // JPEG decode (cg_image.hip)
+    int n_room = -1, n_boxes = 0;
+    int scene_tex = 0;                   // bit k: the uploaded room/boxes carry texture k
+    // texture modes 1-3 (cg_rast_set_textures): device copies of the maps
+    DevBuf tmarble, tnoise, twoven, twoven_ao, twoven_op, twoven_nrm, tgrill, tgrill_op, tgrill_nrm, rtexel;
+    int tex_loaded = 0;                  // bit k: texture k renderable
+    cg_ctx *tex_owner = nullptr;         // a lane reads its parent's maps
+    // cg_rast_draw_frames_device: frames overlap on `lanes` (child contexts,
+    // each with its own stream and scratch; scene copied device to device)
+    static constexpr int kRastLanes = 8;
+    cg_ctx *lanes[kRastLanes] = {};
+    hipEvent_t lane_ev[kRastLanes] = {};
+    hipEvent_t seq_ev[kRastLanes] = {};   // cg_rast_draw_sequence_device: a lane's latest chain step
+    hipEvent_t start_ev = nullptr;
+    unsigned scene_gen = 0, lane_gen[kRastLanes] = {};
+};
+
+// cg_api_rt.hip's, called by cg_api_rt_host.hip too: a frame's RtFrame from the caller's arguments
+// (lights uploaded on st), and its kernels enqueued on st
+int fill_frame(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cam, const cg_rt_shard *shard,
+               hipStream_t st, RtFrame &F);
+int rt_enqueue(cg_ctx *c, const RtFrame &Fin, void *d_out_v, hipStream_t st, int slot = 0);

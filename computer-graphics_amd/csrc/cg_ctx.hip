@@ -1,0 +1,200 @@
+// cg_ctx.hip -- the context behind the extern "C" boundary (include/cg_render.h): creation,
+// destruction, error text and the accessors the kernel files use.  Nothing throws across the
+// ABI; HIP failures become CG_E_HIP with the HIP message kept for cg_last_error().
+#include "cg_ctx.h"
+
+namespace cg {
+int ctx_device(const cg_ctx *c) { return c->device; }
+hipStream_t ctx_stream(const cg_ctx *c) { return c->stream; }
+void ctx_set_error(cg_ctx *c, const std::string &e) { c->err = e; }
+// cg_rt_frame_columns over the context's scene (the full width without one)
+void ctx_rt_columns(const cg_ctx *c, const cg_rt_camera *cam, int *c0, int *c1)
+{
+    *c0 = 0;
+    *c1 = cam->width;
+    if (c->n_tris >= 0 && cam->width > 0) rt_box_columns(c->box_lo, c->box_hi, cam, c0, c1);
+}
+// exposed to the rasteriser's, the starfield's and the image decoder's files: slot `which`
+// (kBuf*, cg_host.h) grown to at least `bytes`
+void *ctx_buf(cg_ctx *c, int which, size_t bytes, hipError_t *e)
+{
+    static DevBuf cg_ctx::*const fields[] = {
+        &cg_ctx::rtris, &cg_ctx::rhdr,   &cg_ctx::rspan,  &cg_ctx::rpix,   &cg_ctx::rargb,    &cg_ctx::rdepth, &cg_ctx::rshadow,
+        &cg_ctx::rcount, &cg_ctx::rrecs, &cg_ctx::rgeo,   &cg_ctx::rpc,    &cg_ctx::rtl,      &cg_ctx::rrnd,   &cg_ctx::rjt,
+        &cg_ctx::sstars, &cg_ctx::sframe, &cg_ctx::rtexel, &cg_ctx::iscratch, &cg_ctx::rseq};
+    static_assert(sizeof(fields) / sizeof(fields[0]) == kBufFieldsEnd && kBufFieldsEnd <= kBufBig0, "named slots");
+    static_assert(sizeof(c->rbig) / sizeof(c->rbig[0]) == kBufBigEnd - kBufBig0 && kBufBigEnd <= kBufOwner, "rbig slots");
+    static_assert(sizeof(c->rbuf) / sizeof(c->rbuf[0]) == kBufOwnerEnd - kBufOwner, "rbuf slots");
+    DevBuf *b = nullptr;
+    if (which >= 0 && which < kBufFieldsEnd) b = &(c->*fields[which]);
+    else if (which >= kBufBig0 && which < kBufBigEnd) b = &c->rbig[which - kBufBig0];
+    else if (which >= kBufOwner && which < kBufOwnerEnd) b = &c->rbuf[which - kBufOwner];
+    if (!b) {
+        *e = hipErrorInvalidValue;
+        return nullptr;
+    }
+    *e = b->ensure(bytes);
+    return *e == hipSuccess ? b->p : nullptr;
+}
+StarState *ctx_star(cg_ctx *c) { return &c->star; }
+int ctx_invalid(cg_ctx *c, const char *what)
+{
+    c->err = what;
+    return CG_E_INVALID;
+}
+int ctx_fail(cg_ctx *c, hipError_t e, const char *what)
+{
+    c->err = std::string(what) + ": " + hipGetErrorString(e);
+    return CG_E_HIP;
+}
+void ctx_events(cg_ctx *c, hipEvent_t *a, hipEvent_t *b)
+{
+    *a = c->ev0;
+    *b = c->ev1;
+}
+void rast_release(cg_ctx *c)
+{
+    c->rtris.release(); c->rhdr.release(); c->rspan.release(); c->rpix.release();
+    c->rargb.release(); c->rdepth.release(); c->rshadow.release(); c->rcount.release();
+    c->rrecs.release(); c->rgeo.release(); c->rroom.release(); c->rboxes.release();
+    c->rpc.release(); c->rtl.release(); c->rrnd.release(); c->rjt.release();
+    c->rseq.release();
+    for (DevBuf &b : c->rbig) b.release();
+    for (DevBuf &b : c->rbuf) b.release();
+    c->rframe = RastFrame{};
+    c->sstars.release(); c->sframe.release();
+    c->tmarble.release(); c->tnoise.release(); c->twoven.release(); c->twoven_ao.release();
+    c->twoven_op.release(); c->twoven_nrm.release(); c->tgrill.release(); c->tgrill_op.release();
+    c->tgrill_nrm.release(); c->rtexel.release();
+}
+int ctx_rast_route(cg_ctx *c, long long cap)
+{
+    if (c->rast_route >= 0) return c->rast_route;
+    if (c->route_limit > 0) return cap <= c->route_limit ? CG_RAST_ROUTE_DENSE : CG_RAST_ROUTE_COMPACT;
+    return cg_rast_route(cap);
+}
+bool ctx_rast_forced_compact(cg_ctx *c) { return c->rast_route == CG_RAST_ROUTE_COMPACT; }
+RastLast *ctx_rast_last(cg_ctx *c) { return &c->rlast; }
+RastFrame *ctx_rast_frame(cg_ctx *c) { return &c->rframe; }
+bool ctx_rast_want_owner(cg_ctx *c) { return c->rast_want_owner; }
+// the device texture maps and which textures are renderable (bit k: texture k)
+int rast_tex_maps(cg_ctx *c, RastTexMaps *m)
+{
+    if (c->tex_owner) c = c->tex_owner;
+    m->marble = (const uint8_t *)c->tmarble.p;
+    m->marble_noise = (const float *)c->tnoise.p;
+    m->woven = (const uint8_t *)c->twoven.p;
+    m->woven_ao = (const uint8_t *)c->twoven_ao.p;
+    m->woven_op = (const uint8_t *)c->twoven_op.p;
+    m->woven_nrm = (const uint8_t *)c->twoven_nrm.p;
+    m->grill = (const uint8_t *)c->tgrill.p;
+    m->grill_op = (const uint8_t *)c->tgrill_op.p;
+    m->grill_nrm = (const uint8_t *)c->tgrill_nrm.p;
+    return c->tex_loaded;
+}
+}  // namespace cg
+
+extern "C" int cg_device_count(void)
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+    return n;
+}
+
+extern "C" int cg_create(int device, cg_ctx **out)
+{
+    if (!out) return CG_E_INVALID;
+    *out = nullptr;
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return CG_E_NODEVICE;
+    if (device < 0 || device >= n) return CG_E_INVALID;
+    if (hipSetDevice(device) != hipSuccess) return CG_E_NODEVICE;
+    cg_ctx *c = new (std::nothrow) cg_ctx;
+    if (!c) return CG_E_INVALID;
+    c->device = device;
+    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) {
+        delete c;
+        return CG_E_HIP;
+    }
+    *out = c;
+    return CG_OK;
+}
+
+extern "C" void cg_destroy(cg_ctx *c)
+{
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    DevBuf *bufs[] = {&c->tris, &c->geo, &c->tc, &c->shade, &c->sph, &c->frame,
+                      &c->probe_a, &c->probe_b, &c->probe_c, &c->probe_d, &c->lights, &c->big,
+                      &c->gstart, &c->gtris, &c->objmask};
+    if (c->big_ev) {
+        (void)hipEventSynchronize(c->big_ev);
+        (void)hipEventDestroy(c->big_ev);
+    }
+    for (DevBuf *b : bufs) b->release();
+    if (c->big_demand) (void)hipHostFree(c->big_demand);
+    for (auto &x : c->xs) {
+        if (x.st) (void)hipStreamSynchronize(x.st);
+        if (x.ev) {
+            (void)hipEventSynchronize(x.ev);
+            (void)hipEventDestroy(x.ev);
+        }
+        if (x.done) (void)hipEventDestroy(x.done);
+        if (x.demand) (void)hipHostFree(x.demand);
+        x.tc.release(); x.big.release(); x.frame.release();
+        if (x.st) (void)hipStreamDestroy(x.st);
+    }
+    if (c->bev_start) (void)hipEventDestroy(c->bev_start);
+    if (c->hits.ev) {
+        (void)hipEventSynchronize(c->hits.ev);
+        (void)hipEventDestroy(c->hits.ev);
+    }
+    if (c->hits.demand) (void)hipHostFree(c->hits.demand);
+    c->hits.tc.release(); c->hits.big.release(); c->hits.planes.release(); c->hits.pick.release();
+    if (c->aux) (void)hipStreamSynchronize(c->aux);
+    for (int k = 0; k < cg_ctx::kRastLanes; ++k) {
+        if (c->lanes[k]) cg_destroy(c->lanes[k]);
+        if (c->lane_ev[k]) (void)hipEventDestroy(c->lane_ev[k]);
+        if (c->seq_ev[k]) (void)hipEventDestroy(c->seq_ev[k]);
+    }
+    if (c->start_ev) (void)hipEventDestroy(c->start_ev);
+    for (int k = 0; k < 2; ++k) {
+        c->ptc[k].release(); c->plat[k].release(); c->pflag[k].release(); c->psup[k].release();
+        c->pumask[k].release(); c->pobj[k].release();
+        if (c->ev_cert[k]) (void)hipEventDestroy(c->ev_cert[k]);
+        if (c->ev_lat[k]) (void)hipEventDestroy(c->ev_lat[k]);
+    }
+    if (c->aux) (void)hipStreamDestroy(c->aux);
+    if (c->xfer) (void)hipStreamSynchronize(c->xfer);
+    for (int k = 0; k < 2; ++k) {
+        c->hslot[k].release();
+        if (c->ev_rdone[k]) (void)hipEventDestroy(c->ev_rdone[k]);
+        if (c->ev_cdone[k]) (void)hipEventDestroy(c->ev_cdone[k]);
+    }
+    if (c->xfer) (void)hipStreamDestroy(c->xfer);
+    c->hdr_rgba.release(); c->hdr_hist.release(); c->hdr_argb.release(); c->hdr_scales.release();
+    c->rs_info.release();
+    for (int k = 0; k < cg_ctx::kRastHostSlots; ++k) {
+        c->rs_argb[k].release(); c->rs_depth[k].release(); c->rs_shadow[k].release();
+        if (c->rs_rdone[k]) (void)hipEventDestroy(c->rs_rdone[k]);
+        if (c->rs_cdone[k]) (void)hipEventDestroy(c->rs_cdone[k]);
+    }
+    if (c->rs_host) (void)hipHostFree(c->rs_host);
+    for (auto &q : c->seq) {
+        q.dev.release();
+        if (q.host) (void)hipHostFree(q.host);
+        if (q.up) (void)hipEventDestroy(q.up);
+        if (q.done) (void)hipEventDestroy(q.done);
+    }
+    rt_grid_release(c->gbuild);
+    rast_release(c);
+    star_release(&c->star);
+    if (c->ev0) (void)hipEventDestroy(c->ev0);
+    if (c->ev1) (void)hipEventDestroy(c->ev1);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
+    delete c;
+}
+
+extern "C" const char *cg_last_error(const cg_ctx *c) { return c ? c->err.c_str() : "no context"; }

@@ -47,17 +47,7 @@
 #include <thread>
 #include <vector>
 
-#include "cg_internal.h"
-
-namespace cg {
-int rt_render_frames(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams, int n_frames,
-                     const cg_rt_shard *shard, void *d_out, size_t frame_stride, int pix_format, void *stream,
-                     uint32_t *d_done, uint32_t *target, const int *group_starts, int ngroups, int light_stride);
-int ctx_device(const cg_ctx *c);
-hipStream_t ctx_stream(const cg_ctx *c);
-void ctx_set_error(cg_ctx *c, const std::string &e);
-void ctx_rt_columns(const cg_ctx *c, const cg_rt_camera *cam, int *c0, int *c1);
-}  // namespace cg
+#include "cg_host.h"
 
 using namespace cg;
 

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "cg_geom.h"
+#include "cg_host.h"
 
 namespace cg {
 

@@ -5,7 +5,7 @@
 #include <cstdlib>
 
 #include "cg_hdr.h"
-#include "cg_internal.h"
+#include "cg_host.h"
 
 namespace cg {
 

@@ -26,15 +26,7 @@
 #include <string>
 #include <vector>
 
-#include "cg_internal.h"
-
-namespace cg {
-void *ctx_buf(cg_ctx *c, int which, size_t bytes, hipError_t *e);
-hipStream_t ctx_stream(cg_ctx *c);
-int ctx_invalid(cg_ctx *c, const char *what);
-int ctx_fail(cg_ctx *c, hipError_t e, const char *what);
-int ctx_device(cg_ctx *c);
-}  // namespace cg
+#include "cg_host.h"
 
 namespace {
 
@@ -699,7 +691,7 @@ int decode_into(cg_ctx *c, const uint8_t *data, size_t n, uint8_t *d_out, size_t
     coef_bytes = (coef_bytes + 255) & ~(size_t)255;
     const size_t need = coef_bytes + plane_bytes * f.ncomp + (to_host ? out_bytes : 0);
     hipError_t e = hipSuccess;
-    uint8_t *scratch = static_cast<uint8_t *>(ctx_buf(c, 17, need, &e));
+    uint8_t *scratch = static_cast<uint8_t *>(ctx_buf(c, kBufImage, need, &e));
     if (!scratch) return ctx_fail(c, e, "jpeg scratch");
     for (int i = 0; i < f.ncomp; ++i)
         if ((e = hipMemcpyAsync(scratch + coef_off[i], f.comp[i].coef.data(), f.comp[i].coef.size() * 2,

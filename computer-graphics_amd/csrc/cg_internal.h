@@ -1,4 +1,4 @@
-// cg_internal.h -- device-side data layouts shared by the shim and kernels.
+// cg_internal.h -- device-side data layouts shared by the host code and the kernels.
 #pragma once
 
 #include <hip/hip_ext.h>

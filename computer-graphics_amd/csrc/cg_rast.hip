@@ -26,14 +26,10 @@
 #include <float.h>
 #include <limits.h>
 
+#include "cg_host.h"
 #include "cg_rast_dev.h"
 
 namespace cg {
-
-void *ctx_buf(cg_ctx *c, int which, size_t bytes, hipError_t *e);
-int ctx_fail(cg_ctx *c, hipError_t e, const char *what);
-int ctx_invalid(cg_ctx *c, const char *what);
-void ctx_events(cg_ctx *c, hipEvent_t *a, hipEvent_t *b);
 
 constexpr int kSetupPreChunks = 16;  // input triangles counted in one round trip: < 64 * 16
 
@@ -622,18 +618,6 @@ void launch_rast_post_direct(const RastArgs &A, const float4 *state, const int32
                        (const int32_t *)nullptr);
 }
 
-int rast_colour_fill(cg_ctx *c, const RastArgs &A, const cg_rast_params *p, const RowRec *recs, const int *count,
-                     const RastHdr *hdr, const int *n_dev, int max_recs, float4 *state, float *d_depth,
-                     int32_t *shadow, hipStream_t st, long long *n_shaded);
-int rast_seq_colour_fill(cg_ctx *c, const RastArgs &A, const cg_rast_params *p, const RowRec *recs, const int *count,
-                         const RastHdr *hdr, const int *n_dev, int max_recs, float4 *state, float *d_depth,
-                         int32_t *shadow, hipStream_t st, const RastSeq &q);
-int rast_seq_chain_mode0(cg_ctx *c, hipStream_t st, const RastSeq &q);
-
-hipError_t launch_rast_clip(const cg_rast_params &prm, const cg_rtri *d_room, int n_room, const cg_rtri *d_boxes,
-                            int n_boxes, cg_rtri *d_stage, int *d_counts, cg_vec4 *d_light, int *d_first,
-                            hipStream_t st);
-
 // The fill + post pipeline.  Either the triangle count is known on the host
 // (n_dev == nullptr, n = count) or it lives on the device (n_dev, n = capacity,
 // light read from d_light).
@@ -647,9 +631,6 @@ static int rast_pipeline(cg_ctx *c, cg_rtri *d_tris, int n, int *n_dev, const cg
                          cg_vec4 light, const cg_vec4 *d_light, uint32_t *d_argb, float *d_depth,
                          int32_t *d_shadow, hipStream_t st, cg_stats *stats, bool events_open, int tex_mask,
                          RastStage sg, const RastSeq *seq = nullptr);
-int rast_tex_maps(cg_ctx *c, RastTexMaps *m);
-int rast_make_args(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *p, cg_vec4 light,
-                   const cg_vec4 *d_light, int tex_mask, RastArgs *out);
 
 // glm::inverse for mat4 (glm/detail/type_mat4x4.inl:37-90), column-major
 // m[4c + r] = m[c][r]: findU / findV's inverse(R) (skeleton.cpp:1762).
@@ -750,11 +731,11 @@ int rast_draw_device(cg_ctx *c, const cg_rtri *d_room, int n_room, const cg_rtri
     const int cap = n_in > 0 ? 32 * n_in : 1;
     hipError_t e;
     // the clipped list, then each input triangle's staged survivors (32 each)
-    cg_rtri *tris = (cg_rtri *)ctx_buf(c, 0, ((size_t)cap + 32 * (size_t)n_in) * sizeof(cg_rtri), &e);
+    cg_rtri *tris = (cg_rtri *)ctx_buf(c, kBufTris, ((size_t)cap + 32 * (size_t)n_in) * sizeof(cg_rtri), &e);
     if (!tris) return ctx_fail(c, e, "alloc clipped triangles");
-    int *geo = (int *)ctx_buf(c, 9, 64 + 4 * (size_t)n_in, &e);   // [0] count, [4..7] light, [16..] counts
+    int *geo = (int *)ctx_buf(c, kBufGeo, 64 + 4 * (size_t)n_in, &e);   // [0] count, [4..7] light, [16..] counts
     if (!geo) return ctx_fail(c, e, "alloc geometry header");
-    int *misc = (int *)ctx_buf(c, 7, ((size_t)p->height + 16) * sizeof(int), &e);   // count[H] | first_tri
+    int *misc = (int *)ctx_buf(c, kBufCount, ((size_t)p->height + 16) * sizeof(int), &e);   // count[H] | first_tri
     if (!misc) return ctx_fail(c, e, "alloc counts");
     hipEvent_t e0, e1;
     ctx_events(c, &e0, &e1);
@@ -777,21 +758,21 @@ static int rast_pipeline(cg_ctx *c, cg_rtri *d_tris, int n, int *n_dev, const cg
     const size_t npx = (size_t)W * H;
     const int nn = n > 0 ? n : 1;
     hipError_t e;
-    RastSpan *spans = (RastSpan *)ctx_buf(c, 2, (size_t)nn * H * sizeof(RastSpan), &e);
+    RastSpan *spans = (RastSpan *)ctx_buf(c, kBufSpan, (size_t)nn * H * sizeof(RastSpan), &e);
     if (!spans) return ctx_fail(c, e, "alloc spans");
-    RastHdr *hdr = (RastHdr *)ctx_buf(c, 1, (size_t)nn * sizeof(RastHdr), &e);
+    RastHdr *hdr = (RastHdr *)ctx_buf(c, kBufHdr, (size_t)nn * sizeof(RastHdr), &e);
     if (!hdr) return ctx_fail(c, e, "alloc hdr");
     // fill -> post state: 4 B/pixel in colour mode 0, the colour fill's 16 B in modes 1-2
-    void *state = ctx_buf(c, 3, npx * (p->colour_mode == 0 ? sizeof(uint32_t) : sizeof(float4)), &e);
+    void *state = ctx_buf(c, kBufPix, npx * (p->colour_mode == 0 ? sizeof(uint32_t) : sizeof(float4)), &e);
     if (!state) return ctx_fail(c, e, "alloc state");
-    int *misc = (int *)ctx_buf(c, 7, ((size_t)H + 16) * sizeof(int), &e);   // count[H] | first_tri
+    int *misc = (int *)ctx_buf(c, kBufCount, ((size_t)H + 16) * sizeof(int), &e);   // count[H] | first_tri
     if (!misc) return ctx_fail(c, e, "alloc counts");
     int *count = misc, *first_tri = misc + H;
-    RowRec *recs = (RowRec *)ctx_buf(c, 8, (size_t)H * nn * sizeof(RowRec), &e);
+    RowRec *recs = (RowRec *)ctx_buf(c, kBufRecs, (size_t)H * nn * sizeof(RowRec), &e);
     if (!recs) return ctx_fail(c, e, "alloc row records");
     int32_t *shadow = d_shadow;   // mode 0 carries the marks in the state; modes 1-2 need the plane
     if (!shadow && p->colour_mode != 0) {
-        shadow = (int32_t *)ctx_buf(c, 6, npx * sizeof(int32_t), &e);
+        shadow = (int32_t *)ctx_buf(c, kBufShadow, npx * sizeof(int32_t), &e);
         if (!shadow) return ctx_fail(c, e, "alloc shadow");
     }
     RastArgs A;

@@ -49,24 +49,10 @@
 // Every store is bounded by its buffer's capacity; no kernel waits on another.
 #include <algorithm>
 
+#include "cg_host.h"
 #include "cg_rast_dev.h"
 
 namespace cg {
-
-void *ctx_buf(cg_ctx *c, int which, size_t bytes, hipError_t *e);
-int ctx_fail(cg_ctx *c, hipError_t e, const char *what);
-int ctx_invalid(cg_ctx *c, const char *what);
-void ctx_events(cg_ctx *c, hipEvent_t *a, hipEvent_t *b);
-hipError_t launch_rast_clip(const cg_rast_params &prm, const cg_rtri *d_room, int n_room, const cg_rtri *d_boxes,
-                            int n_boxes, cg_rtri *d_stage, int *d_counts, cg_vec4 *d_light, int *d_first,
-                            hipStream_t st);
-int rast_make_args(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *p, cg_vec4 light,
-                   const cg_vec4 *d_light, int tex_mask, RastArgs *out);
-int rast_seq_chain_mode0(cg_ctx *c, hipStream_t st, const RastSeq &q);
-int rast_seq_chain_exact(cg_ctx *c, hipStream_t st, const RastSeq &q, const long long *total);
-int rast_rand_stream(cg_ctx *c, int rnd_buf, int jt_buf, uint64_t offset, long long S, hipStream_t st, int32_t **out);
-void launch_rast_post_direct(const RastArgs &A, const float4 *state, const int32_t *shadow, uint32_t *d_argb,
-                             hipStream_t st);
 
 typedef unsigned long long u64;
 
@@ -821,11 +807,11 @@ __global__ __launch_bounds__(256) void rast_big_colour_kernel(RastArgs A0, const
 // ---- host ----
 namespace {
 
-// ctx_buf slots of this route's own buffers (cg_shim.hip: rbig[which - 20])
-enum { kBufTris = 20, kBufPre, kBufNrows, kBufSpanOff, kBufSpanTy, kBufHist, kBufRowOff, kBufScan,
+// ctx_buf slots of this route's own buffers (cg_ctx::rbig[which - kBufBig0])
+enum { kBigTris = kBufBig0, kBigPre, kBigNrows, kBigSpanOff, kBigSpanTy, kBigHist, kBigRowOff, kBigScan,
        // colour modes 1-2 only: segments per span, their offsets, each record's first entry, the
        // entries' fragment counts, their prefix, the rand() stream and its jump table
-       kBufNseg, kBufSegOff, kBufRecEnt, kBufEnt, kBufFbase, kBufRnd, kBufJt };
+       kBigNseg, kBigSegOff, kBigRecEnt, kBigEnt, kBigFbase, kBigRnd, kBigJt };
 
 // The refusal of a colour mode 1-2 frame that cg_rast_set_route(ctx, 1) forced here: the hook is a
 // colour-mode-0 A/B switch (modes 1-2 reach this route on the automatic choice only).
@@ -850,7 +836,7 @@ int big_scan(cg_ctx *c, hipStream_t st, const int *in, long long N, u64 *out)
         return e == hipSuccess ? CG_OK : ctx_fail(c, e, "memset");
     }
     const long long nb = (N + kScanBlock - 1) / kScanBlock;
-    u64 *bsum = (u64 *)ctx_buf(c, kBufScan, (size_t)nb * sizeof(u64), &e);
+    u64 *bsum = (u64 *)ctx_buf(c, kBigScan, (size_t)nb * sizeof(u64), &e);
     if (!bsum) return ctx_fail(c, e, "alloc scan sums");
     hipLaunchKernelGGL(rast_big_scan_reduce_kernel, dim3((unsigned)nb), dim3(kScanThreads), 0, st, in, N, bsum);
     hipLaunchKernelGGL(rast_big_scan_top_kernel, dim3(1), dim3(kScanThreads), 0, st, bsum, (int)nb, out + N);
@@ -869,10 +855,10 @@ int big_colour(cg_ctx *c, const RastArgs &A, const cg_rast_params *p, const RowR
     hipError_t e;
     const size_t npx = (size_t)A.W * A.H, ne = n_ent > 0 ? (size_t)n_ent : 1;
     int32_t *shadow = d_shadow;   // the post-pass reads the marks from the plane
-    if (!shadow && !(shadow = (int32_t *)ctx_buf(c, 6, npx * sizeof(int32_t), &e))) return ctx_fail(c, e, "alloc shadow");
-    int *ent = (int *)ctx_buf(c, kBufEnt, ne * sizeof(int), &e);
+    if (!shadow && !(shadow = (int32_t *)ctx_buf(c, kBufShadow, npx * sizeof(int32_t), &e))) return ctx_fail(c, e, "alloc shadow");
+    int *ent = (int *)ctx_buf(c, kBigEnt, ne * sizeof(int), &e);
     if (!ent) return ctx_fail(c, e, "alloc entry counts");
-    u64 *fbase = (u64 *)ctx_buf(c, kBufFbase, (ne + 1) * sizeof(u64), &e);
+    u64 *fbase = (u64 *)ctx_buf(c, kBigFbase, (ne + 1) * sizeof(u64), &e);
     if (!fbase) return ctx_fail(c, e, "alloc fragment numbers");
     const int fgrid = xcd_grid(A.H, ((A.W + kFillPx - 1) / kFillPx * kXcdRows + 3) / 4);
     {
@@ -895,7 +881,7 @@ int big_colour(cg_ctx *c, const RastArgs &A, const cg_rast_params *p, const RowR
     int32_t *rnd = nullptr;
     {
         KtScope kt(KT_RAST_BIG_RAND, st);
-        if (const int rc = rast_rand_stream(c, kBufRnd, kBufJt, offset, (long long)S, st, &rnd)) return rc;
+        if (const int rc = rast_rand_stream(c, kBigRnd, kBigJt, offset, (long long)S, st, &rnd)) return rc;
     }
     {
         KtScope kt(KT_RAST_BIG_SHADE, st);
@@ -931,21 +917,21 @@ int big_pipeline(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *
     hipError_t e;
     RastArgs A;
     if (const int rc = rast_make_args(c, d_tris, n, p, light, d_light, tex_mask, &A)) return rc;
-    int *misc = (int *)ctx_buf(c, 7, ((size_t)H + 16) * sizeof(int), &e);   // count[H] | first_tri
+    int *misc = (int *)ctx_buf(c, kBufCount, ((size_t)H + 16) * sizeof(int), &e);   // count[H] | first_tri
     if (!misc) return ctx_fail(c, e, "alloc counts");
     int *count = misc, *first_tri = misc + H;
     const size_t nn = n > 0 ? (size_t)n : 1;
-    RastHdr *hdr = (RastHdr *)ctx_buf(c, 1, nn * sizeof(RastHdr), &e);
+    RastHdr *hdr = (RastHdr *)ctx_buf(c, kBufHdr, nn * sizeof(RastHdr), &e);
     if (!hdr) return ctx_fail(c, e, "alloc hdr");
-    int *nrows = (int *)ctx_buf(c, kBufNrows, nn * sizeof(int), &e);
+    int *nrows = (int *)ctx_buf(c, kBigNrows, nn * sizeof(int), &e);
     if (!nrows) return ctx_fail(c, e, "alloc row counts");
-    u64 *span_off = (u64 *)ctx_buf(c, kBufSpanOff, (nn + 1) * sizeof(u64), &e);
+    u64 *span_off = (u64 *)ctx_buf(c, kBigSpanOff, (nn + 1) * sizeof(u64), &e);
     if (!span_off) return ctx_fail(c, e, "alloc span offsets");
-    u64 *row_off = (u64 *)ctx_buf(c, kBufRowOff, ((size_t)H + 2) * sizeof(u64), &e);
+    u64 *row_off = (u64 *)ctx_buf(c, kBigRowOff, ((size_t)H + 2) * sizeof(u64), &e);
     if (!row_off) return ctx_fail(c, e, "alloc row offsets");
     const bool colour = p->colour_mode != 0;
     // fill -> post state: 4 B/pixel in colour mode 0, the colour walk's 16 B in modes 1-2
-    void *state = ctx_buf(c, 3, npx * (colour ? sizeof(float4) : sizeof(uint32_t)), &e);
+    void *state = ctx_buf(c, kBufPix, npx * (colour ? sizeof(float4) : sizeof(uint32_t)), &e);
     if (!state) return ctx_fail(c, e, "alloc state");
     hipEvent_t e0, e1;
     ctx_events(c, &e0, &e1);
@@ -965,12 +951,12 @@ int big_pipeline(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *
         if (const int rc = big_read(c, st, &n_spans, span_off + n, sizeof(u64), "span total")) return rc;
     }
     const size_t ns = n_spans > 0 ? (size_t)n_spans : 1;
-    RastSpan *spans = (RastSpan *)ctx_buf(c, 2, ns * sizeof(RastSpan), &e);
+    RastSpan *spans = (RastSpan *)ctx_buf(c, kBufSpan, ns * sizeof(RastSpan), &e);
     if (!spans) return ctx_fail(c, e, "alloc spans");
-    uint2 *span_ty = (uint2 *)ctx_buf(c, kBufSpanTy, ns * sizeof(uint2), &e);
+    uint2 *span_ty = (uint2 *)ctx_buf(c, kBigSpanTy, ns * sizeof(uint2), &e);
     if (!span_ty) return ctx_fail(c, e, "alloc span keys");
     const long long chunks = (long long)((n_spans + kBigChunk - 1) / kBigChunk);
-    int *hist = (int *)ctx_buf(c, kBufHist, (size_t)std::max(chunks, 1ll) * H * sizeof(int), &e);
+    int *hist = (int *)ctx_buf(c, kBigHist, (size_t)std::max(chunks, 1ll) * H * sizeof(int), &e);
     if (!hist) return ctx_fail(c, e, "alloc row histogram");
     if (n > 0) {
         KtScope kt(KT_RAST_BIG_SETUP, st);
@@ -982,9 +968,9 @@ int big_pipeline(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *
     // -- colour modes 1-2: the entries of c each span takes, their offsets
     u64 *seg_off = nullptr, n_ent = 0;
     if (colour) {
-        int *nseg = (int *)ctx_buf(c, kBufNseg, ns * sizeof(int), &e);
+        int *nseg = (int *)ctx_buf(c, kBigNseg, ns * sizeof(int), &e);
         if (!nseg) return ctx_fail(c, e, "alloc span segments");
-        seg_off = (u64 *)ctx_buf(c, kBufSegOff, (ns + 1) * sizeof(u64), &e);
+        seg_off = (u64 *)ctx_buf(c, kBigSegOff, (ns + 1) * sizeof(u64), &e);
         if (!seg_off) return ctx_fail(c, e, "alloc segment offsets");
         {
             KtScope kt(KT_RAST_BIG_COUNT, st);
@@ -1011,11 +997,11 @@ int big_pipeline(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *
     }
     if (const int rc = big_read(c, st, tot, row_off + H, sizeof(tot), "record total")) return rc;
     const u64 n_recs = tot[0];
-    RowRec *recs = (RowRec *)ctx_buf(c, 8, (size_t)std::max<u64>(n_recs, 1) * sizeof(RowRec), &e);
+    RowRec *recs = (RowRec *)ctx_buf(c, kBufRecs, (size_t)std::max<u64>(n_recs, 1) * sizeof(RowRec), &e);
     if (!recs) return ctx_fail(c, e, "alloc row records");
     A.state16 = !colour && tot[1] < 32768;
     u64 *rec_ent = nullptr;
-    if (colour && !(rec_ent = (u64 *)ctx_buf(c, kBufRecEnt, (size_t)std::max<u64>(n_recs, 1) * sizeof(u64), &e)))
+    if (colour && !(rec_ent = (u64 *)ctx_buf(c, kBigRecEnt, (size_t)std::max<u64>(n_recs, 1) * sizeof(u64), &e)))
         return ctx_fail(c, e, "alloc record entries");
     if (chunks > 0 && n_recs > 0) {
         KtScope kt(KT_RAST_BIG_ROWS, st);
@@ -1124,13 +1110,13 @@ int rast_big_draw(cg_ctx *c, const cg_rtri *d_room, int n_room, const cg_rtri *d
     const size_t ni = n_in > 0 ? (size_t)n_in : 1;
     hipError_t e;
     // each input triangle's staged survivors (32 each)
-    cg_rtri *stage = (cg_rtri *)ctx_buf(c, 0, ni * kGeomMaxLeaves * sizeof(cg_rtri), &e);
+    cg_rtri *stage = (cg_rtri *)ctx_buf(c, kBufTris, ni * kGeomMaxLeaves * sizeof(cg_rtri), &e);
     if (!stage) return ctx_fail(c, e, "alloc clip staging");
-    int *geo = (int *)ctx_buf(c, 9, 64 + 4 * ni, &e);   // [4..7] light, [16..] counts
+    int *geo = (int *)ctx_buf(c, kBufGeo, 64 + 4 * ni, &e);   // [4..7] light, [16..] counts
     if (!geo) return ctx_fail(c, e, "alloc geometry header");
-    int *misc = (int *)ctx_buf(c, 7, ((size_t)p->height + 16) * sizeof(int), &e);   // count[H] | first_tri
+    int *misc = (int *)ctx_buf(c, kBufCount, ((size_t)p->height + 16) * sizeof(int), &e);   // count[H] | first_tri
     if (!misc) return ctx_fail(c, e, "alloc counts");
-    u64 *pre = (u64 *)ctx_buf(c, kBufPre, (ni + 1) * sizeof(u64), &e);
+    u64 *pre = (u64 *)ctx_buf(c, kBigPre, (ni + 1) * sizeof(u64), &e);
     if (!pre) return ctx_fail(c, e, "alloc clip offsets");
     hipEvent_t e0, e1;
     ctx_events(c, &e0, &e1);
@@ -1146,7 +1132,7 @@ int rast_big_draw(cg_ctx *c, const cg_rtri *d_room, int n_room, const cg_rtri *d
     if (const int rc = big_read(c, st, &total, pre + n_in, sizeof(u64), "clipped count")) return rc;
     if (total > (u64)kGeomMaxLeaves * (u64)ni) return ctx_invalid(c, "clipped count past the clip's capacity");
     const int n = (int)total;
-    cg_rtri *tris = (cg_rtri *)ctx_buf(c, kBufTris, (size_t)std::max(n, 1) * sizeof(cg_rtri), &e);
+    cg_rtri *tris = (cg_rtri *)ctx_buf(c, kBigTris, (size_t)std::max(n, 1) * sizeof(cg_rtri), &e);
     if (!tris) return ctx_fail(c, e, "alloc clipped triangles");
     if (n > 0) {
         KtScope kt(KT_RAST_BIG_CLIP, st);

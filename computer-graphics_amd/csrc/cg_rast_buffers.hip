@@ -14,13 +14,10 @@
 // Colour modes 1-2 never make state words (their fill keeps a colour per pixel); a buffers call
 // has the route run the mode-0 fill once more for them (the owner does not depend on the colour
 // mode: modes 1-2 ignore textures, :604), and `screen` comes from the colour fill's float4.
+#include "cg_host.h"
 #include "cg_rast_dev.h"
 
 namespace cg {
-
-void *ctx_buf(cg_ctx *c, int which, size_t bytes, hipError_t *e);
-int ctx_fail(cg_ctx *c, hipError_t e, const char *what);
-int ctx_invalid(cg_ctx *c, const char *what);
 
 typedef unsigned long long u64;
 

@@ -27,12 +27,10 @@
 #include <vector>
 
 #include "cg_glibc_rand.h"
+#include "cg_host.h"
 #include "cg_rast_dev.h"
 
 namespace cg {
-
-void *ctx_buf(cg_ctx *c, int which, size_t bytes, hipError_t *e);
-int ctx_fail(cg_ctx *c, hipError_t e, const char *what);
 
 constexpr int kRandChunk = 31 * 32;    // rand() values per generator thread
 
@@ -437,9 +435,9 @@ int rast_colour_fill(cg_ctx *c, const RastArgs &A, const cg_rast_params *p, cons
 {
     hipError_t e;
     const int n = A.n > 0 ? A.n : 1, H = A.H;
-    int *pc = (int *)ctx_buf(c, 10, (size_t)n * H * sizeof(int), &e);
+    int *pc = (int *)ctx_buf(c, kBufPc, (size_t)n * H * sizeof(int), &e);
     if (!pc) return ctx_fail(c, e, "alloc pass counts");
-    long long *tl = (long long *)ctx_buf(c, 11, (2 * (size_t)n + 2) * sizeof(long long), &e);
+    long long *tl = (long long *)ctx_buf(c, kBufTl, (2 * (size_t)n + 2) * sizeof(long long), &e);
     if (!tl) return ctx_fail(c, e, "alloc triangle counts");
     long long *tot = tl, *tbase = tl + n, *total = tl + 2 * n;
     if ((e = hipMemsetAsync(pc, 0, (size_t)n * H * sizeof(int), st)) != hipSuccess) return ctx_fail(c, e, "memset");
@@ -455,7 +453,7 @@ int rast_colour_fill(cg_ctx *c, const RastArgs &A, const cg_rast_params *p, cons
         return ctx_fail(c, e, "shaded-fragment count");
     *n_shaded = S;
     int32_t *rnd = nullptr;
-    if (const int rc = rast_rand_stream(c, 12, 13, p->rand_offset, S, st, &rnd)) return rc;
+    if (const int rc = rast_rand_stream(c, kBufRnd, kBufJt, p->rand_offset, S, st, &rnd)) return rc;
     hipLaunchKernelGGL(rast_fill_rand_kernel, dim3(H), dim3(64), (size_t)(max_recs > 0 ? max_recs : 1) * 8, st, A,
                        recs, count, pc, tbase, rnd, p->colour_mode, state, d_depth, shadow,
                        (const cg_rast_seq_frame *)nullptr);
@@ -472,7 +470,7 @@ int rast_seq_tables(cg_ctx *c, long long nb, long long *have, uint32_t **tables)
 {
     hipError_t e;
     const size_t words = (size_t)kSeqJump + (size_t)(nb > *have ? nb : *have) * kRandDeg;
-    uint32_t *t = (uint32_t *)ctx_buf(c, 18, words * sizeof(uint32_t), &e);
+    uint32_t *t = (uint32_t *)ctx_buf(c, kBufSeq, words * sizeof(uint32_t), &e);
     if (!t) return ctx_fail(c, e, "alloc generator tables");
     *tables = t;
     if (nb <= *have) return CG_OK;
@@ -496,11 +494,11 @@ int rast_seq_colour_fill(cg_ctx *c, const RastArgs &A, const cg_rast_params *p, 
 {
     hipError_t e;
     const int n = A.n > 0 ? A.n : 1, H = A.H;
-    int *pc = (int *)ctx_buf(c, 10, (size_t)n * H * sizeof(int), &e);
+    int *pc = (int *)ctx_buf(c, kBufPc, (size_t)n * H * sizeof(int), &e);
     if (!pc) return ctx_fail(c, e, "alloc pass counts");
-    long long *tl = (long long *)ctx_buf(c, 11, (2 * (size_t)n + 2) * sizeof(long long), &e);
+    long long *tl = (long long *)ctx_buf(c, kBufTl, (2 * (size_t)n + 2) * sizeof(long long), &e);
     if (!tl) return ctx_fail(c, e, "alloc triangle counts");
-    int32_t *rnd = (int32_t *)ctx_buf(c, 12, 3 * (size_t)(q.cap > 0 ? q.cap : 1) * sizeof(int32_t), &e);
+    int32_t *rnd = (int32_t *)ctx_buf(c, kBufRnd, 3 * (size_t)(q.cap > 0 ? q.cap : 1) * sizeof(int32_t), &e);
     if (!rnd) return ctx_fail(c, e, "alloc rand stream");
     long long *tot = tl, *tbase = tl + n, *total = tl + 2 * n;
     if ((e = hipMemsetAsync(pc, 0, (size_t)n * H * sizeof(int), st)) != hipSuccess) return ctx_fail(c, e, "memset");

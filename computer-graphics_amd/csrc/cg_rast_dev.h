@@ -68,8 +68,6 @@ struct RastSeq {
 constexpr int kRastDenseInputs = 4096;                                  // input triangles the dense Draw accepts
 constexpr long long kRastDenseList = (long long)kGeomMaxLeaves * kRastDenseInputs;   // 131072: its list capacity
 constexpr long long kRastMaxInputs = 4194304;                           // cg_rast_set_scene's limit
-// The route a frame of list capacity `cap` takes on this context (its forced route, else cg_rast_route).
-int ctx_rast_route(cg_ctx *c, long long cap);
 // What cg_rast_scratch_info reports of the latest frame.  The dense route leaves its counts on
 // the device (n_dev, count[H]); the compact route knows them on the host.
 struct RastLast {
@@ -81,7 +79,6 @@ struct RastLast {
     int H = 0;
     hipStream_t st = nullptr;
 };
-RastLast *ctx_rast_last(cg_ctx *c);
 struct RowRec;
 // What the latest frame left in context scratch, for the buffers kernel (cg_rast_buffers.hip):
 // the ordered z-buffer's state words and the row records they name.  Host bookkeeping only.
@@ -101,18 +98,6 @@ struct RastFrame {
     int n_in = 0;
     hipStream_t st = nullptr;
 };
-RastFrame *ctx_rast_frame(cg_ctx *c);
-// A buffers call is running the frame (cg_rast_draw_buffers*, cg_rast_pick): colour modes 1-2
-// also run the ordered z-buffer's fill for the state words, which they otherwise never make.
-bool ctx_rast_want_owner(cg_ctx *c);
-enum { kBufOwner = 40, kBufClipPre, kBufScreen, kBufLow, kBufHigh, kBufClipId, kBufTriId, kBufPos, kBufPick };
-// cg_rast_set_route(ctx, 1) holds: the A/B hook's compact frames are colour mode 0 only
-bool ctx_rast_forced_compact(cg_ctx *c);
-int rast_big_render(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *p, cg_vec4 light, uint32_t *d_argb,
-                    float *d_depth, int32_t *d_shadow, hipStream_t st, cg_stats *stats, int tex_mask);
-int rast_big_draw(cg_ctx *c, const cg_rtri *d_room, int n_room, const cg_rtri *d_boxes, int n_boxes,
-                  const cg_rast_params *p, uint32_t *d_argb, float *d_depth, int32_t *d_shadow, hipStream_t st,
-                  cg_stats *stats, int **n_out, int tex_mask, const RastSeq *seq);
 
 // Ordered per-row records (one wave per screen row): for every triangle in
 // order whose span on this row has a fragment on screen, a 48-byte record

@@ -13,6 +13,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "cg_host.h"
 #include "cg_rt_dev.h"
 
 namespace cg {
@@ -2488,7 +2489,7 @@ __global__ void rt_probe_direct_light_kernel(RtFrame F, const RtTri *__restrict_
 }
 
 // ---------------------------------------------------------------------------
-// Launch helpers (called by the shim).
+// Launch helpers (called by the cg_api_*.hip files).
 // d_sup_masks (optional): two-level certificates -- super-tiles, then their
 // tiles.  By default one fused rt_tile_cert_kernel launch does both levels and
 // the RtTri constants (the super-tile masks stay in LDS; d_sup_masks unused);

@@ -34,6 +34,7 @@
 #include <cstdio>
 #include <vector>
 
+#include "cg_host.h"
 #include "cg_rt_dev.h"
 #include "cg_rt_grid.h"
 
@@ -58,7 +59,7 @@ struct PendRay {
 // bin's shadow candidates) is a sequence of chunks in one pool per kind, a
 // chunk being the survivors of one workgroup pass over <= 1024 candidates
 // (one pool reservation); chunk c of list k is chunk[k * nch + c].  Pool
-// capacities come from the host (cg_shim.hip: sized on a scene's first
+// capacities come from the host (cg_api_rt.hip: sized on a scene's first
 // frame, grown from the demand each later frame reports); a reservation past
 // the capacity marks the list overflowed and its consumers fall back to
 // every triangle -- slower, the same image -- while the full demand is still
@@ -2660,7 +2661,7 @@ hipError_t launch_rt_big(const RtFrame &F, RtTri *d_tc, const RtShade *d_shade, 
     const dim3 egrid(std::min(cnt_wgs, (F.n_tris + 1023) / 1024), bins);   // workgroups stride over a bin's list
     hipLaunchKernelGGL(rt_bin_count_kernel, egrid, dim3(256), 0, st, F, d_tc, d_tris, B);
     hipLaunchKernelGGL(rt_bin_scan_kernel, dim3(1), dim3(1024), 0, st, B, 2 * bins);
-    // sizing passes (cg_shim.hip) stop early and report the demand: dry 1
+    // sizing passes (cg_api_rt.hip) stop early and report the demand: dry 1
     // after the camera-ray lists, dry 2 after the many-light shadow lists
     auto demand = [&]() {
         const hipError_t c = h_demand ? hipMemcpyAsync(h_demand, B.pool_n, 4 * sizeof(unsigned long long),

@@ -23,7 +23,7 @@
 
 #include <algorithm>
 
-#include "cg_internal.h"
+#include "cg_host.h"
 
 namespace cg {
 

@@ -18,6 +18,7 @@
 
 #include <algorithm>
 
+#include "cg_host.h"
 #include "cg_rt_dev.h"
 
 namespace cg {

@@ -6,7 +6,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "cg_internal.h"
+#include "cg_host.h"
 #include "cg_rt_grid.h"
 
 using namespace cg;

@@ -9,20 +9,9 @@
 #include <new>
 #include <vector>
 
-#include "cg_internal.h"
-
-namespace cg {
-void *ctx_buf(cg_ctx *c, int which, size_t bytes, hipError_t *e);
-int ctx_fail(cg_ctx *c, hipError_t e, const char *what);
-hipStream_t ctx_stream(cg_ctx *c);
-int ctx_device(cg_ctx *c);
-void ctx_events(cg_ctx *c, hipEvent_t *a, hipEvent_t *b);
-StarState *ctx_star(cg_ctx *c);
-}  // namespace cg
+#include "cg_host.h"
 
 using namespace cg;
-
-extern "C" int cg_glibc_rand(uint64_t offset, int n, int32_t *out);
 
 // :41-46 -- (float(rand()) / float(RAND_MAX) - 0.5) * 2 is evaluated in double
 extern "C" int cg_starfield_init(float *stars, int n)
@@ -86,9 +75,9 @@ extern "C" int cg_starfield_draw(cg_ctx *c, const float *stars, int n, int width
     if (!c || n < 0 || (n && !stars) || !argb || width <= 0 || height <= 0) return CG_E_INVALID;
     hipError_t e;
     const size_t npx = (size_t)width * height;
-    float *d_st = (float *)ctx_buf(c, 14, (size_t)(n > 0 ? n : 1) * 3 * sizeof(float), &e);
+    float *d_st = (float *)ctx_buf(c, kBufStars, (size_t)(n > 0 ? n : 1) * 3 * sizeof(float), &e);
     if (!d_st) return ctx_fail(c, e, "alloc stars");
-    uint32_t *d_px = (uint32_t *)ctx_buf(c, 15, npx * sizeof(uint32_t), &e);
+    uint32_t *d_px = (uint32_t *)ctx_buf(c, kBufStarFrame, npx * sizeof(uint32_t), &e);
     if (!d_px) return ctx_fail(c, e, "alloc starfield frame");
     hipStream_t st = ctx_stream(c);
     if (n && (e = hipMemcpyAsync(d_st, stars, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, st)) != hipSuccess)

@@ -1,6 +1,6 @@
 """GPU: certificates published beside the lattice launch (cg_internal.h LatReady /
 LatPublish, CG_CERT_CONC=1; VERDICT r05 item 1 -- built, measured slower, off by
-default, cg_shim.hip cert_concurrent).  A whole-frame batched call starts its
+default, cg_api_rt.hip cert_concurrent).  A whole-frame batched call starts its
 lattice launch beside its certificate launch; each lattice workgroup waits only
 for its own super-tile's publication word, or -- past its bound, or forced with
 CG_LAT_FORCE_UNCERT=1 -- renders its tile uncertified (every triangle and the

@@ -309,7 +309,7 @@ def test_rt_render_frames_batched(rt, golden):
 @pytest.mark.parametrize("nl", [1, 4])
 def test_rt_render_frames_lateral_windows(rt, nl):
     """A batch's lattice launches cover only the union of its cameras' column windows (the
-    scene box's projection, cg_shim.hip rt_enqueue_lattice_batch): cameraPos moving sideways
+    scene box's projection, cg_api_rt.hip rt_enqueue_lattice_batch): cameraPos moving sideways
     -- windows at either edge, one camera that sees nothing at all (an empty window), one
     centred -- rendered as one batched launch (the edge workgroups store the columns outside
     the union black) == each frame rendered alone (no window), one light and a light set."""
