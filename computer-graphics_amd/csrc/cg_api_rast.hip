@@ -175,7 +175,7 @@ extern "C" int cg_rast_draw_frames_device(cg_ctx *c, const cg_rast_params *ps, i
             return ctx_invalid(c, "draw_frames: colour mode 0 frames of one size (modes 1-2 chain rand offsets)");
     CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    if (ctx_rast_route(c, kGeomMaxLeaves * ((long long)c->n_room + 7ll * c->n_boxes)) == CG_RAST_ROUTE_COMPACT) {
+    if (ctx_rast_route(c, kGeomMaxLeaves * ((long long)c->n_room + 7ll * c->n_boxes), false) == CG_RAST_ROUTE_COMPACT) {
         // compact-route frames follow each other on `stream`: a lane would hold its own copy of the scratch
         for (int f = 0; f < n_frames; ++f) {
             const size_t o = (size_t)f * stride;
@@ -321,8 +321,8 @@ static int rast_sequence_device(cg_ctx *c, const cg_rast_params *ps, int n_frame
         return std::max(1, std::min(v, (int)cg_ctx::kRastLanes));
     }();
     // compact-route frames follow each other on `stream` (a lane would hold its own copy of the scratch)
-    const bool compact =
-        ctx_rast_route(c, kGeomMaxLeaves * ((long long)c->n_room + 7ll * c->n_boxes)) == CG_RAST_ROUTE_COMPACT;
+    q.route = ctx_rast_route(c, kGeomMaxLeaves * ((long long)c->n_room + 7ll * c->n_boxes), colour);
+    const bool compact = q.route == CG_RAST_ROUTE_COMPACT;
     const int L = compact ? 1 : std::min(lane_cap > 0 ? std::min(lanes, lane_cap) : lanes, n_frames);
     if (L > 1) {
         const int rc = rast_lanes_ready(c, L);

@@ -67,10 +67,11 @@ void rast_release(cg_ctx *c)
     c->twoven_op.release(); c->twoven_nrm.release(); c->tgrill.release(); c->tgrill_op.release();
     c->tgrill_nrm.release(); c->rtexel.release();
 }
-int ctx_rast_route(cg_ctx *c, long long cap)
+int ctx_rast_route(cg_ctx *c, long long cap, bool colour)
 {
     if (c->rast_route >= 0) return c->rast_route;
     if (c->route_limit > 0) return cap <= c->route_limit ? CG_RAST_ROUTE_DENSE : CG_RAST_ROUTE_COMPACT;
+    if (colour && cap > kRastDenseColourList) return CG_RAST_ROUTE_COMPACT;
     return cg_rast_route(cap);
 }
 bool ctx_rast_forced_compact(cg_ctx *c) { return c->rast_route == CG_RAST_ROUTE_COMPACT; }

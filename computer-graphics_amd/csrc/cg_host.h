@@ -43,8 +43,10 @@ int ctx_fail(cg_ctx *c, hipError_t e, const char *what);
 // cg_rt_frame_columns over the context's scene (the full width without one)
 void ctx_rt_columns(const cg_ctx *c, const cg_rt_camera *cam, int *c0, int *c1);
 StarState *ctx_star(cg_ctx *c);
-// The route a frame of list capacity `cap` takes on this context (its forced route, else cg_rast_route).
-int ctx_rast_route(cg_ctx *c, long long cap);
+// The route a frame of list capacity `cap` takes on this context: its forced route, else its route
+// limit, else cg_rast_route -- but compact for a colour mode 1-2 frame (`colour`) whose list the dense
+// colour fill's LDS counters cannot hold (kRastDenseColourList).
+int ctx_rast_route(cg_ctx *c, long long cap, bool colour);
 // cg_rast_set_route(ctx, 1) holds: the A/B hook's compact frames are colour mode 0 only
 bool ctx_rast_forced_compact(cg_ctx *c);
 RastLast *ctx_rast_last(cg_ctx *c);

@@ -705,7 +705,7 @@ int rast_render_device(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_pa
                        uint32_t *d_argb, float *d_depth, int32_t *d_shadow, hipStream_t st,
                        cg_stats *stats, int tex_mask)
 {
-    if (ctx_rast_route(c, n) == CG_RAST_ROUTE_COMPACT)
+    if (ctx_rast_route(c, n, p->colour_mode != 0) == CG_RAST_ROUTE_COMPACT)
         return rast_big_render(c, d_tris, n, p, light, d_argb, d_depth, d_shadow, st, stats, tex_mask);
     return rast_pipeline(c, const_cast<cg_rtri *>(d_tris), n, nullptr, p, light, nullptr, d_argb, d_depth, d_shadow,
                          st, stats, false, tex_mask, RastStage{nullptr, nullptr, 0});
@@ -720,7 +720,9 @@ int rast_draw_device(cg_ctx *c, const cg_rtri *d_room, int n_room, const cg_rtri
 {
     if (p->width <= 2 || p->height <= 2 || p->height > kRastMaxRows || p->focal == 0.0f) return CG_E_INVALID;
     const long long n_in_ll = (long long)n_room + 7ll * n_boxes;
-    if (ctx_rast_route(c, kGeomMaxLeaves * n_in_ll) == CG_RAST_ROUTE_COMPACT)
+    // a sequence's frames all take the route the call chose (its lanes and tables follow it)
+    const int route = seq ? seq->route : ctx_rast_route(c, kGeomMaxLeaves * n_in_ll, p->colour_mode != 0);
+    if (route == CG_RAST_ROUTE_COMPACT)
         return rast_big_draw(c, d_room, n_room, d_boxes, n_boxes, p, d_argb, d_depth, d_shadow, st, stats, n_out,
                              tex_mask, seq);
     if (n_in_ll > kRastDenseInputs)
@@ -757,6 +759,9 @@ static int rast_pipeline(cg_ctx *c, cg_rtri *d_tris, int n, int *n_dev, const cg
     const int W = p->width, H = p->height;
     const size_t npx = (size_t)W * H;
     const int nn = n > 0 ? n : 1;
+    if (p->colour_mode != 0 && nn > kRastDenseColourList)   // reached only on a forced dense route or a route limit
+        return ctx_invalid(c, "dense route: colour modes 1-2 count fragments per list slot in LDS, at most 20480 "
+                              "slots (32 an input triangle); the automatic route takes the compact route there");
     hipError_t e;
     RastSpan *spans = (RastSpan *)ctx_buf(c, kBufSpan, (size_t)nn * H * sizeof(RastSpan), &e);
     if (!spans) return ctx_fail(c, e, "alloc spans");

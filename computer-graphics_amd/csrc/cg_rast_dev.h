@@ -62,11 +62,16 @@ struct RastSeq {
     // frames on several lanes: the frame's chain step waits for the previous frame's (wait_ev,
     // null for the first) and announces itself (done_ev); null on one stream
     hipEvent_t wait_ev, done_ev;
+    int route;                 // the route of every frame of the call (ctx_rast_route with the call's colour frames)
 };
 
 // ---- routes (cg_rast_route): the dense pipeline of cg_rast.hip, the compact one of cg_rast_big.hip ----
 constexpr int kRastDenseInputs = 4096;                                  // input triangles the dense Draw accepts
 constexpr long long kRastDenseList = (long long)kGeomMaxLeaves * kRastDenseInputs;   // 131072: its list capacity
+// Colour modes 1-2 on the dense route count fragments per list slot in LDS (rast_count_kernel 4 B,
+// rast_fill_rand_kernel 8 B a slot): what gfx950's 160 KiB a workgroup holds.  A longer list in
+// those modes takes the compact route.
+constexpr long long kRastDenseColourList = 160 * 1024 / 8;              // 20480
 constexpr long long kRastMaxInputs = 4194304;                           // cg_rast_set_scene's limit
 // What cg_rast_scratch_info reports of the latest frame.  The dense route leaves its counts on
 // the device (n_dev, count[H]); the compact route knows them on the host.

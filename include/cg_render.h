@@ -698,7 +698,12 @@ int cg_rast_state_bytes(cg_ctx *ctx);
  * triangle order by a stable counting sort of the spans.  cg_rast_route
  * (host-only) is the automatic choice: DENSE for list_capacity <= 131072,
  * else COMPACT; list_capacity is 32 * (n_room + 7 * n_boxes) for the
- * cg_rast_draw* entries and n for cg_rast_render*.
+ * cg_rast_draw* entries and n for cg_rast_render*.  A colour mode 1-2 frame
+ * takes COMPACT already for list_capacity > 20480: the dense route's colour
+ * fill counts fragments per list slot in LDS (8 bytes a slot, 160 KiB); a
+ * cg_rast_draw_sequence_device call with such a frame runs all its frames
+ * there.  A forced dense route or a route limit that puts such a frame on the
+ * dense route fails with CG_E_INVALID and a message.
  * The compact route serves cg_rast_draw, cg_rast_draw_device, cg_rast_render
  * and cg_rast_render_device in colour modes 0-2 with texture modes 0-3 (modes
  * 1-2 ignore textures, as the reference does) and the indirect_first rule;

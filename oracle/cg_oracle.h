@@ -152,8 +152,18 @@ void cgo_rast_default_params(cgo_rast_params *p, int width, int height);
  * triangles written to out (cap entries), light position (camera space,
  * rotated) to *light_out. */
 int  cgo_rast_geometry(const cgo_rast_params *p, cgo_rast_tri *out, int cap, cgo_v4 *light_out);
+/* The same on a caller's room and boxes (cg_rast_set_scene's arguments): the records' texture
+ * fields stand, p->setting / setting_boxes are not applied.  Any number of triangles. */
+int  cgo_rast_geometry_scene(const cgo_rast_params *p, const cgo_rast_tri *room, int n_room,
+                             const cgo_rast_tri *boxes, int n_boxes, cgo_rast_tri *out, int cap,
+                             cgo_v4 *light_out);
+/* One clip plane (1-6); returns the count the plane gives, of which min(count, cap) are written. */
 int  cgo_rast_clip(const cgo_rast_tri *in, int n, int plane, const cgo_rast_params *p,
                    cgo_rast_tri *out, int cap);
+/* Test hook: while counts (uint64_t[56], caller-owned) is set, every triangle cgo_rast_clip
+ * handles adds one to counts[8 * plane + case]: case 0 all three vertices in, 1-3 only v0 / v1 /
+ * v2 in, 4-6 only v2 / v1 / v0 out, 7 dropped.  NULL stops the counting.  Not thread-safe. */
+void cgo_rast_clip_case_counts(uint64_t *counts);
 void cgo_rast_vertex_shader(const cgo_rast_params *p, cgo_v4 v, cgo_pixel *px);
 void cgo_rast_interpolate(cgo_pixel a, cgo_pixel b, cgo_pixel *result, int n);
 /* Returns rows; left/right must hold >= rows entries (pass NULL to query). */
@@ -162,6 +172,16 @@ int  cgo_rast_polygon_rows(const cgo_pixel *vp, cgo_pixel *left, cgo_pixel *righ
  * are float[3*W*H]. */
 void cgo_rast_draw(const cgo_rast_params *p, uint32_t *argb, float *depth, int32_t *shadow,
                    float *screen_buf, float *low_buf, float *high_buf, cgo_rast_counters *cnt);
+/* The same frame of a caller's room and boxes. */
+void cgo_rast_draw_scene(const cgo_rast_params *p, const cgo_rast_tri *room, int n_room,
+                         const cgo_rast_tri *boxes, int n_boxes, uint32_t *argb, float *depth,
+                         int32_t *shadow, float *screen_buf, float *low_buf, float *high_buf,
+                         cgo_rast_counters *cnt);
+/* Draw from the buffer clears on (skeleton.cpp:243-308) for an already clipped list and the
+ * light in rotated camera space: what cg_rast_render takes. */
+void cgo_rast_draw_list(const cgo_rast_params *p, const cgo_rast_tri *tris, int n, cgo_v4 light,
+                        uint32_t *argb, float *depth, int32_t *shadow, float *screen_buf,
+                        float *low_buf, float *high_buf, cgo_rast_counters *cnt);
 
 /* ------------------------- texture loading ----------------------------- */
 /* cv::imread(path, CV_LOAD_IMAGE_UNCHANGED) of a JPEG as the reference's

@@ -210,30 +210,40 @@ static cgo_rast_tri extra_tri(cgo_v4 a, cgo_v4 b, cgo_v4 c, const cgo_rast_tri *
     return e;
 }
 
+/* Test hook: how often each clip case was taken, counts[8 * plane + case] with case 0 = all in,
+ * 1-3 = only v0 / v1 / v2 in, 4-6 = only v2 / v1 / v0 out, 7 = dropped (plane 5 counts 0 or 7). */
+static uint64_t *g_case_counts;
+void cgo_rast_clip_case_counts(uint64_t *counts) { g_case_counts = counts; }
+#define CASE(k) do { if (g_case_counts) g_case_counts[8 * plane + (k)]++; } while (0)
+
 /* Apply one of the 7 reference cases given in/out predicates and edge params. */
 static int clip_cases(cgo_rast_tri t, const int *I, const int *O, float tp[3][3],
-                      cgo_rast_tri *out, int n, int cap, int quirk6_v02, float quirk6_t21)
+                      cgo_rast_tri *out, int n, int cap, int quirk6_v02, float quirk6_t21, int plane)
 {
-    if (I[0] && I[1] && I[2]) return push(out, n, cap, &t);
+    if (I[0] && I[1] && I[2]) { CASE(0); return push(out, n, cap, &t); }
     if (I[0] && O[1] && O[2]) {
+        CASE(1);
         cgo_v4 v0 = t.v0, v1 = t.v1, v2 = t.v2;
         t.v1 = lerp_from(v0, v1, tp[0][1]);
         t.v2 = lerp_from(v0, v2, tp[0][2]);
         return push(out, n, cap, &t);
     }
     if (O[0] && I[1] && O[2]) {
+        CASE(2);
         cgo_v4 v0 = t.v0, v1 = t.v1, v2 = t.v2;
         t.v0 = lerp_from(v1, v0, tp[1][0]);
         t.v2 = lerp_from(v1, v2, tp[1][2]);
         return push(out, n, cap, &t);
     }
     if (O[0] && O[1] && I[2]) {
+        CASE(3);
         cgo_v4 v0 = t.v0, v1 = t.v1, v2 = t.v2;
         t.v1 = lerp_from(v2, v1, tp[2][1]);
         t.v0 = lerp_from(v2, v0, tp[2][0]);
         return push(out, n, cap, &t);
     }
     if (I[0] && I[1] && O[2]) {
+        CASE(4);
         cgo_v4 p12 = lerp_from(t.v1, t.v2, tp[1][2]);
         cgo_v4 p02 = lerp_from(t.v0, t.v2, tp[0][2]);
         t.v2 = p02;
@@ -242,6 +252,7 @@ static int clip_cases(cgo_rast_tri t, const int *I, const int *O, float tp[3][3]
         return push(out, n, cap, &e);
     }
     if (I[0] && O[1] && (quirk6_v02 >= 0 ? quirk6_v02 : I[2])) {
+        CASE(5);
         cgo_v4 p01 = lerp_from(t.v0, t.v1, tp[0][1]);
         cgo_v4 p21 = lerp_from(t.v2, t.v1, quirk6_v02 >= 0 ? quirk6_t21 : tp[2][1]);
         t.v1 = p01;
@@ -250,6 +261,7 @@ static int clip_cases(cgo_rast_tri t, const int *I, const int *O, float tp[3][3]
         return push(out, n, cap, &e);
     }
     if (O[0] && I[1] && I[2]) {
+        CASE(6);
         cgo_v4 p10 = lerp_from(t.v1, t.v0, tp[1][0]);
         cgo_v4 p20 = lerp_from(t.v2, t.v0, tp[2][0]);
         t.v0 = p10;
@@ -257,8 +269,10 @@ static int clip_cases(cgo_rast_tri t, const int *I, const int *O, float tp[3][3]
         n = push(out, n, cap, &t);
         return push(out, n, cap, &e);
     }
+    CASE(7);
     return n;   /* all out (or NaN): dropped */
 }
+#undef CASE
 
 int cgo_rast_clip(const cgo_rast_tri *in, int cnt, int plane, const cgo_rast_params *p,
                   cgo_rast_tri *out, int cap)
@@ -267,7 +281,9 @@ int cgo_rast_clip(const cgo_rast_tri *in, int cnt, int plane, const cgo_rast_par
     for (int i = 0; i < cnt; ++i) {
         const cgo_rast_tri *t = &in[i];
         if (plane == 5) {                                       /* :1497-1505 */
-            if (t->v0.z > 0.01f && t->v1.z > 0.01f && t->v2.z > 0.01f) n = push(out, n, cap, t);
+            const int in5 = t->v0.z > 0.01f && t->v1.z > 0.01f && t->v2.z > 0.01f;
+            if (g_case_counts) g_case_counts[8 * 5 + (in5 ? 0 : 7)]++;
+            if (in5) n = push(out, n, cap, t);
             continue;
         }
         if (plane == 6) {                                       /* :1507-1670 */
@@ -281,29 +297,29 @@ int cgo_rast_clip(const cgo_rast_tri *in, int cnt, int plane, const cgo_rast_par
                     tp[a][b] = (a == b) ? 0.0f : (wl - w[a]) / (w[b] - w[a]);
             float t21q = (wl - w[2]) / (w[1] - w[0]);           /* :1615 quirk */
             int q = t->v2.x <= wl;                              /* :1607 quirk */
-            n = clip_cases(*t, I, O, tp, out, n, cap, q, t21q);
+            n = clip_cases(*t, I, O, tp, out, n, cap, q, t21q, 6);
             continue;
         }
         clipinfo ci;
         clip_info(t, plane, p, &ci);
-        n = clip_cases(*t, ci.in, ci.out, ci.tp, out, n, cap, -1, 0.0f);
+        n = clip_cases(*t, ci.in, ci.out, ci.tp, out, n, cap, -1, 0.0f, plane);
     }
     return n;
 }
 
 /* ---------------------------- geometry --------------------------------- */
 
-/* skeleton.cpp:205-241 (Draw's host part) */
-int cgo_rast_geometry(const cgo_rast_params *p, cgo_rast_tri *out, int cap, cgo_v4 *light_out)
+/* skeleton.cpp:205-241 (Draw's host part) on a caller's room and boxes; the records' texture
+ * fields stand.  The two lists grow with the scene: a box brings 7 triangles (itself and its
+ * shadow volume), a clip plane at most doubles a list. */
+int cgo_rast_geometry_scene(const cgo_rast_params *p, const cgo_rast_tri *room, int nr,
+                            const cgo_rast_tri *boxes, int nb, cgo_rast_tri *out, int cap,
+                            cgo_v4 *light_out)
 {
-    cgo_rast_tri room[16], boxes[32];
-    int nr, nb;
-    cgo_rast_load_scene(room, &nr, boxes, &nb);
-    for (int i = 0; i < nr; ++i) room[i].texture = p->setting;          /* TestModelH.h:85-129 */
-    for (int i = 0; i < nb; ++i) boxes[i].texture = p->setting_boxes;   /* TestModelH.h:148-260 */
-    enum { MAXT = 8192 };
-    cgo_rast_tri *A = (cgo_rast_tri *)malloc(sizeof(cgo_rast_tri) * MAXT);
-    cgo_rast_tri *B = (cgo_rast_tri *)malloc(sizeof(cgo_rast_tri) * MAXT);
+    size_t cap_ab = (size_t)nr + 7 * (size_t)nb;
+    if (cap_ab < 64) cap_ab = 64;
+    cgo_rast_tri *A = (cgo_rast_tri *)malloc(sizeof(cgo_rast_tri) * cap_ab);
+    cgo_rast_tri *B = (cgo_rast_tri *)malloc(sizeof(cgo_rast_tri) * cap_ab);
     int n = 0;
     /* toCameraSpace (:701-716) */
     for (int i = 0; i < nr; ++i) A[n++] = room[i];
@@ -346,17 +362,38 @@ int cgo_rast_geometry(const cgo_rast_params *p, cgo_rast_tri *out, int cap, cgo_
     }
     /* clip planes 1..6 (:236-241) */
     for (int plane = 1; plane <= 6; ++plane) {
-        int k = cgo_rast_clip(A, n, plane, p, B, MAXT);
-        if (k > MAXT) k = MAXT;
+        if (2 * (size_t)n > cap_ab) {                       /* B must hold the plane's output */
+            cap_ab = 2 * (size_t)n;
+            A = (cgo_rast_tri *)realloc(A, sizeof(cgo_rast_tri) * cap_ab);
+            free(B);
+            B = (cgo_rast_tri *)malloc(sizeof(cgo_rast_tri) * cap_ab);
+        }
+        int k = cgo_rast_clip(A, n, plane, p, B, (int)cap_ab);
         cgo_rast_tri *tmp = A; A = B; B = tmp;
         n = k;
     }
     int w = n < cap ? n : cap;
-    if (out) memcpy(out, A, sizeof(cgo_rast_tri) * (size_t)w);
+    if (out && w > 0) memcpy(out, A, sizeof(cgo_rast_tri) * (size_t)w);
     if (light_out) *light_out = lightPos;
     free(A);
     free(B);
     return n;
+}
+
+/* The reference scene: LoadTestModel with the texture setting applied. */
+static void reference_scene(const cgo_rast_params *p, cgo_rast_tri *room, int *nr, cgo_rast_tri *boxes, int *nb)
+{
+    cgo_rast_load_scene(room, nr, boxes, nb);
+    for (int i = 0; i < *nr; ++i) room[i].texture = p->setting;          /* TestModelH.h:85-129 */
+    for (int i = 0; i < *nb; ++i) boxes[i].texture = p->setting_boxes;   /* TestModelH.h:148-260 */
+}
+
+int cgo_rast_geometry(const cgo_rast_params *p, cgo_rast_tri *out, int cap, cgo_v4 *light_out)
+{
+    cgo_rast_tri room[16], boxes[32];
+    int nr, nb;
+    reference_scene(p, room, &nr, boxes, &nb);
+    return cgo_rast_geometry_scene(p, room, nr, boxes, nb, out, cap, light_out);
 }
 
 /* ---------------------------- raster ----------------------------------- */
@@ -661,21 +698,20 @@ static void pixel_shader(rast_state *s, const cgo_pixel *px, const cgo_rast_tri 
 
 static inline cgo_v3 ld3(const float *b, size_t o) { return v3(b[3 * o], b[3 * o + 1], b[3 * o + 2]); }
 
-/* skeleton.cpp:203-308 */
-void cgo_rast_draw(const cgo_rast_params *p, uint32_t *argb, float *depth, int32_t *shadow,
-                   float *screen_buf, float *low_buf, float *high_buf, cgo_rast_counters *cnt)
+/* skeleton.cpp:243-308: Draw from the buffer clears on, for an already clipped list and the
+ * light position in rotated camera space. */
+void cgo_rast_draw_list(const cgo_rast_params *p, const cgo_rast_tri *tris, int n, cgo_v4 light,
+                        uint32_t *argb, float *depth, int32_t *shadow,
+                        float *screen_buf, float *low_buf, float *high_buf, cgo_rast_counters *cnt)
 {
     const int W = p->width, H = p->height;
     const size_t npx = (size_t)W * H;
-    enum { CAP = 8192 };
-    cgo_rast_tri *tris = (cgo_rast_tri *)malloc(sizeof(cgo_rast_tri) * CAP);
     rast_state s;
     memset(&s, 0, sizeof(s));
     s.p = p;
     s.cnt = cnt;
     cgo_mat4_inverse(p->R, s.Rinv);
-    int n = cgo_rast_geometry(p, tris, CAP, &s.lightPos);
-    if (n > CAP) n = CAP;
+    s.lightPos = light;
     s.depth = depth ? depth : (float *)malloc(sizeof(float) * npx);
     s.shadow = shadow ? shadow : (int32_t *)malloc(sizeof(int32_t) * npx);
     s.screen = screen_buf ? screen_buf : (float *)malloc(sizeof(float) * 3 * npx);
@@ -759,11 +795,34 @@ void cgo_rast_draw(const cgo_rast_params *p, uint32_t *argb, float *depth, int32
             out[o] = cgo_put_pixel(val);
         }
     }
-    free(line); free(left); free(right); free(tris);
+    free(line); free(left); free(right);
     if (!depth) free(s.depth);
     if (!shadow) free(s.shadow);
     if (!screen_buf) free(s.screen);
     if (!low_buf) free(s.low);
     if (!high_buf) free(s.high);
     if (!argb) free(out);
+}
+
+/* skeleton.cpp:203-308 on a caller's room and boxes */
+void cgo_rast_draw_scene(const cgo_rast_params *p, const cgo_rast_tri *room, int nr,
+                         const cgo_rast_tri *boxes, int nb, uint32_t *argb, float *depth, int32_t *shadow,
+                         float *screen_buf, float *low_buf, float *high_buf, cgo_rast_counters *cnt)
+{
+    cgo_v4 light;
+    int n = cgo_rast_geometry_scene(p, room, nr, boxes, nb, 0, 0, &light);
+    cgo_rast_tri *tris = (cgo_rast_tri *)malloc(sizeof(cgo_rast_tri) * (size_t)(n > 0 ? n : 1));
+    n = cgo_rast_geometry_scene(p, room, nr, boxes, nb, tris, n, &light);
+    cgo_rast_draw_list(p, tris, n, light, argb, depth, shadow, screen_buf, low_buf, high_buf, cnt);
+    free(tris);
+}
+
+/* skeleton.cpp:203-308 */
+void cgo_rast_draw(const cgo_rast_params *p, uint32_t *argb, float *depth, int32_t *shadow,
+                   float *screen_buf, float *low_buf, float *high_buf, cgo_rast_counters *cnt)
+{
+    cgo_rast_tri room[16], boxes[32];
+    int nr, nb;
+    reference_scene(p, room, &nr, boxes, &nb);
+    cgo_rast_draw_scene(p, room, nr, boxes, nb, argb, depth, shadow, screen_buf, low_buf, high_buf, cnt);
 }

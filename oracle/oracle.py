@@ -125,6 +125,14 @@ def load():
         "cgo_rast_default_params": (None, [C.POINTER(RastParams), C.c_int, C.c_int]),
         "cgo_rast_geometry": (C.c_int, [C.POINTER(RastParams), C.POINTER(RastTri), C.c_int,
                                         C.POINTER(V4)]),
+        "cgo_rast_geometry_scene": (C.c_int, [C.POINTER(RastParams), C.POINTER(RastTri), C.c_int,
+                                              C.POINTER(RastTri), C.c_int, C.POINTER(RastTri), C.c_int,
+                                              C.POINTER(V4)]),
+        "cgo_rast_draw_scene": (None, [C.POINTER(RastParams), C.POINTER(RastTri), C.c_int, C.POINTER(RastTri),
+                                       C.c_int, P, P, P, P, P, P, C.POINTER(RastCounters)]),
+        "cgo_rast_draw_list": (None, [C.POINTER(RastParams), C.POINTER(RastTri), C.c_int, V4,
+                                      P, P, P, P, P, P, C.POINTER(RastCounters)]),
+        "cgo_rast_clip_case_counts": (None, [P]),
         "cgo_rast_polygon_rows": (C.c_int, [C.POINTER(Pixel), C.POINTER(Pixel), C.POINTER(Pixel),
                                             C.c_int]),
         "cgo_rast_interpolate": (None, [Pixel, Pixel, C.POINTER(Pixel), C.c_int]),
@@ -321,23 +329,96 @@ def jpeg_decode(data: bytes) -> np.ndarray:
     return out if nc.value == 3 else out[:, :, 0]
 
 
-def rast_geometry(p):
+def rast_tris(tris, n=None):
+    """A RastTri array from anything with the 84-byte record layout (the library's RTri array, a
+    numpy array, bytes); an existing RastTri array passes through."""
+    if isinstance(tris, C.Array) and tris._type_ is RastTri:
+        return tris
+    raw = bytes(tris) if not isinstance(tris, np.ndarray) else tris.tobytes()
+    k = len(raw) // C.sizeof(RastTri) if n is None else n
+    arr = (RastTri * max(k, 1))()
+    C.memmove(arr, raw, k * C.sizeof(RastTri))
+    return arr
+
+
+def _rast_scene(scene):
+    room, nr, boxes, nb = scene
+    return rast_tris(room, nr), nr, rast_tris(boxes, nb), nb
+
+
+def rast_geometry(p, scene=None):
+    """Draw's host part: (clipped RastTri array, n, light V4).  scene = (room, n_room, boxes,
+    n_boxes) as cg_rast_set_scene takes them (the records' texture fields stand); default
+    LoadTestModel with p's texture settings."""
     lib = load()
-    out = (RastTri * 8192)()
     light = V4()
-    n = lib.cgo_rast_geometry(C.byref(p), out, 8192, C.byref(light))
+    if scene is None:
+        n = lib.cgo_rast_geometry(C.byref(p), None, 0, C.byref(light))
+        out = (RastTri * max(n, 1))()
+        n = lib.cgo_rast_geometry(C.byref(p), out, n, C.byref(light))
+        return out, n, light
+    room, nr, boxes, nb = _rast_scene(scene)
+    n = lib.cgo_rast_geometry_scene(C.byref(p), room, nr, boxes, nb, None, 0, C.byref(light))
+    out = (RastTri * max(n, 1))()
+    n = lib.cgo_rast_geometry_scene(C.byref(p), room, nr, boxes, nb, out, n, C.byref(light))
     return out, n, light
 
 
-def rast_draw(p, counters=False):
-    """Full RAST frame: (argb uint32, depth float32, shadow int32) planes of W*H."""
+def rast_clip_cases(p, scene=None):
+    """How often Draw's clip takes each case on this frame: uint64 (7, 8), [plane 1-6][case] with
+    case 0 = all in, 1-3 = only v0 / v1 / v2 in, 4-6 = only v2 / v1 / v0 out, 7 = dropped."""
     lib = load()
+    counts = np.zeros(56, np.uint64)
+    lib.cgo_rast_clip_case_counts(counts.ctypes.data_as(C.c_void_p))
+    try:
+        if scene is None:
+            lib.cgo_rast_geometry(C.byref(p), None, 0, None)
+        else:
+            room, nr, boxes, nb = _rast_scene(scene)
+            lib.cgo_rast_geometry_scene(C.byref(p), room, nr, boxes, nb, None, 0, None)
+    finally:
+        lib.cgo_rast_clip_case_counts(None)
+    return counts.reshape(7, 8)
+
+
+def _rast_planes(p, buffers):
     npx = p.width * p.height
-    argb = np.zeros(npx, np.uint32)
-    depth = np.zeros(npx, np.float32)
-    shadow = np.zeros(npx, np.int32)
+    out = {"argb": np.zeros(npx, np.uint32), "depth": np.zeros(npx, np.float32), "shadow": np.zeros(npx, np.int32)}
+    if buffers:
+        out.update({k: np.zeros((npx, 3), np.float32) for k in ("screen", "low", "high")})
+    ptrs = [out[k].ctypes.data_as(C.c_void_p) if k in out else None
+            for k in ("argb", "depth", "shadow", "screen", "low", "high")]
+    return out, ptrs
+
+
+def _rast_result(out, cnt, counters, buffers):
+    if buffers:
+        return (out, cnt) if counters else out
+    planes = (out["argb"], out["depth"], out["shadow"])
+    return planes + (cnt,) if counters else planes
+
+
+def rast_draw(p, counters=False, scene=None, buffers=False):
+    """Full RAST frame: (argb uint32, depth float32, shadow int32) planes of W*H; with buffers a
+    dict of those and the float screen / low / high buffers (W*H, 3).  scene as in rast_geometry."""
+    lib = load()
+    out, ptrs = _rast_planes(p, buffers)
     cnt = RastCounters()
-    vp = C.c_void_p
-    lib.cgo_rast_draw(C.byref(p), argb.ctypes.data_as(vp), depth.ctypes.data_as(vp),
-                      shadow.ctypes.data_as(vp), None, None, None, C.byref(cnt))
-    return (argb, depth, shadow, cnt) if counters else (argb, depth, shadow)
+    if scene is None:
+        lib.cgo_rast_draw(C.byref(p), *ptrs, C.byref(cnt))
+    else:
+        room, nr, boxes, nb = _rast_scene(scene)
+        lib.cgo_rast_draw_scene(C.byref(p), room, nr, boxes, nb, *ptrs, C.byref(cnt))
+    return _rast_result(out, cnt, counters, buffers)
+
+
+def rast_draw_list(p, tris, n, light, counters=False, buffers=False):
+    """Draw from the buffer clears on, for an already clipped list and the light in rotated
+    camera space (what cg_rast_render takes); results as rast_draw."""
+    lib = load()
+    out, ptrs = _rast_planes(p, buffers)
+    cnt = RastCounters()
+    lt = light if isinstance(light, V4) else V4(light.x, light.y, light.z, light.w) if hasattr(light, "x") \
+        else V4(*light)
+    lib.cgo_rast_draw_list(C.byref(p), rast_tris(tris, n), n, lt, *ptrs, C.byref(cnt))
+    return _rast_result(out, cnt, counters, buffers)

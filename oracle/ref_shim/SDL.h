@@ -18,6 +18,11 @@
  *   CG_REF_SETTING / CG_REF_SETTING_BOXES   (-DCG_REF_RAST) the rasteriser's texture modes.
  *   CG_REF_BOX_INDEX                 (-DCG_REF_RAST) value for the one Triangle::index that the
  *                                    reference leaves uninitialised (see below); unset = untouched.
+ *   CG_REF_CAM / CG_REF_FOCAL / CG_REF_LIGHT   (-DCG_REF_RT, -DCG_REF_RAST) start values of cameraPos
+ *                                    ("x,y,z"), focalLength and the light's position ("x,y,z":
+ *                                    lights[0].position / sceneCoordinatesLightPos), given to the
+ *                                    program's globals before the first key is handled; unset =
+ *                                    untouched.  For the scene-loading builds (ref_shim/scene/).
  *
  * Build with exactly one of -DCG_REF_RT, -DCG_REF_RAST, -DCG_REF_STAR.  glm is included before
  * this header by all three programs, so their globals can be declared extern here.
@@ -163,6 +168,45 @@ template <class V> static inline void cg_ref_shim_put_light(const V &v, FILE *f)
 {
     fwrite(&v[0].position, sizeof(float), 4, f);
 }
+template <class V> static inline void cg_ref_shim_set_light(V &v, const float *xyz)
+{
+    if (!v.empty()) {
+        v[0].position.x = xyz[0]; v[0].position.y = xyz[1]; v[0].position.z = xyz[2];
+    }
+}
+#endif
+
+#if defined(CG_REF_RT) || defined(CG_REF_RAST)
+static inline bool cg_ref_shim_xyz(const char *name, float *xyz)
+{
+    const char *v = getenv(name);
+    if (!v)
+        return false;
+    if (sscanf(v, "%f,%f,%f", &xyz[0], &xyz[1], &xyz[2]) != 3) {
+        fprintf(stderr, "%s: expected x,y,z\n", name);
+        exit(3);
+    }
+    return true;
+}
+
+/* Start values for the programs' globals, at the first SDL_PollEvent: the model is loaded (and the
+ * raytracer's light exists), nothing is drawn and no key is handled yet.  w stays 1. */
+static inline void cg_ref_shim_start_values()
+{
+    float v[3];
+    if (cg_ref_shim_xyz("CG_REF_CAM", v)) {
+        cameraPos.x = v[0]; cameraPos.y = v[1]; cameraPos.z = v[2];
+    }
+    if (const char *f = getenv("CG_REF_FOCAL"))
+        focalLength = strtof(f, 0);
+    if (cg_ref_shim_xyz("CG_REF_LIGHT", v)) {
+#if defined(CG_REF_RT)
+        cg_ref_shim_set_light(lights, v);
+#else
+        sceneCoordinatesLightPos.x = v[0]; sceneCoordinatesLightPos.y = v[1]; sceneCoordinatesLightPos.z = v[2];
+#endif
+    }
+}
 #endif
 
 static inline void cg_ref_shim_dump_state()
@@ -207,6 +251,10 @@ static inline int SDL_PollEvent(SDL_Event *e)
 #if defined(CG_REF_RAST)
     if (s.key_pos == 0 && !s.key_given)     /* first Update(): the model is loaded, nothing drawn yet */
         cg_ref_shim_define_box_index(originalbox);
+#endif
+#if defined(CG_REF_RT) || defined(CG_REF_RAST)
+    if (s.key_pos == 0 && !s.key_given)
+        cg_ref_shim_start_values();
 #endif
     if (s.key_given) {                  /* second call of this Update(): queue empty */
         s.key_given = false;

@@ -128,9 +128,10 @@ def write_bgr_maps(workdir):
             f.write(np.ascontiguousarray(img).tobytes())
 
 
-def run_session(name, spec, binaries, workdir):
+def run_session(name, spec, binaries, workdir, extra_env=None):
     """Run one session of a reference binary in workdir (which holds Textures/ when the session is
-    textured).  -> (frames, screenshot ARGB or None); frames = [{"state": ..., plane: sha}]."""
+    textured).  -> (frames, screenshot ARGB or None); frames = [{"state": ..., plane: sha}].
+    extra_env: further variables for the binary ({name: value}; None removes one set here)."""
     prog = spec["program"]
     W, H = SIZES[prog]
     npx = W * H
@@ -142,6 +143,11 @@ def run_session(name, spec, binaries, workdir):
                    CG_REF_BOX_INDEX=str(UNSET_BOX_INDEX))
     if "dts" in spec:
         env["CG_REF_TICKS"] = ",".join(str(t) for t in star_ticks(spec["dts"]))
+    for k, v in (extra_env or {}).items():
+        if v is None:
+            env.pop(k, None)
+        else:
+            env[k] = v
     run = os.path.join(workdir, name + ".run")       # the program writes screenshot.bmp into its cwd
     os.makedirs(run, exist_ok=True)
     if textured(spec):

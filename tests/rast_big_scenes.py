@@ -51,6 +51,28 @@ def camera_list(n, W, H, focal, rows, rng):
     return t
 
 
+def oracle_params(p):
+    """The oracle's parameter record of the frame a cgamd.RastParams describes."""
+    import oracle
+    v4 = lambda v: (v.x, v.y, v.z, v.w)   # noqa: E731
+    return oracle.rast_params(p.width, p.height, p.focal, v4(p.camera), list(p.R), v4(p.light_scene),
+                              p.indirect_first, p.colour_mode, p.rand_offset, yaw=p.yaw)
+
+
+def oracle_scene_frame(p, room, nr, boxes, nb):
+    """(argb, depth, shadow, counters): the oracle's Draw of a caller's room and boxes -- its own
+    clip, its own fill; nothing of the library's."""
+    import oracle
+    return oracle.rast_draw(oracle_params(p), counters=True, scene=(room, nr, boxes, nb))
+
+
+def oracle_list_frame(p, tris, n, light):
+    """(argb, depth, shadow, counters): the oracle's Draw of an already clipped list (what
+    cg_rast_render takes)."""
+    import oracle
+    return oracle.rast_draw_list(oracle_params(p), tris, n, light, counters=True)
+
+
 def scratch_need(n_in, info, W, H, chunk):
     """Device bytes per buffer that one compact-route cg_rast_draw frame needs: a formula of the
     frame's own counts (cg_rast_scratch_info out[2..4]) and the struct sizes.  Triangle 84 B,

@@ -57,9 +57,11 @@ def triangle_lines(lib, po, T):
         yield np.frombuffer(line, PIXEL)[:N - 1]
 
 
-def owner_planes(params, tris, n, W, H):
+def owner_planes(params, tris, n, W, H, shadow_marks=True):
     """(depth float32, shadow int32, clip int32, pos float32[., 4]) of W * H pixels for an
-    untextured clipped list: the ordered z-buffer by hand.  params: the oracle's or cgamd's."""
+    untextured clipped list: the ordered z-buffer by hand.  params: the oracle's or cgamd's.
+    Without shadow_marks the shadow-volume triangles are skipped (they never own a pixel or
+    write depth) and the shadow plane stays zero: for lists whose volumes cover the frame."""
     lib = _lib()
     po = oracle_params(params)
     assert (po.width, po.height) == (W, H)
@@ -71,6 +73,8 @@ def owner_planes(params, tris, n, W, H):
         T = tris[i]
         assert T.texture == 0, "untextured lists only"
         shades = T.color.x >= 0
+        if not shades and not shadow_marks:
+            continue
         for line in triangle_lines(lib, po, T):
             line = line[(line["x"] >= 0) & (line["x"] < W) & (line["y"] >= 0) & (line["y"] < H)]
             if not line.size:

@@ -1,5 +1,6 @@
 """GPU: colour modes 1-2 (the random-colour and night-vision modes) on the rasteriser's compact
-route -- against the oracle on the reference scene and against the dense route everywhere else.
+route -- against the oracle on the reference scene, on meshes and on clipped lists
+(oracle.rast_draw(scene=...) / oracle.rast_draw_list), and beside it against the dense route.
 cg_rast_set_route_limit(ctx, 1) makes every frame with a non-empty list an automatic compact
 frame, so the kernels are reached at small shapes.  Every comparison covers all three planes on
 every pixel at tolerance 0 (ARGB, depth as float bits, shadow), plus n_shaded."""
@@ -62,7 +63,7 @@ def _compact_render(ctx, tris, n, p, light):
 
 
 def _dense_of_prepared(ctx, p, room, nr, boxes, nb):
-    """The checker away from the reference scene: clip on the host, render the list densely."""
+    """The library's other route on a mesh: clip on the host, render the list densely."""
     tris, n, light = cgamd.rast_prepare(p, room, nr, boxes, nb)
     return _dense_render(ctx, tris, n, p, light), n
 
@@ -70,6 +71,13 @@ def _dense_of_prepared(ctx, p, room, nr, boxes, nb):
 def _same_frame(got, ref, what):
     _same(got[:3], ref[:3], what)
     assert got[3].n_shaded == ref[3].n_shaded, f"{what}: n_shaded {got[3].n_shaded} != {ref[3].n_shaded}"
+
+
+def _same_as_oracle(got, ora, what):
+    """ora: rast_big_scenes.oracle_scene_frame / oracle_list_frame -- planes and the shaded count."""
+    _same(got[:3], ora[:3], what + " against the oracle")
+    if got[3].n_shaded >= 0:                                  # -1: a colour mode 0 frame does not count
+        assert got[3].n_shaded == ora[3].n_shaded, f"{what}: n_shaded {got[3].n_shaded}, the oracle {ora[3].n_shaded}"
 
 
 def test_route_limit_hook(cctx):
@@ -148,7 +156,31 @@ def test_beyond_the_dense_limit(cctx, mode):
     info = cctx.rast_scratch_info()
     assert info["route"] == COMPACT and info["tris"] == n
     _same_frame(got, ref, f"6000-triangle room, mode {mode}")
+    _same_as_oracle(got, sc.oracle_scene_frame(p, room, B["n"], NO_BOXES, 0), f"6000-triangle room, mode {mode}")
     assert got[3].n_shaded > 0
+
+
+@pytest.mark.parametrize("mode", [1, 2])
+def test_between_the_colour_limit_and_the_dense_limit(cctx, mode):
+    """700 inputs: a list capacity of 22,400, within the dense route's 131,072 but beyond the 20,480
+    slots its colour fill counts in LDS.  The automatic choice is the compact route in modes 1-2
+    (before, such a frame failed with "colour count launch: invalid argument") and still the dense
+    one in mode 0; a forced dense route says why it cannot."""
+    W, H, F, n = 96, 48, 48.0, 700
+    room = cgamd.rast_random_scene(n, 0.3, seed=0x70C)
+    p = cgamd.rast_params(W, H, F, colour_mode=mode, rand_offset=31)
+    assert cgamd.rast_route(32 * n) == DENSE
+    cctx.rast_set_scene(room, n, NO_BOXES, 0)
+    got = cctx.rast_draw(p)
+    assert cctx.rast_scratch_info()["route"] == COMPACT
+    _same_as_oracle(got, sc.oracle_scene_frame(p, room, n, NO_BOXES, 0), f"700-triangle room, mode {mode}")
+    assert got[3].n_shaded > 0
+    p0 = cgamd.rast_params(W, H, F)
+    m0 = cctx.rast_draw(p0)
+    assert cctx.rast_scratch_info()["route"] == DENSE
+    _same_as_oracle(m0, sc.oracle_scene_frame(p0, room, n, NO_BOXES, 0), "700-triangle room, mode 0")
+    with forced(cctx, DENSE), pytest.raises(RuntimeError, match="dense route: colour modes"):
+        cctx.rast_draw(p)
 
 
 # ---- 3. shadow volumes -------------------------------------------------------------------------
@@ -165,6 +197,7 @@ def test_shadow_volumes(cctx):
     info = cctx.rast_scratch_info()
     assert info["route"] == COMPACT and info["tris"] == n
     _same_frame(got, ref, "700 boxes with shadow volumes, mode 1")
+    _same_as_oracle(got, sc.oracle_scene_frame(p, room, nr, boxes, 700), "700 boxes with shadow volumes, mode 1")
 
 
 # ---- 4. numbering across segment and block boundaries ------------------------------------------
@@ -182,6 +215,10 @@ def test_numbering_across_segments(cctx, which, form):
     got = _compact_render(cctx, tris, n, p, LIGHT)
     assert cctx.rast_scratch_info()["spans"] == n * 7
     _same_frame(got, ref, f"{which} {form}")
+    # the oracle walks rand() call by call, so it checks the same list at a small index
+    small = cgamd.rast_params(W, H, F, colour_mode=1, rand_offset=5)
+    _same_as_oracle(_compact_render(cctx, tris, n, small, LIGHT), sc.oracle_list_frame(small, tris, n, LIGHT),
+                    f"{which} {form} at rand() index 5")
     # ties shade twice: more fragments drew than the final frame shows
     assert got[3].n_shaded > np.count_nonzero(got[1])
     # the order matters: one fragment further along the stream, every colour changes
@@ -212,6 +249,7 @@ def test_long_row_at_the_dense_limit(cctx):
     info = cctx.rast_scratch_info()
     assert info["spans"] == n and info["recs"] > 0.9 * n
     _same_frame(got, ref, f"{n} triangles on row 3")
+    _same_as_oracle(got, sc.oracle_list_frame(p, tris, n, LIGHT), f"{n} triangles on row 3")
 
 
 def test_long_row_beyond_the_dense_limit(cctx):
@@ -329,6 +367,7 @@ def test_degenerate_scenes(cctx):
         if route is not None:
             assert info["route"] == route, name
         _same_frame(got, ref, name)
+        _same_as_oracle(got, sc.oracle_scene_frame(p1, room, nr, NO_BOXES, 0), name)
         rec = info_d.cpu().numpy().view(cgamd.RAST_SEQ_DTYPE)
         assert int(rec["n_shaded"][0]) == got[3].n_shaded and not rec["status"].any()
         assert int(rec["rand_offset"][1]) == 99 + 3 * got[3].n_shaded

@@ -1,7 +1,9 @@
 """GPU: the rasteriser's compact route (cg_rast_big.hip) -- scratch and work that follow what the
-frame covers -- against the oracle on the reference scene and against the dense route (the
-kernels the oracle pins) everywhere else.  Every comparison covers all three planes on every
-pixel at tolerance 0: ARGB, depth as float bits, shadow."""
+frame covers -- against the oracle, on the reference scene and on meshes and clipped lists
+(oracle.rast_draw(scene=...) / oracle.rast_draw_list: the oracle's own clip and fill, which
+tests/test_ref_scene_sessions.py holds to the reference program on meshes), and beside it against
+the dense route.  Every comparison covers all three planes on every pixel at tolerance 0: ARGB,
+depth as float bits, shadow."""
 import ctypes as C
 
 import numpy as np
@@ -52,7 +54,7 @@ def _render(ctx, route, tris, n, p, light):
 
 
 def _dense_of_prepared(ctx, p, room, nr, boxes, nb):
-    """The checker away from the reference scene: clip on the host, render the list densely."""
+    """The library's other route on a mesh: clip on the host, render the list densely."""
     tris, n, light = cgamd.rast_prepare(p, room, nr, boxes, nb)
     return _render(ctx, DENSE, tris, n, p, light), n
 
@@ -136,6 +138,7 @@ def test_beyond_the_old_limit(bctx):
     info = bctx.rast_scratch_info()
     assert info["route"] == COMPACT and info["tris"] == n
     _same((a, d, s), (ra, rd, rs), "6000-triangle room")
+    _same((a, d, s), sc.oracle_scene_frame(p, room, B["n"], NO_BOXES, 0)[:3], "6000-triangle room against the oracle")
     assert (st.n_tris, st.n_spans) == (rst.n_tris, rst.n_spans) == (n, rst.n_spans)
     # a forced dense Draw of this scene fails as cg_rast_set_scene did
     with pytest.raises(RuntimeError, match="dense route"):
@@ -155,6 +158,7 @@ def test_shadow_volumes(bctx):
     info = bctx.rast_scratch_info()
     assert info["route"] == COMPACT and info["tris"] == n
     _same((a, d, s), (ra, rd, rs), "700 boxes with shadow volumes")
+    _same((a, d, s), sc.oracle_scene_frame(p, room, nr, boxes, 700)[:3], "700 boxes against the oracle")
 
 
 # ---- 4. record order across the row-list passes' block boundaries ------------------------------
@@ -187,6 +191,7 @@ def test_order_across_block_boundaries(bctx, which, form, rows):
     assert info["route"] == COMPACT and info["tris"] == n
     assert info["spans"] == n * (rows[1] - rows[0] + 1)
     _same(got[:3], ref[:3], f"{which} {form} rows {rows}")
+    _same(got[:3], sc.oracle_list_frame(p, tris, n, light)[:3], f"{which} {form} rows {rows} against the oracle")
     # the ties are real: swapping the two colours of every pair changes the frame
     sw = t.copy()
     k = np.arange(n - n % 2)
@@ -209,6 +214,7 @@ def test_long_row_takes_the_32_bit_state(bctx):
     assert info["spans"] == n and info["recs"] >= 32768
     assert got[1].reshape(H, W)[3].any() and not np.delete(got[1].reshape(H, W), 3, 0).any()
     _same(got[:3], ref[:3], "40,000 triangles on row 3")
+    _same(got[:3], sc.oracle_list_frame(p, tris, n, light)[:3], "40,000 triangles on row 3 against the oracle")
 
 
 # ---- 6. degenerate inputs -----------------------------------------------------------------------
@@ -236,10 +242,12 @@ def test_degenerate_scenes(bctx):
             # fewer spans than three a triangle
             assert 0 < info["recs"] < info["spans"] < 3 * info["tris"]
         _same(got[:3], ref[:3], name)
+        _same(got[:3], sc.oracle_scene_frame(pp, r, nr, NO_BOXES, 0)[:3], f"{name} against the oracle")
     # an empty list through cg_rast_render
     ref = _render(bctx, DENSE, NO_BOXES, 0, p, cgamd.Vec4(0, 0, 0, 1))
     got = _render(bctx, COMPACT, NO_BOXES, 0, p, cgamd.Vec4(0, 0, 0, 1))
     _same(got[:3], ref[:3], "empty list")
+    _same(got[:3], sc.oracle_list_frame(p, NO_BOXES, 0, cgamd.Vec4(0, 0, 0, 1))[:3], "empty list against the oracle")
 
 
 # ---- 7. scratch scales with the frame -----------------------------------------------------------

@@ -2,7 +2,8 @@
 routes.  Every comparison covers every pixel at tolerance 0, floats compared as bits: the float
 planes and the picture against the oracle's cgo_rast_draw, the owner's clip / pos against the
 ordered z-buffer restated over the oracle's primitives (rast_owner_ref.owner_planes), tri against
-host-only cg_rast_prepare counts (rast_owner_ref.input_of_clip)."""
+host-only cg_rast_prepare counts (rast_owner_ref.input_of_clip).  The caller's list and the mesh
+are drawn by the oracle too (oracle.rast_draw_list / oracle.rast_draw(scene=...))."""
 import ctypes as C
 import functools
 
@@ -188,6 +189,8 @@ def test_callers_list_with_ties(bctx, n, route, state_bytes):
     own = {"depth": depth, "shadow": shadow, "clip": clip, "pos": pos, "tri": clip}
     _same(got, own, ("clip", "pos", "tri", "depth", "shadow"), f"list of {n} route {route}")
     _same(got, {"argb": a, "depth": d, "shadow": s}, ("argb", "depth", "shadow"), f"list of {n} against rast_render")
+    ora = oracle.rast_draw_list(sc.oracle_params(p), tris, n, light, buffers=True)
+    _same(got, ora, ("screen", "low", "high", "argb", "depth", "shadow"), f"list of {n} route {route} against the oracle")
     # every triangle is listed twice in a row (an exact depth tie on every fragment): the later
     # twin, the odd index, always owns
     owned = got["clip"][got["clip"] >= 0]
@@ -212,6 +215,8 @@ def test_mesh_beyond_the_dense_inputs(bctx):
     src = ro.input_of_clip(p, room, B["n"], NO_BOXES, 0)
     ref["tri"] = np.where(ref["clip"] >= 0, src[np.maximum(ref["clip"], 0)], NONE).astype(np.int32)
     _same(got, ref, ALL, "6000-triangle room")
+    ora = oracle.rast_draw(sc.oracle_params(p), scene=(room, B["n"], NO_BOXES, 0), buffers=True)
+    _same(got, ora, ("screen", "low", "high", "argb", "depth", "shadow"), "6000-triangle room against the oracle")
     assert (got["clip"] >= 0).any()
 
 
