@@ -246,6 +246,17 @@ _SIGS = {
     "cg_rast_draw_sequence": (C.c_int, [P, C.POINTER(RastParams), C.c_int, P, P, P, C.c_size_t, C.c_int,
                                         C.POINTER(RastSeqFrame), C.POINTER(Stats)]),
     "cg_rast_set_rand_capacity": (C.c_int, [P, C.c_longlong]),
+    "cg_rast_draw_picture_device": (C.c_int, [P, C.POINTER(RastParams), P, P, P, P]),
+    "cg_rast_draw_picture": (C.c_int, [P, C.POINTER(RastParams), P, C.POINTER(Stats)]),
+    "cg_rast_draw_sequence_picture_device": (C.c_int, [P, C.POINTER(RastParams), C.c_int, P, P, P, C.c_size_t, P,
+                                                       P]),
+    "cg_rast_tonemap_pack_device": (C.c_int, [P, P, C.c_size_t, C.c_int, C.c_size_t, P, C.c_int, C.c_float, P,
+                                              C.c_size_t, P]),
+    "cg_rast_pack_pixel": (C.c_uint32, [P, C.c_float, C.c_int, C.c_float]),
+    "cg_rast_draw_exposed_device": (C.c_int, [P, C.POINTER(RastParams), C.c_int, C.POINTER(HdrExposureParams), P,
+                                              C.c_int, C.c_float, P, C.c_size_t, P, P, P]),
+    "cg_rast_draw_exposed": (C.c_int, [P, C.POINTER(RastParams), C.c_int, C.POINTER(HdrExposureParams), P, C.c_int,
+                                       C.c_float, P, C.c_size_t, P, C.POINTER(RastSeqFrame), C.POINTER(Stats)]),
     "cg_rast_route": (C.c_int, [C.c_longlong]),
     "cg_rast_set_route": (C.c_int, [P, C.c_int]),
     "cg_rast_set_route_limit": (C.c_int, [P, C.c_longlong]),
@@ -383,6 +394,23 @@ def hdr_tone(op, v, white2=1.0):
     out = np.empty(v.shape, np.float32)
     for i, b in enumerate(v.ravel().view(np.uint32).tolist()):
         out.flat[i] = lib.cg_hdr_tone(op, _f32_arg(b), white2)
+    return out
+
+
+def rast_pack_pixel(rgba, scale=1.0, op=TONE_LINEAR, white2=1.0):
+    """cg_rast_pack_pixel over float32[..., 4] pixels: the rasteriser's pack of each (an uncovered
+    pixel, !(w > 0), gives 0; a channel that is not positive is 0 before the scale) as uint32[...]
+    (host-only; no GPU needed).  The scale passes by bit pattern, the pixels by address."""
+    lib = load()
+    px = np.ascontiguousarray(rgba, np.float32)
+    if px.shape[-1:] != (4,):
+        raise ValueError("pixels of four floats")
+    out = np.empty(px.shape[:-1], np.uint32)
+    flat = px.reshape(-1, 4)
+    s = _f32_arg(np.float32(scale).view(np.uint32))
+    base = flat.ctypes.data
+    for i in range(len(flat)):
+        out.flat[i] = lib.cg_rast_pack_pixel(P(base + 16 * i), s, op, white2)
     return out
 
 
@@ -1484,6 +1512,75 @@ class Context:
             self.h, arr, n, ptr(argb), ptr(depth), ptr(shadow), stride, chunk,
             C.cast(info.ctypes.data, C.POINTER(RastSeqFrame)), C.byref(st)), "cg_rast_draw_sequence")
         return argb, depth, shadow, info, st
+
+    def rast_draw_picture(self, params):
+        """cg_rast_draw_picture: rast_draw's frame before PutPixelSDL clamps it, float32[H, W, 4]
+        (PIX_RGBA_F32) -- x, y, z what antiAliasing returns and w = 1 inside, zeros on the border."""
+        out = np.zeros((params.height, params.width, 4), np.float32)
+        st = Stats()
+        self._check(self.lib.cg_rast_draw_picture(self.h, C.byref(params), out.ctypes.data_as(P), C.byref(st)),
+                    "cg_rast_draw_picture")
+        return out, st
+
+    def rast_draw_picture_device(self, params, d_rgba, d_depth=None, d_shadow=None, stream=None):
+        """cg_rast_draw_picture_device: rast_draw_device with W * H float4 pixels at d_rgba."""
+        self._check(self.lib.cg_rast_draw_picture_device(self.h, C.byref(params), P(d_rgba),
+                                                         P(d_depth) if d_depth else None,
+                                                         P(d_shadow) if d_shadow else None,
+                                                         P(stream) if stream else None),
+                    "cg_rast_draw_picture_device")
+
+    def rast_draw_sequence_picture_device(self, params_list, d_rgba, d_depth=None, d_shadow=None, frame_stride=0,
+                                          d_info=None, stream=None):
+        """cg_rast_draw_sequence_picture_device: rast_draw_sequence_device with float frames, frame f
+        at d_rgba + f * frame_stride pixels of 16 bytes."""
+        arr = (RastParams * max(len(params_list), 1))(*params_list)
+        self._check(self.lib.cg_rast_draw_sequence_picture_device(
+            self.h, arr, len(params_list), P(d_rgba), P(d_depth) if d_depth else None,
+            P(d_shadow) if d_shadow else None, frame_stride, P(d_info) if d_info else None,
+            P(stream) if stream else None), "cg_rast_draw_sequence_picture_device")
+
+    def rast_tonemap_pack_device(self, d_rgba, n_pixels, n_frames, d_scales, d_argb, op=TONE_LINEAR, white2=1.0,
+                                 src_stride=0, dst_stride=0, stream=None):
+        """cg_rast_tonemap_pack_device: rt_tonemap_pack_device with the rasteriser's border and clamp rules."""
+        self._check(self.lib.cg_rast_tonemap_pack_device(self.h, P(d_rgba), n_pixels, n_frames, src_stride,
+                                                         P(d_scales), op, white2, P(d_argb), dst_stride,
+                                                         P(stream) if stream else None),
+                    "cg_rast_tonemap_pack_device")
+
+    def rast_draw_exposed_device(self, params_list, d_argb, d_scales, params, d_info, d_prev=None, op=TONE_LINEAR,
+                                 white2=1.0, frame_stride=0, stream=None):
+        """cg_rast_draw_exposed_device: the key script's frames drawn, exposed and packed into d_argb +
+        f * frame_stride pixels, their scales into d_scales, their records into d_info (device
+        memory, len(params_list) + 1 RastSeqFrame records)."""
+        arr = (RastParams * max(len(params_list), 1))(*params_list)
+        self._check(self.lib.cg_rast_draw_exposed_device(self.h, arr, len(params_list), C.byref(params),
+                                                         P(d_prev) if d_prev else None, op, white2, P(d_argb),
+                                                         frame_stride, P(d_scales), P(d_info) if d_info else None,
+                                                         P(stream) if stream else None),
+                    "cg_rast_draw_exposed_device")
+
+    def rast_draw_exposed(self, params_list, permille=990, target=1.0, scale_min=2.0 ** -16, scale_max=2.0 ** 16,
+                          rate=1.0, prev=None, op=TONE_LINEAR, white2=1.0):
+        """cg_rast_draw_exposed: (frames uint32[n, H, W], scales float32[n], info, rc) in host memory;
+        rc is CG_OK, or CG_E_CAPACITY when a frame was flagged (everything is delivered all the same)."""
+        n = len(params_list)
+        if n == 0:
+            return np.zeros((0, 0, 0), np.uint32), np.zeros(0, np.float32), np.zeros(1, RAST_SEQ_DTYPE), CG_OK
+        arr = (RastParams * n)(*params_list)
+        params = hdr_params(permille, target, scale_min, scale_max, rate)
+        out = np.zeros((n, params_list[0].height, params_list[0].width), np.uint32)
+        scales = np.zeros(n, np.float32)
+        info = np.zeros(n + 1, RAST_SEQ_DTYPE)
+        pv = None if prev is None else np.array([prev], np.float32)
+        st = Stats()
+        rc = self.lib.cg_rast_draw_exposed(self.h, arr, n, C.byref(params),
+                                           pv.ctypes.data_as(P) if pv is not None else None, op, white2,
+                                           out.ctypes.data_as(P), 0, scales.ctypes.data_as(P),
+                                           C.cast(info.ctypes.data, C.POINTER(RastSeqFrame)), C.byref(st))
+        if rc != CG_E_CAPACITY:
+            self._check(rc, "cg_rast_draw_exposed")
+        return out, scales, info, rc
 
     def rast_set_route(self, route):
         """Test and A/B hook: -1 automatic, RAST_ROUTE_DENSE / RAST_ROUTE_COMPACT forced."""

@@ -1,10 +1,12 @@
 // cg_api_rast.hip -- the rasteriser's entry points: scene, routes, lanes, sequences, textures,
-// buffers and picking.  Host code only (kernels: cg_rast*.hip, cg_geometry.hip).
+// buffers and picking, the float picture and exposed key scripts.  Host code only (kernels:
+// cg_rast*.hip, cg_geometry.hip, cg_hdr.hip).
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
 
 #include "cg_ctx.h"
+#include "cg_hdr.h"
 
 // bit k set: some triangle of the list carries texture k (1-3)
 static int rast_tex_mask(const cg_rtri *t, int n)
@@ -128,7 +130,7 @@ extern "C" int cg_rast_scratch_info(cg_ctx *c, uint64_t out[5])
     if (L.route >= 0) CG_TRY(c, hipStreamSynchronize(L.st ? L.st : c->stream), "rast frame");
     auto held = [](const cg_ctx *x) {
         size_t b = x->rtris.bytes + x->rhdr.bytes + x->rspan.bytes + x->rpix.bytes + x->rcount.bytes + x->rrecs.bytes +
-                   x->rgeo.bytes;
+                   x->rgeo.bytes + x->rhdr_rgba.bytes;
         for (const DevBuf &d : x->rbig) b += d.bytes;
         b += x->rbuf[kBufOwner - kBufOwner].bytes + x->rbuf[kBufClipPre - kBufOwner].bytes;   // a buffers call's scratch
         return b;
@@ -267,7 +269,7 @@ extern "C" int cg_rast_set_rand_capacity(cg_ctx *c, long long fragments)
 
 static int rast_sequence_device(cg_ctx *c, const cg_rast_params *ps, int n_frames, uint32_t *d_argb, float *d_depth,
                                 int32_t *d_shadow, size_t frame_stride, cg_rast_seq_frame *d_info, void *stream,
-                                bool resume, int lane_cap);
+                                bool resume, int lane_cap, int pix = CG_PIX_ARGB8888);
 
 extern "C" int cg_rast_draw_sequence_device(cg_ctx *c, const cg_rast_params *ps, int n_frames, uint32_t *d_argb,
                                             float *d_depth, int32_t *d_shadow, size_t frame_stride,
@@ -279,10 +281,10 @@ extern "C" int cg_rast_draw_sequence_device(cg_ctx *c, const cg_rast_params *ps,
 // cg_rast_draw_sequence_device, and a chunk of cg_rast_draw_sequence.  resume: the first frame
 // starts at the index an earlier call on the same stream left in d_info[0] (its closing record),
 // as every later frame does; ps[0].rand_offset is then ignored too.  lane_cap > 0: at most so
-// many lanes.
+// many lanes.  pix: d_argb's pixel format (CG_PIX_RGBA_F32: float4 pixels, frame_stride in those).
 static int rast_sequence_device(cg_ctx *c, const cg_rast_params *ps, int n_frames, uint32_t *d_argb, float *d_depth,
                                 int32_t *d_shadow, size_t frame_stride, cg_rast_seq_frame *d_info, void *stream,
-                                bool resume, int lane_cap)
+                                bool resume, int lane_cap, int pix)
 {
     if (!c || n_frames < 0 || (n_frames && (!ps || !d_argb))) return CG_E_INVALID;
     if (c->n_room < 0) {
@@ -352,6 +354,7 @@ static int rast_sequence_device(cg_ctx *c, const cg_rast_params *ps, int n_frame
         CG_TRY(c, hipEventRecord(c->start_ev, st), "event");
         for (int k = 0; k < L; ++k) CG_TRY(c, hipStreamWaitEvent(c->lanes[k]->stream, c->start_ev, 0), "lane wait");
     }
+    const size_t wpp = pix == CG_PIX_RGBA_F32 ? 4 : 1;   // 4-byte words a pixel of d_argb takes
     for (int f = 0; f < n_frames; ++f) {
         const size_t o = (size_t)f * stride;
         cg_ctx *l = L > 1 ? c->lanes[f % L] : c;
@@ -361,9 +364,9 @@ static int rast_sequence_device(cg_ctx *c, const cg_rast_params *ps, int n_frame
         q.wait_ev = L > 1 && f > 0 ? c->seq_ev[(f - 1) % L] : nullptr;
         q.done_ev = L > 1 ? c->seq_ev[f % L] : nullptr;
         const int rc = rast_draw_device(l, (const cg_rtri *)l->rroom.p, l->n_room, (const cg_rtri *)l->rboxes.p,
-                                        l->n_boxes, &ps[f], d_argb + o, d_depth ? d_depth + o : nullptr,
+                                        l->n_boxes, &ps[f], d_argb + o * wpp, d_depth ? d_depth + o : nullptr,
                                         d_shadow ? d_shadow + o : nullptr, L > 1 ? l->stream : st, nullptr, nullptr,
-                                        l->scene_tex, &q);
+                                        l->scene_tex, &q, pix);
         if (rc) {
             if (l != c) c->err = std::string("lane: ") + l->err;
             return rc;
@@ -818,6 +821,208 @@ extern "C" int cg_rast_draw_sequence(cg_ctx *c, const cg_rast_params *ps, int n_
         stats->kernel_ms = kernel_ms;
         stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         stats->n_tris = *h_ntris;
+        stats->n_spans = 0;
+        stats->n_shaded = shaded;
+    }
+    return rc_out;
+}
+
+// ---- the float picture (CG_PIX_RGBA_F32) and exposed frames (kernels: the post-pass's *_f32
+// variants, cg_hdr.hip's rast_tonemap_pack_kernel) ----
+extern "C" int cg_rast_draw_picture_device(cg_ctx *c, const cg_rast_params *p, float *d_rgba, float *d_depth,
+                                           int32_t *d_shadow, void *stream)
+{
+    if (!c || !p || !d_rgba || ((uintptr_t)d_rgba & 15)) return CG_E_INVALID;
+    if (c->n_room < 0) {
+        c->err = "draw before cg_rast_set_scene";
+        return CG_E_NOSCENE;
+    }
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    return rast_draw_device(c, (const cg_rtri *)c->rroom.p, c->n_room, (const cg_rtri *)c->rboxes.p, c->n_boxes, p,
+                            (uint32_t *)d_rgba, d_depth, d_shadow, stream ? (hipStream_t)stream : c->stream, nullptr,
+                            nullptr, c->scene_tex, nullptr, CG_PIX_RGBA_F32);
+}
+
+extern "C" int cg_rast_draw_picture(cg_ctx *c, const cg_rast_params *p, float *rgba, cg_stats *stats)
+{
+    if (!c || !p || !rgba || p->width <= 2 || p->height <= 2) return CG_E_INVALID;
+    if (c->n_room < 0) {
+        c->err = "draw before cg_rast_set_scene";
+        return CG_E_NOSCENE;
+    }
+    auto t0 = std::chrono::steady_clock::now();
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    const size_t bytes = (size_t)p->width * p->height * 16;
+    hipError_t e;
+    float *d_rgba = (float *)ctx_buf(c, kBufRastHdr, bytes, &e);
+    if (!d_rgba) return ctx_fail(c, e, "alloc picture");
+    int *d_n = nullptr;
+    const int rc = rast_draw_device(c, (const cg_rtri *)c->rroom.p, c->n_room, (const cg_rtri *)c->rboxes.p, c->n_boxes,
+                                    p, (uint32_t *)d_rgba, nullptr, nullptr, c->stream, stats, &d_n, c->scene_tex,
+                                    nullptr, CG_PIX_RGBA_F32);
+    if (rc) return rc;
+    int n = 0;
+    CG_TRY(c, hipMemcpyAsync(&n, d_n, sizeof(int), hipMemcpyDeviceToHost, c->stream), "d2h count");
+    CG_TRY(c, hipMemcpyAsync(rgba, d_rgba, bytes, hipMemcpyDeviceToHost, c->stream), "d2h picture");
+    CG_TRY(c, hipStreamSynchronize(c->stream), "rast frame");
+    if (stats) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
+        stats->kernel_ms = ms;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->n_tris = n;
+    }
+    return CG_OK;
+}
+
+extern "C" int cg_rast_draw_sequence_picture_device(cg_ctx *c, const cg_rast_params *ps, int n_frames, float *d_rgba,
+                                                    float *d_depth, int32_t *d_shadow, size_t frame_stride,
+                                                    cg_rast_seq_frame *d_info, void *stream)
+{
+    if ((uintptr_t)d_rgba & 15) return CG_E_INVALID;
+    return rast_sequence_device(c, ps, n_frames, (uint32_t *)d_rgba, d_depth, d_shadow, frame_stride, d_info, stream,
+                                false, 0, CG_PIX_RGBA_F32);
+}
+
+extern "C" int cg_rast_tonemap_pack_device(cg_ctx *c, const float *d_rgba, size_t n_pixels, int n_frames,
+                                           size_t src_stride, const float *d_scales, int op, float white2,
+                                           uint32_t *d_argb, size_t dst_stride, void *stream)
+{
+    if (!c || n_frames < 0 || !hdr_tone_ok(op, white2) || n_pixels >= ((size_t)1 << 32)) return CG_E_INVALID;
+    if (n_frames == 0) return CG_OK;
+    const size_t ss = src_stride ? src_stride : n_pixels, ds = dst_stride ? dst_stride : n_pixels;
+    if (!d_scales || ((uintptr_t)d_scales & 3) || (n_pixels && (!d_rgba || !d_argb)) || ((uintptr_t)d_rgba & 15) ||
+        ((uintptr_t)d_argb & 3) || ss < n_pixels || ds < n_pixels)
+        return CG_E_INVALID;
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    CG_TRY(c, launch_rast_tonemap_pack(d_rgba, n_pixels, n_frames, ss, d_scales, op, white2, d_argb, ds,
+                                       stream ? (hipStream_t)stream : c->stream),
+           "tonemap pack launch");
+    return CG_OK;
+}
+
+constexpr int kRastHdrChunkFrames = 8;   // frames of cg_rast_draw_exposed_device's scratch
+
+// what both forms of cg_rast_draw_exposed check before anything is enqueued (the sequence checks the rest)
+static int rast_exposed_check(cg_ctx *c, const cg_rast_params *ps, int n_frames, const cg_hdr_exposure_params *params,
+                              int op, float white2, size_t frame_stride)
+{
+    if (!c || n_frames < 0 || (n_frames && !ps)) return CG_E_INVALID;
+    if (!hdr_params_ok(params)) return ctx_invalid(c, "draw_exposed: exposure parameters");
+    if (!hdr_tone_ok(op, white2)) return ctx_invalid(c, "draw_exposed: tone curve");
+    if (c->n_room < 0) {
+        c->err = "draw before cg_rast_set_scene";
+        return CG_E_NOSCENE;
+    }
+    if (n_frames == 0) return CG_OK;
+    if (ps[0].width <= 2 || ps[0].height <= 2) return ctx_invalid(c, "draw_exposed: frame size");
+    const size_t px = (size_t)ps[0].width * ps[0].height;
+    for (int f = 0; f < n_frames; ++f)
+        if (ps[f].colour_mode < 0 || ps[f].colour_mode > 2 || ps[f].width != ps[0].width ||
+            ps[f].height != ps[0].height || (frame_stride && frame_stride < px))
+            return ctx_invalid(c, "draw_exposed: colour modes 0-2, frames of one size, frame_stride >= W * H");
+    return CG_OK;
+}
+
+// Frames f0 .. f0 + nf - 1 (nf <= kRastHdrChunkFrames) of an exposed call: the float sequence into
+// the context's scratch (resuming at d_info[0] when f0 > 0), then histogram, exposure (previous
+// scale *d_prev) and pack, all on st.  d_info: the chunk's first record.
+static int rast_exposed_chunk(cg_ctx *c, const cg_rast_params *ps, int f0, int nf,
+                              const cg_hdr_exposure_params &params, const float *d_prev, int op, float white2,
+                              uint32_t *d_argb, size_t stride, float *d_scales, cg_rast_seq_frame *d_info,
+                              hipStream_t st)
+{
+    const size_t px = (size_t)ps[0].width * ps[0].height;
+    hipError_t e;
+    float *rgba = (float *)ctx_buf(c, kBufRastHdr, kRastHdrChunkFrames * px * 16, &e);
+    if (!rgba) return ctx_fail(c, e, "alloc exposure frames");
+    CG_TRY(c, c->hdr_hist.ensure(kRastHdrChunkFrames * CG_HDR_BINS * sizeof(uint32_t)), "alloc exposure histograms");
+    const int rc = rast_sequence_device(c, ps + f0, nf, (uint32_t *)rgba, nullptr, nullptr, px, d_info, st, f0 > 0, 0,
+                                        CG_PIX_RGBA_F32);
+    if (rc) return rc;
+    uint32_t *hist = (uint32_t *)c->hdr_hist.p;
+    CG_TRY(c, launch_hdr_histogram(rgba, 4, px, nf, px, hist, nullptr, st), "histogram launch");
+    CG_TRY(c, launch_hdr_exposure(hist, nf, params, d_prev, d_scales, st), "exposure launch");
+    CG_TRY(c, launch_rast_tonemap_pack(rgba, px, nf, px, d_scales, op, white2, d_argb, stride, st), "tonemap pack launch");
+    return CG_OK;
+}
+
+extern "C" int cg_rast_draw_exposed_device(cg_ctx *c, const cg_rast_params *ps, int n_frames,
+                                           const cg_hdr_exposure_params *params, const float *d_prev, int op,
+                                           float white2, uint32_t *d_argb, size_t frame_stride, float *d_scales,
+                                           cg_rast_seq_frame *d_info, void *stream)
+{
+    if (int rc = rast_exposed_check(c, ps, n_frames, params, op, white2, frame_stride)) return rc;
+    if (n_frames == 0) return CG_OK;
+    if (!d_argb || ((uintptr_t)d_argb & 3) || !d_scales || ((uintptr_t)d_scales & 3) || ((uintptr_t)d_prev & 3))
+        return CG_E_INVALID;
+    if (!d_info) return ctx_invalid(c, "draw_exposed: d_info is required");
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const size_t stride = frame_stride ? frame_stride : (size_t)ps[0].width * ps[0].height;
+    for (int f0 = 0; f0 < n_frames; f0 += kRastHdrChunkFrames) {
+        const int nf = std::min(kRastHdrChunkFrames, n_frames - f0);
+        if (int rc = rast_exposed_chunk(c, ps, f0, nf, *params, f0 ? d_scales + f0 - 1 : d_prev, op, white2,
+                                        d_argb + (size_t)f0 * stride, stride, d_scales + f0, d_info + f0, st))
+            return rc;
+    }
+    return CG_OK;
+}
+
+// Host-memory form: the device form's chunks into context scratch, each chunk's frames downloaded
+// after its render; the scales (and the caller's previous scale) live in one device array,
+// [0] the previous scale, [1 + f] frame f's; the records in the host sequence's device array.
+extern "C" int cg_rast_draw_exposed(cg_ctx *c, const cg_rast_params *ps, int n_frames,
+                                    const cg_hdr_exposure_params *params, const float *prev, int op, float white2,
+                                    uint32_t *argb, size_t frame_stride, float *scales, cg_rast_seq_frame *info,
+                                    cg_stats *stats)
+{
+    if (int rc = rast_exposed_check(c, ps, n_frames, params, op, white2, frame_stride)) return rc;
+    if (n_frames == 0) return CG_OK;
+    if (!argb || !scales) return CG_E_INVALID;
+    auto t0 = std::chrono::steady_clock::now();
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    const size_t px = (size_t)ps[0].width * ps[0].height;
+    const size_t stride = frame_stride ? frame_stride : px;
+    CG_TRY(c, c->hdr_argb.ensure(kRastHdrChunkFrames * px * sizeof(uint32_t)), "alloc exposed frames");
+    CG_TRY(c, c->hdr_scales.ensure(((size_t)n_frames + 1) * sizeof(float)), "alloc scales");
+    const size_t rec_bytes = ((size_t)n_frames + 1) * sizeof(cg_rast_seq_frame);
+    CG_TRY(c, c->rs_info.ensure(rec_bytes), "alloc records");
+    float *d_s = (float *)c->hdr_scales.p;
+    uint32_t *d_a = (uint32_t *)c->hdr_argb.p;
+    cg_rast_seq_frame *d_info = (cg_rast_seq_frame *)c->rs_info.p;
+    if (prev) CG_TRY(c, hipMemcpyAsync(d_s, prev, sizeof(float), hipMemcpyHostToDevice, c->stream), "upload scale");
+    float ms_sum = 0.f;
+    for (int f0 = 0; f0 < n_frames; f0 += kRastHdrChunkFrames) {
+        const int nf = std::min(kRastHdrChunkFrames, n_frames - f0);
+        CG_TRY(c, hipEventRecord(c->ev0, c->stream), "event");
+        if (int rc = rast_exposed_chunk(c, ps, f0, nf, *params, f0 || prev ? d_s + f0 : nullptr, op, white2, d_a, px,
+                                        d_s + 1 + f0, d_info + f0, c->stream))
+            return rc;
+        CG_TRY(c, hipEventRecord(c->ev1, c->stream), "event");
+        for (int f = 0; f < nf; ++f)
+            CG_TRY(c, hipMemcpyAsync(argb + (size_t)(f0 + f) * stride, d_a + (size_t)f * px, px * sizeof(uint32_t),
+                                     hipMemcpyDeviceToHost, c->stream),
+                   "download frames");
+        CG_TRY(c, hipStreamSynchronize(c->stream), "exposed frames");
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
+        ms_sum += ms;
+    }
+    CG_TRY(c, hipMemcpy(scales, d_s + 1, (size_t)n_frames * sizeof(float), hipMemcpyDeviceToHost), "download scales");
+    std::vector<cg_rast_seq_frame> rec((size_t)n_frames + 1);
+    CG_TRY(c, hipMemcpy(rec.data(), d_info, rec_bytes, hipMemcpyDeviceToHost), "download records");
+    if (info) std::memcpy(info, rec.data(), rec_bytes);
+    int rc_out = CG_OK;
+    long long shaded = -1;
+    for (int f = 0; f < n_frames; ++f) {
+        if (ps[f].colour_mode != 0) shaded = std::max(shaded, 0ll) + rec[f].n_shaded;
+        if (rec[f].status != 0 && rc_out == CG_OK) rc_out = rec[f].status;
+    }
+    if (stats) {
+        stats->kernel_ms = ms_sum;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->n_tris = (int)std::max(c->rlast.n, 0ll);
         stats->n_spans = 0;
         stats->n_shaded = shaded;
     }

@@ -247,6 +247,9 @@ struct cg_ctx {
     // cg_rast_draw_sequence_device: the generator's tables (windows, seed words, J_b for
     // rseq_chunks chunks) and the stream's capacity in fragments (0: 4 * W * H)
     DevBuf rseq;
+    // cg_rast_draw_exposed*: a chunk of 8 CG_PIX_RGBA_F32 frames (kBufRastHdr); the histograms, the
+    // host form's ARGB chunk and scales are the raytracer chain's (hdr_hist, hdr_argb, hdr_scales)
+    DevBuf rhdr_rgba;
     long long rseq_chunks = 0, rand_cap = 0;
     // cg_rast_draw_sequence (host output): two sets of plane slots of `chunk` frames (downloaded on
     // `xfer` as hslot is, with events of their own), the call's n_frames + 1 device records, and their

@@ -96,6 +96,17 @@ CG_HD unsigned hdr_pack(float x, float y, float z, float s, int op, float white2
     return put_pixel(v3(hdr_tone(op, x * s, white2), hdr_tone(op, y * s, white2), hdr_tone(op, z * s, white2)));
 }
 
+// The rasteriser's pack (cg_rast_tonemap_pack_device, cg_rast_pack_pixel).  Border rule: a pixel
+// with !(w > 0) is one the reference never gave PutPixelSDL, so its word is 0.  Clamp rule: each
+// channel is c > 0 ? c : 0 before the scale (a NaN gives 0), since the reference shows a negative
+// channel as black and Reinhard's v / (1 + v) has a pole at -1.
+CG_HD float hdr_clamp0(float c) { return c > 0.0f ? c : 0.0f; }
+CG_HD unsigned hdr_rast_pack(float x, float y, float z, float w, float s, int op, float white2)
+{
+    const unsigned px = hdr_pack(hdr_clamp0(x), hdr_clamp0(y), hdr_clamp0(z), s, op, white2);
+    return w > 0.0f ? px : 0u;   // a select after the pack: no lane leaves the kernel's straight line
+}
+
 inline bool hdr_params_ok(const cg_hdr_exposure_params *p)
 {
     return p && p->permille >= 0 && p->permille <= 1000 && p->rate >= 0.0f && p->rate <= 1.0f &&

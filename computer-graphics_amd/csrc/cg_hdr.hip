@@ -203,6 +203,22 @@ __global__ __launch_bounds__(256) void rt_tonemap_pack_kernel(const float4 *__re
     }
 }
 
+// rt_tonemap_pack_kernel with the rasteriser's border and clamp rules (cg_rast_tonemap_pack_device,
+// hdr_rast_pack): an uncovered pixel packs to 0, a channel that is not positive to 0 before the scale.
+__global__ __launch_bounds__(256) void rast_tonemap_pack_kernel(const float4 *__restrict__ src, size_t n, int n_frames,
+                                                                size_t sstride, const float *__restrict__ scales,
+                                                                int op, float white2, uint32_t *__restrict__ dst,
+                                                                size_t dstride)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    for (int f = blockIdx.y; f < n_frames; f += gridDim.y) {
+        const float s = scales[f];
+        const float4 v = src[(size_t)f * sstride + i];
+        dst[(size_t)f * dstride + i] = hdr_rast_pack(v.x, v.y, v.z, v.w, s, op, white2);
+    }
+}
+
 // CG_HDR_PEEL: merge rounds before the LDS add (0 .. 8; default 1), for scripts/hdr_rate.py
 static int hdr_peel()
 {
@@ -262,6 +278,16 @@ hipError_t launch_rt_tonemap_pack(const float *d_rgba, size_t n, int n_frames, s
     return hipGetLastError();
 }
 
+hipError_t launch_rast_tonemap_pack(const float *d_rgba, size_t n, int n_frames, size_t sstride, const float *d_scales,
+                                    int op, float white2, uint32_t *d_argb, size_t dstride, hipStream_t st)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(rast_tonemap_pack_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)(n_frames < 65535 ? n_frames : 65535)),
+                       dim3(256), 0, st, (const float4 *)d_rgba, n, n_frames, sstride, d_scales, op, white2, d_argb,
+                       dstride);
+    return hipGetLastError();
+}
+
 }  // namespace cg
 
 using namespace cg;
@@ -271,6 +297,10 @@ extern "C" float cg_hdr_luminance(float x, float y, float z) { return hdr_lumina
 extern "C" int cg_hdr_bin(float L) { return hdr_bin(L); }
 extern "C" float cg_hdr_bin_edge(int bin) { return bin < 0 || bin >= kHdrBins ? 0.0f : hdr_bin_edge(bin); }
 extern "C" float cg_hdr_tone(int op, float v, float white2) { return hdr_tone(op, v, white2); }
+extern "C" uint32_t cg_rast_pack_pixel(const float rgba[4], float scale, int op, float white2)
+{
+    return rgba ? hdr_rast_pack(rgba[0], rgba[1], rgba[2], rgba[3], scale, op, white2) : 0u;
+}
 
 extern "C" int cg_hdr_exposure(const uint32_t *hist, int n_frames, const cg_hdr_exposure_params *params,
                                const float *prev, float *scales)

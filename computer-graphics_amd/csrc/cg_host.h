@@ -29,7 +29,9 @@ enum {
     kBufTris = 0, kBufHdr, kBufSpan, kBufPix, kBufArgb, kBufDepth, kBufShadow, kBufCount, kBufRecs, kBufGeo,
     kBufPc, kBufTl, kBufRnd, kBufJt,     // colour modes 1-2 (cg_rast_colour.hip)
     kBufStars, kBufStarFrame,            // cg_starfield.hip
-    kBufTexel, kBufImage, kBufSeq, kBufFieldsEnd,
+    kBufTexel, kBufImage, kBufSeq,
+    kBufRastHdr,                         // cg_rast_draw_exposed*: a chunk's CG_PIX_RGBA_F32 frames
+    kBufFieldsEnd,
     kBufBig0 = 20, kBufBigEnd = kBufBig0 + 15,
     kBufOwner = 40, kBufClipPre, kBufScreen, kBufLow, kBufHigh, kBufClipId, kBufTriId, kBufPos, kBufPick, kBufOwnerEnd
 };
@@ -117,6 +119,8 @@ hipError_t launch_hdr_exposure(const uint32_t *, int, const cg_hdr_exposure_para
                                hipStream_t);
 hipError_t launch_rt_tonemap_pack(const float *, size_t, int, size_t, const float *, int, float, uint32_t *, size_t,
                                   hipStream_t);
+hipError_t launch_rast_tonemap_pack(const float *, size_t, int, size_t, const float *, int, float, uint32_t *, size_t,
+                                    hipStream_t);
 // cg_api_rt.hip: cg_rt_render_frames_device, plus per-frame completion signals for cg_dist
 int rt_render_frames(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams, int n_frames,
                      const cg_rt_shard *shard, void *d_out, size_t frame_stride, int pix_format, void *stream,
@@ -128,7 +132,7 @@ hipError_t launch_rast_clip(const cg_rast_params &prm, const cg_rtri *d_room, in
                             int n_boxes, cg_rtri *d_stage, int *d_counts, cg_vec4 *d_light, int *d_first,
                             hipStream_t st);
 void launch_rast_post_direct(const RastArgs &A, const float4 *state, const int32_t *shadow, uint32_t *d_argb,
-                             hipStream_t st);
+                             hipStream_t st, int pix = CG_PIX_ARGB8888);
 int rast_make_args(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *p, cg_vec4 light,
                    const cg_vec4 *d_light, int tex_mask, RastArgs *out);
 int rast_render_device(cg_ctx *ctx, const cg_rtri *d_tris, int n, const cg_rast_params *p,
@@ -136,14 +140,15 @@ int rast_render_device(cg_ctx *ctx, const cg_rtri *d_tris, int n, const cg_rast_
                        hipStream_t st, cg_stats *stats, int tex_mask);
 int rast_draw_device(cg_ctx *c, const cg_rtri *d_room, int n_room, const cg_rtri *d_boxes, int n_boxes,
                      const cg_rast_params *p, uint32_t *d_argb, float *d_depth, int32_t *d_shadow,
-                     hipStream_t st, cg_stats *stats, int **n_out, int tex_mask, const RastSeq *seq = nullptr);
+                     hipStream_t st, cg_stats *stats, int **n_out, int tex_mask, const RastSeq *seq = nullptr,
+                     int pix = CG_PIX_ARGB8888);
 // cg_rast_big.hip
 void rast_big_blocks(int *batch, int *chunk);
 int rast_big_render(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *p, cg_vec4 light, uint32_t *d_argb,
                     float *d_depth, int32_t *d_shadow, hipStream_t st, cg_stats *stats, int tex_mask);
 int rast_big_draw(cg_ctx *c, const cg_rtri *d_room, int n_room, const cg_rtri *d_boxes, int n_boxes,
                   const cg_rast_params *p, uint32_t *d_argb, float *d_depth, int32_t *d_shadow, hipStream_t st,
-                  cg_stats *stats, int **n_out, int tex_mask, const RastSeq *seq);
+                  cg_stats *stats, int **n_out, int tex_mask, const RastSeq *seq, int pix = CG_PIX_ARGB8888);
 // cg_rast_colour.hip
 int rast_rand_stream(cg_ctx *c, int rnd_buf, int jt_buf, uint64_t offset, long long S, hipStream_t st, int32_t **out);
 int rast_colour_fill(cg_ctx *c, const RastArgs &A, const cg_rast_params *p, const RowRec *recs, const int *count,

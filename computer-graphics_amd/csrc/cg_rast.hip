@@ -23,6 +23,8 @@
 //        neighbours are seen darkened and down/right ones not, which is
 //        recomputed per pixel from the shadow buffer, then antiAliasing
 //        (:1736-1753) and PutPixelSDL.  Border pixels stay 0x00000000.
+//        rast_post_f32_kernel (CG_PIX_RGBA_F32, cg_rast_draw_picture*): the same
+//        text storing the float value PutPixelSDL would have been given.
 #include <float.h>
 #include <limits.h>
 
@@ -427,192 +429,35 @@ __global__ __launch_bounds__(256) void rast_fill_kernel(RastArgs A, const RowRec
 // state is the colour fill's float4 (cg_rast_colour.hip) instead of the fill's
 // record word, and the shadow marks come from the shadow plane; skip (may be
 // null): a sequence frame's status word, non-zero = the frame is not drawn.
-template <bool DIRECT, bool TEX>
-__global__ __launch_bounds__(256) void rast_post_kernel(const cg_rtri *__restrict__ tris, RastArgs A0,
-                                                       const void *__restrict__ state_v,
-                                                       const RowRec *__restrict__ recs,
-                                                       const int32_t *__restrict__ sh,
-                                                       uint32_t *__restrict__ argb,
-                                                       const int32_t *__restrict__ skip)
-{
-    if (DIRECT && skip && *skip != 0) return;             // sequence frame over the capacity: plane untouched
-    RastArgs A = A0;
-    if (!DIRECT && A.d_light) {                           // light from the device geometry (:223)
-        const cg_vec4 L = *A.d_light;
-        A.light[0] = L.x; A.light[1] = L.y; A.light[2] = L.z;
-    }
-    __shared__ float s_c[9][kPostHH][kPostHW];      // sc.xyz, lo.xyz, hi.xyz
-    __shared__ float s_d[kPostHH][kPostHW];
-    // The halo-2 words (colour modes 1-2: the shadow marks; mode 0: the state
-    // words) live in s_c's space: every thread takes what it needs from them
-    // (its pixels' records and darkenings) into registers before the barrier
-    // after which s_c is written.  26.4 KB instead of 29.7: six workgroups
-    // per CU instead of five.
-    static_assert(sizeof(uint32_t) * kPostSH * kPostSW <= sizeof(float) * 9 * kPostHH * kPostHW, "halo words fit");
-    int (*s_sh)[kPostSW] = reinterpret_cast<int (*)[kPostSW]>(&s_c[0][0][0]);
-    const int W = A.W, H = A.H;
-    static_assert(kPostTH == kXcdRows, "a post tile row is one XCD row group");
-    int m;
-    const int g = xcd_group(H, (W + kPostTW - 1) / kPostTW, m);
-    if (g < 0) return;
-    const int gx0 = m * kPostTW, gy0 = g * kPostTH;
-    const uint32_t *st4 = static_cast<const uint32_t *>(state_v);
-    const uint16_t *st2 = static_cast<const uint16_t *>(state_v);
-    auto state_at = [&](size_t o) -> uint32_t {   // the 4-byte form
-        if (!A.state16) return st4[o];
-        const uint32_t v = st2[o];
-        return (v & 0x7fffu) | ((v >> 15) << 31);
-    };
-    const float4 *st16 = static_cast<const float4 *>(state_v);
-    // all global loads first (shadow marks, shade state), so each thread has them in flight together
-    constexpr int kShR = (kPostSH * kPostSW + 255) / 256, kStR = (kPostHH * kPostHW + 255) / 256;
-    // mode 0: the state words (record + 1, mark in bit 31) of the tile + halo 2
-    uint32_t (*s_st)[kPostSW] = reinterpret_cast<uint32_t (*)[kPostSW]>(&s_c[0][0][0]);
-    uint32_t shv[kShR];
-#pragma unroll
-    for (int r = 0; r < kShR; ++r) {
-        const int i = threadIdx.x + 256 * r;
-        const int cy = i / kPostSW, cx = i - cy * kPostSW;
-        const int gx = gx0 - 2 + cx, gy = gy0 - 2 + cy;
-        const bool in = i < kPostSH * kPostSW && gx >= 0 && gy >= 0 && gx < W && gy < H;
-        if (DIRECT) shv[r] = in ? (uint32_t)sh[(size_t)gy * W + gx] : 0u;
-        else shv[r] = in ? state_at((size_t)gy * W + gx) : 0u;
-    }
-#pragma unroll
-    for (int r = 0; r < kShR; ++r) {
-        const int i = threadIdx.x + 256 * r;
-        if (i < kPostSH * kPostSW) {
-            if (DIRECT) (&s_sh[0][0])[i] = (int)shv[r];
-            else (&s_st[0][0])[i] = shv[r];
-        }
-    }
-    __syncthreads();
-    float dv[kStR];   // each pixel's darkening, from the marks before s_c is written
-#pragma unroll
-    for (int r = 0; r < kStR; ++r) {
-        const int i = threadIdx.x + 256 * r;
-        const int cy = i / kPostHW, cx = i - cy * kPostHW;
-        const int gx = gx0 - 1 + cx, gy = gy0 - 1 + cy;
-        dv[r] = 0.0f;
-        if (i < kPostHH * kPostHW && gx >= 1 && gy >= 1 && gx < W - 1 && gy < H - 1)
-            dv[r] = DIRECT ? darken_at(&s_sh[0][0], kPostSW, cy + 1, cx + 1)
-                           : darken_at(&s_st[0][0], kPostSW, cy + 1, cx + 1);
-    }
-    if constexpr (DIRECT) {
-        __syncthreads();   // the marks are dead: s_c's space is free
-#pragma unroll
-        for (int r = 0; r < kStR; ++r) {
-            const int i = threadIdx.x + 256 * r;
-            if (i >= kPostHH * kPostHW) break;
-            const int cy = i / kPostHW, cx = i - cy * kPostHW;
-            const int gx = gx0 - 1 + cx, gy = gy0 - 1 + cy;
-            vec3 sc = v3(0.f, 0.f, 0.f), lo = sc, hi = sc;
-            const float d = dv[r];
-            if (gx >= 0 && gy >= 0 && gx < W && gy < H) {
-                const float4 s4 = st16[(size_t)gy * W + gx];
-                const int tb = __float_as_int(s4.x);
-                const bool tri = tb >= 0 && !(tb & kStateDirect);
-                shade3c(A, s4, tri ? tris[tb & ~(1 << 30)].color : cg_vec3{0.f, 0.f, 0.f}, sc, lo, hi);
-            }
-            s_c[0][cy][cx] = sc.x; s_c[1][cy][cx] = sc.y; s_c[2][cy][cx] = sc.z;
-            s_c[3][cy][cx] = lo.x; s_c[4][cy][cx] = lo.y; s_c[5][cy][cx] = lo.z;
-            s_c[6][cy][cx] = hi.x; s_c[7][cy][cx] = hi.y; s_c[8][cy][cx] = hi.z;
-            s_d[cy][cx] = d;
-        }
-    } else {
-        // The shading fragments of the tile + halo 1: each thread's record
-        // loads go out together, then their triangles', then the arithmetic --
-        // two dependent round trips instead of two per pixel.
-        RowRec rv[kStR];
-        int recv[kStR];
-#pragma unroll
-        for (int r = 0; r < kStR; ++r) {
-            const int i = threadIdx.x + 256 * r;
-            const int cy = i / kPostHW, cx = i - cy * kPostHW;
-            const int gx = gx0 - 1 + cx, gy = gy0 - 1 + cy;
-            const bool in = i < kPostHH * kPostHW && gx >= 0 && gy >= 0 && gx < W && gy < H;
-            recv[r] = in ? (int)(s_st[cy + 1][cx + 1] & ~kStShadow) - 1 : -1;
-            if (recv[r] >= 0) rv[r] = recs[(size_t)gy * A.n + recv[r]];
-        }
-        __syncthreads();   // the state words are dead: s_c's space is free
-        cg_vec4 tnv[kStR];
-        cg_vec3 colv[kStR];
-#pragma unroll
-        for (int r = 0; r < kStR; ++r)
-            if (recv[r] >= 0) {
-                const int t = rec_t(rv[r]);
-                tnv[r] = tris[t].normal;
-                colv[r] = tris[t].color;
-            }
-#pragma unroll
-        for (int r = 0; r < kStR; ++r) {
-            const int i = threadIdx.x + 256 * r;
-            if (i >= kPostHH * kPostHW) break;
-            const int cy = i / kPostHW, cx = i - cy * kPostHW;
-            const int gx = gx0 - 1 + cx, gy = gy0 - 1 + cy;
-            vec3 sc = v3(0.f, 0.f, 0.f), lo = sc, hi = sc;
-            const float d = dv[r];
-            if (recv[r] >= 0) {   // a shading fragment (:580-585, rebuilt as shade_from_record does)
-                const RowRec &R = rv[r];
-                const float fi = (float)(gx - R.lx);
-                const float z = R.lz + (R.sz * fi);                               // :543, as the fill evaluated it
-                const float X = R.lX + (R.sX * fi), Y = R.lY + (R.sY * fi);       // :547-548 numerators
-                const int t = rec_t(R);
-                vec3 N = v3(tnv[r].x, tnv[r].y, tnv[r].z);
-                int tex = 0;
-                uint32_t texel = 0u;
-                if (TEX && R.tex != 0 && rast_tex_present(A, R.tex)) {
-                    tex = R.tex;
-                    N = rast_tex_normal(A, tex, R.index, z, X, Y, gx, gy, N, texel);
-                }
-                const vec3 D = illum_D(A, z, X, Y, N);                            // :580-585 (:590-645)
-                const float4 s4 = make_float4(__int_as_float(t | (gx == R.first_x ? (1 << 30) : 0)), D.x, D.y, D.z);
-                shade3c(A, s4, colv[r], sc, lo, hi, tex, texel);
-            }
-            s_c[0][cy][cx] = sc.x; s_c[1][cy][cx] = sc.y; s_c[2][cy][cx] = sc.z;
-            s_c[3][cy][cx] = lo.x; s_c[4][cy][cx] = lo.y; s_c[5][cy][cx] = lo.z;
-            s_c[6][cy][cx] = hi.x; s_c[7][cy][cx] = hi.y; s_c[8][cy][cx] = hi.z;
-            s_d[cy][cx] = d;
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < kPostTH * kPostTW; i += 256) {
-        const int ty = i / kPostTW, tx = i - ty * kPostTW;
-        const int x = gx0 + tx, y = gy0 + ty;
-        if (x >= W || y >= H) continue;
-        const size_t o = (size_t)y * W + x;
-        if (x < 1 || y < 1 || x >= W - 1 || y >= H - 1) {   // :283-284 border never written
-            argb[o] = 0u;
-            continue;
-        }
-        const int cy = ty + 1, cx = tx + 1;
-        auto tap = [&](int b, int yy, int xx) { return v3(s_c[b][yy][xx], s_c[b + 1][yy][xx], s_c[b + 2][yy][xx]); };
-        auto dk = [&](int yy, int xx) { const float d = s_d[yy][xx]; return v3(d, d, d); };
-        const int ty5[5] = {cy, cy - 1, cy + 1, cy, cy}, tx5[5] = {cx, cx, cx, cx - 1, cx + 1};  // c, up, down, left, right
-        vec3 sv[5], lv[5], hv[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            sv[k] = tap(0, ty5[k], tx5[k]);
-            lv[k] = tap(3, ty5[k], tx5[k]);
-            hv[k] = tap(6, ty5[k], tx5[k]);
-        }
-        sv[0] = sv[0] - dk(cy, cx);                        // darkened: itself, up, left
-        sv[1] = sv[1] - dk(cy - 1, cx);
-        sv[3] = sv[3] - dk(cy, cx - 1);
-        // :1741-1750 (x / 5.0f and / 3.0f via div_const, bit-identical)
-        vec3 val = div_const((((sv[0] + sv[1]) + sv[2]) + sv[3]) + sv[4], 5.0f, 1.0f / 5.0f);
-        vec3 val1 = div_const((((lv[0] + lv[1]) + lv[2]) + lv[3]) + lv[4], 5.0f, 1.0f / 5.0f);
-        vec3 val2 = div_const((((hv[0] + hv[1]) + hv[2]) + hv[3]) + hv[4], 5.0f, 1.0f / 5.0f);
-        val = div_const((val + val1) + val2, 3.0f, 1.0f / 3.0f);
-        argb[o] = put_pixel(val);
-    }
-}
+// The text is cg_rast_post_kernel.inc, once per output policy: rast_post_kernel stores PutPixelSDL's
+// word, rast_post_f32_kernel (CG_PIX_RGBA_F32) the float4 it would have been given.
+#define CG_RAST_POST_NAME rast_post_kernel
+#define CG_RAST_POST_F32 0
+#define CG_RAST_POST_OUT uint32_t
+#include "cg_rast_post_kernel.inc"
+#undef CG_RAST_POST_NAME
+#undef CG_RAST_POST_F32
+#undef CG_RAST_POST_OUT
+#define CG_RAST_POST_NAME rast_post_f32_kernel
+#define CG_RAST_POST_F32 1
+#define CG_RAST_POST_OUT float4
+#include "cg_rast_post_kernel.inc"
+#undef CG_RAST_POST_NAME
+#undef CG_RAST_POST_F32
+#undef CG_RAST_POST_OUT
 
 // The colour modes' post-pass over a float4 state and a shadow plane, for the compact route's
-// modes 1-2 (cg_rast_big.hip): the launch below, without a status word.
+// modes 1-2 (cg_rast_big.hip): the launch below, without a status word.  pix: d_argb's pixel format
+// (CG_PIX_RGBA_F32: it holds float4 pixels and the float-storing kernel runs).
 void launch_rast_post_direct(const RastArgs &A, const float4 *state, const int32_t *shadow, uint32_t *d_argb,
-                             hipStream_t st)
+                             hipStream_t st, int pix)
 {
+    if (pix == CG_PIX_RGBA_F32) {
+        hipLaunchKernelGGL((rast_post_f32_kernel<true, false>), dim3(xcd_grid(A.H, (A.W + kPostTW - 1) / kPostTW)),
+                           dim3(256), 0, st, A.tris, A, (const void *)state, (const RowRec *)nullptr, shadow,
+                           (float4 *)d_argb, (const int32_t *)nullptr);
+        return;
+    }
     hipLaunchKernelGGL((rast_post_kernel<true, false>), dim3(xcd_grid(A.H, (A.W + kPostTW - 1) / kPostTW)), dim3(256), 0,
                        st, A.tris, A, (const void *)state, (const RowRec *)nullptr, shadow, d_argb,
                        (const int32_t *)nullptr);
@@ -630,7 +475,7 @@ struct RastStage {
 static int rast_pipeline(cg_ctx *c, cg_rtri *d_tris, int n, int *n_dev, const cg_rast_params *p,
                          cg_vec4 light, const cg_vec4 *d_light, uint32_t *d_argb, float *d_depth,
                          int32_t *d_shadow, hipStream_t st, cg_stats *stats, bool events_open, int tex_mask,
-                         RastStage sg, const RastSeq *seq = nullptr);
+                         RastStage sg, const RastSeq *seq = nullptr, int pix = CG_PIX_ARGB8888);
 
 // glm::inverse for mat4 (glm/detail/type_mat4x4.inl:37-90), column-major
 // m[4c + r] = m[c][r]: findU / findV's inverse(R) (skeleton.cpp:1762).
@@ -713,18 +558,21 @@ int rast_render_device(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_pa
 
 // Whole rasteriser Draw on the device: geometry (shadow volumes + clip) then
 // fill + post.  room/boxes are device pointers (cg_rast_set_scene).  seq: the
-// frame belongs to a sequence (cg_rast_draw_sequence_device).
+// frame belongs to a sequence (cg_rast_draw_sequence_device).  pix: the pixel
+// format of d_argb -- CG_PIX_RGBA_F32: W * H float4, stored by the post-pass's
+// float kernels; every other launch of the frame is the same.
 int rast_draw_device(cg_ctx *c, const cg_rtri *d_room, int n_room, const cg_rtri *d_boxes, int n_boxes,
                      const cg_rast_params *p, uint32_t *d_argb, float *d_depth, int32_t *d_shadow,
-                     hipStream_t st, cg_stats *stats, int **n_out, int tex_mask, const RastSeq *seq)
+                     hipStream_t st, cg_stats *stats, int **n_out, int tex_mask, const RastSeq *seq, int pix)
 {
     if (p->width <= 2 || p->height <= 2 || p->height > kRastMaxRows || p->focal == 0.0f) return CG_E_INVALID;
+    if (pix != CG_PIX_ARGB8888 && pix != CG_PIX_RGBA_F32) return CG_E_INVALID;
     const long long n_in_ll = (long long)n_room + 7ll * n_boxes;
     // a sequence's frames all take the route the call chose (its lanes and tables follow it)
     const int route = seq ? seq->route : ctx_rast_route(c, kGeomMaxLeaves * n_in_ll, p->colour_mode != 0);
     if (route == CG_RAST_ROUTE_COMPACT)
         return rast_big_draw(c, d_room, n_room, d_boxes, n_boxes, p, d_argb, d_depth, d_shadow, st, stats, n_out,
-                             tex_mask, seq);
+                             tex_mask, seq, pix);
     if (n_in_ll > kRastDenseInputs)
         return ctx_invalid(c, "dense route: more than 4096 input triangles (the setup's LDS prefix); "
                               "use the compact route (cg_rast_set_route)");
@@ -747,13 +595,13 @@ int rast_draw_device(cg_ctx *c, const cg_rtri *d_room, int n_room, const cg_rtri
         return ctx_fail(c, e, "rast_clip launch");
     if (n_out) *n_out = geo;
     return rast_pipeline(c, tris, cap, geo, p, cg_vec4{0, 0, 0, 1}, (const cg_vec4 *)(geo + 4), d_argb, d_depth,
-                         d_shadow, st, stats, true, tex_mask, RastStage{tris + cap, geo + 16, n_in}, seq);
+                         d_shadow, st, stats, true, tex_mask, RastStage{tris + cap, geo + 16, n_in}, seq, pix);
 }
 
 static int rast_pipeline(cg_ctx *c, cg_rtri *d_tris, int n, int *n_dev, const cg_rast_params *p,
                          cg_vec4 light, const cg_vec4 *d_light, uint32_t *d_argb, float *d_depth,
                          int32_t *d_shadow, hipStream_t st, cg_stats *stats, bool events_open, int tex_mask,
-                         RastStage sg, const RastSeq *seq)
+                         RastStage sg, const RastSeq *seq, int pix)
 {
     if (p->width <= 2 || p->height <= 2 || p->height > kRastMaxRows) return CG_E_INVALID;
     const int W = p->width, H = p->height;
@@ -809,7 +657,13 @@ static int rast_pipeline(cg_ctx *c, cg_rtri *d_tris, int n, int *n_dev, const cg
                                               st, &ns);
         if (rc) return rc;
         if (stats) stats->n_shaded = ns;
-        if (d_argb)   // null: a buffers call that asks for no picture
+        if (!d_argb) {
+            // null: a buffers call that asks for no picture
+        } else if (pix == CG_PIX_RGBA_F32)
+            hipLaunchKernelGGL((rast_post_f32_kernel<true, false>), dim3(post_grid), dim3(256), 0, st, d_tris, A,
+                               (const void *)state, (const RowRec *)recs, shadow, (float4 *)d_argb,
+                               seq ? (const int32_t *)&seq->info->status : (const int32_t *)nullptr);
+        else
             hipLaunchKernelGGL((rast_post_kernel<true, false>), dim3(post_grid), dim3(256), 0, st, d_tris, A,
                                (const void *)state, (const RowRec *)recs, shadow, d_argb,
                                seq ? (const int32_t *)&seq->info->status : (const int32_t *)nullptr);
@@ -837,6 +691,15 @@ static int rast_pipeline(cg_ctx *c, cg_rtri *d_tris, int n, int *n_dev, const cg
         const int kt_id = KT_RAST_POST;
         if (!d_argb) {
             // a buffers call that asks for no picture
+        } else if (pix == CG_PIX_RGBA_F32) {
+            if (A.textured)
+                kt_launch(kt_id, (rast_post_f32_kernel<false, true>), dim3(post_grid), dim3(256), 0, st, d_tris, A,
+                          (const void *)state, (const RowRec *)recs, (const int32_t *)nullptr, (float4 *)d_argb,
+                          (const int32_t *)nullptr);
+            else
+                kt_launch(kt_id, (rast_post_f32_kernel<false, false>), dim3(post_grid), dim3(256), 0, st, d_tris, A,
+                          (const void *)state, (const RowRec *)recs, (const int32_t *)nullptr, (float4 *)d_argb,
+                          (const int32_t *)nullptr);
         } else if (A.textured)
             kt_launch(kt_id, (rast_post_kernel<false, true>), dim3(post_grid), dim3(256), 0, st, d_tris, A,
                                (const void *)state, (const RowRec *)recs, (const int32_t *)nullptr, d_argb,

@@ -538,150 +538,23 @@ __global__ __launch_bounds__(256) void rast_big_fill_kernel(RastArgs A, const Ro
     }
 }
 
-template <bool TEX>
-__global__ __launch_bounds__(256) void rast_big_post_kernel(const cg_rtri *__restrict__ tris, RastArgs A0,
-                                                           const void *__restrict__ state_v,
-                                                           const RowRec *__restrict__ recs,
-                                                           const u64 *__restrict__ row_off, u64 rec_cap,
-                                                           uint32_t *__restrict__ argb)
-{
-    RastArgs A = A0;
-    if (A.d_light) {                                      // light from the device geometry (:223)
-        const cg_vec4 L = *A.d_light;
-        A.light[0] = L.x; A.light[1] = L.y; A.light[2] = L.z;
-    }
-    __shared__ float s_c[9][kPostHH][kPostHW];      // sc.xyz, lo.xyz, hi.xyz
-    __shared__ float s_d[kPostHH][kPostHW];
-    // the halo-2 state words live in s_c's space until the shade buffers are written (see rast_post_kernel)
-    static_assert(sizeof(uint32_t) * kPostSH * kPostSW <= sizeof(float) * 9 * kPostHH * kPostHW, "halo words fit");
-    const int W = A.W, H = A.H;
-    static_assert(kPostTH == kXcdRows, "a post tile row is one XCD row group");
-    int m;
-    const int g = xcd_group(H, (W + kPostTW - 1) / kPostTW, m);
-    if (g < 0) return;
-    const int gx0 = m * kPostTW, gy0 = g * kPostTH;
-    const uint32_t *st4 = static_cast<const uint32_t *>(state_v);
-    const uint16_t *st2 = static_cast<const uint16_t *>(state_v);
-    auto state_at = [&](size_t o) -> uint32_t {   // the 4-byte form
-        if (!A.state16) return st4[o];
-        const uint32_t v = st2[o];
-        return (v & 0x7fffu) | ((v >> 15) << 31);
-    };
-    constexpr int kShR = (kPostSH * kPostSW + 255) / 256, kStR = (kPostHH * kPostHW + 255) / 256;
-    uint32_t (*s_st)[kPostSW] = reinterpret_cast<uint32_t (*)[kPostSW]>(&s_c[0][0][0]);
-    uint32_t shv[kShR];
-#pragma unroll
-    for (int r = 0; r < kShR; ++r) {
-        const int i = threadIdx.x + 256 * r;
-        const int cy = i / kPostSW, cx = i - cy * kPostSW;
-        const int gx = gx0 - 2 + cx, gy = gy0 - 2 + cy;
-        const bool in = i < kPostSH * kPostSW && gx >= 0 && gy >= 0 && gx < W && gy < H;
-        shv[r] = in ? state_at((size_t)gy * W + gx) : 0u;
-    }
-#pragma unroll
-    for (int r = 0; r < kShR; ++r) {
-        const int i = threadIdx.x + 256 * r;
-        if (i < kPostSH * kPostSW) (&s_st[0][0])[i] = shv[r];
-    }
-    __syncthreads();
-    float dv[kStR];   // each pixel's darkening, from the marks before s_c is written
-#pragma unroll
-    for (int r = 0; r < kStR; ++r) {
-        const int i = threadIdx.x + 256 * r;
-        const int cy = i / kPostHW, cx = i - cy * kPostHW;
-        const int gx = gx0 - 1 + cx, gy = gy0 - 1 + cy;
-        dv[r] = 0.0f;
-        if (i < kPostHH * kPostHW && gx >= 1 && gy >= 1 && gx < W - 1 && gy < H - 1)
-            dv[r] = darken_at(&s_st[0][0], kPostSW, cy + 1, cx + 1);
-    }
-    // the shading fragments of the tile + halo 1: records, then their triangles, then the arithmetic
-    RowRec rv[kStR];
-    int recv[kStR];
-#pragma unroll
-    for (int r = 0; r < kStR; ++r) {
-        const int i = threadIdx.x + 256 * r;
-        const int cy = i / kPostHW, cx = i - cy * kPostHW;
-        const int gx = gx0 - 1 + cx, gy = gy0 - 1 + cy;
-        const bool in = i < kPostHH * kPostHW && gx >= 0 && gy >= 0 && gx < W && gy < H;
-        recv[r] = in ? (int)(s_st[cy + 1][cx + 1] & ~kStShadow) - 1 : -1;
-        if (recv[r] >= 0) {
-            const u64 o = row_off[gy] + (u64)(unsigned)recv[r];
-            if (o < rec_cap) rv[r] = recs[o];
-            else recv[r] = -1;
-        }
-    }
-    __syncthreads();   // the state words are dead: s_c's space is free
-    cg_vec4 tnv[kStR];
-    cg_vec3 colv[kStR];
-#pragma unroll
-    for (int r = 0; r < kStR; ++r)
-        if (recv[r] >= 0) {
-            const int t = rec_t(rv[r]);
-            tnv[r] = tris[t].normal;
-            colv[r] = tris[t].color;
-        }
-#pragma unroll
-    for (int r = 0; r < kStR; ++r) {
-        const int i = threadIdx.x + 256 * r;
-        if (i >= kPostHH * kPostHW) break;
-        const int cy = i / kPostHW, cx = i - cy * kPostHW;
-        const int gx = gx0 - 1 + cx, gy = gy0 - 1 + cy;
-        vec3 sc = v3(0.f, 0.f, 0.f), lo = sc, hi = sc;
-        const float d = dv[r];
-        if (recv[r] >= 0) {   // a shading fragment (:580-585)
-            const RowRec &R = rv[r];
-            const float fi = (float)(gx - R.lx);
-            const float z = R.lz + (R.sz * fi);                               // :543, as the fill evaluated it
-            const float X = R.lX + (R.sX * fi), Y = R.lY + (R.sY * fi);       // :547-548 numerators
-            const int t = rec_t(R);
-            vec3 N = v3(tnv[r].x, tnv[r].y, tnv[r].z);
-            int tex = 0;
-            uint32_t texel = 0u;
-            if (TEX && R.tex != 0 && rast_tex_present(A, R.tex)) {
-                tex = R.tex;
-                N = rast_tex_normal(A, tex, R.index, z, X, Y, gx, gy, N, texel);
-            }
-            const vec3 D = illum_D(A, z, X, Y, N);                            // :580-585 (:590-645)
-            const float4 s4 = make_float4(__int_as_float(t | (gx == R.first_x ? (1 << 30) : 0)), D.x, D.y, D.z);
-            shade3c(A, s4, colv[r], sc, lo, hi, tex, texel);
-        }
-        s_c[0][cy][cx] = sc.x; s_c[1][cy][cx] = sc.y; s_c[2][cy][cx] = sc.z;
-        s_c[3][cy][cx] = lo.x; s_c[4][cy][cx] = lo.y; s_c[5][cy][cx] = lo.z;
-        s_c[6][cy][cx] = hi.x; s_c[7][cy][cx] = hi.y; s_c[8][cy][cx] = hi.z;
-        s_d[cy][cx] = d;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < kPostTH * kPostTW; i += 256) {
-        const int ty = i / kPostTW, tx = i - ty * kPostTW;
-        const int x = gx0 + tx, y = gy0 + ty;
-        if (x >= W || y >= H) continue;
-        const size_t o = (size_t)y * W + x;
-        if (x < 1 || y < 1 || x >= W - 1 || y >= H - 1) {   // :283-284 border never written
-            argb[o] = 0u;
-            continue;
-        }
-        const int cy = ty + 1, cx = tx + 1;
-        auto tap = [&](int b, int yy, int xx) { return v3(s_c[b][yy][xx], s_c[b + 1][yy][xx], s_c[b + 2][yy][xx]); };
-        auto dk = [&](int yy, int xx) { const float d = s_d[yy][xx]; return v3(d, d, d); };
-        const int ty5[5] = {cy, cy - 1, cy + 1, cy, cy}, tx5[5] = {cx, cx, cx, cx - 1, cx + 1};  // c, up, down, left, right
-        vec3 sv[5], lv[5], hv[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            sv[k] = tap(0, ty5[k], tx5[k]);
-            lv[k] = tap(3, ty5[k], tx5[k]);
-            hv[k] = tap(6, ty5[k], tx5[k]);
-        }
-        sv[0] = sv[0] - dk(cy, cx);                        // darkened: itself, up, left
-        sv[1] = sv[1] - dk(cy - 1, cx);
-        sv[3] = sv[3] - dk(cy, cx - 1);
-        // :1741-1750 (x / 5.0f and / 3.0f via div_const, bit-identical)
-        vec3 val = div_const((((sv[0] + sv[1]) + sv[2]) + sv[3]) + sv[4], 5.0f, 1.0f / 5.0f);
-        vec3 val1 = div_const((((lv[0] + lv[1]) + lv[2]) + lv[3]) + lv[4], 5.0f, 1.0f / 5.0f);
-        vec3 val2 = div_const((((hv[0] + hv[1]) + hv[2]) + hv[3]) + hv[4], 5.0f, 1.0f / 5.0f);
-        val = div_const((val + val1) + val2, 3.0f, 1.0f / 3.0f);
-        argb[o] = put_pixel(val);
-    }
-}
+// The text is cg_rast_big_post_kernel.inc, once per output policy (as cg_rast.hip's post-pass):
+// rast_big_post_kernel stores PutPixelSDL's word, rast_big_post_f32_kernel (CG_PIX_RGBA_F32) the
+// float4 it would have been given.
+#define CG_RAST_POST_NAME rast_big_post_kernel
+#define CG_RAST_POST_F32 0
+#define CG_RAST_POST_OUT uint32_t
+#include "cg_rast_big_post_kernel.inc"
+#undef CG_RAST_POST_NAME
+#undef CG_RAST_POST_F32
+#undef CG_RAST_POST_OUT
+#define CG_RAST_POST_NAME rast_big_post_f32_kernel
+#define CG_RAST_POST_F32 1
+#define CG_RAST_POST_OUT float4
+#include "cg_rast_big_post_kernel.inc"
+#undef CG_RAST_POST_NAME
+#undef CG_RAST_POST_F32
+#undef CG_RAST_POST_OUT
 
 // ---- 5-7. colour modes 1-2 ----
 // nseg[s]: the entries of c that span s takes, one per fill segment its visible extent overlaps
@@ -850,7 +723,7 @@ int big_scan(cg_ctx *c, hipStream_t st, const int *in, long long N, u64 *out)
 // then S), generator, number and shade, post.  seq: the frame's record is written too.
 int big_colour(cg_ctx *c, const RastArgs &A, const cg_rast_params *p, const RowRec *recs, const u64 *row_off,
                const int *count, u64 n_recs, const u64 *rec_ent, u64 n_ent, float4 *state, uint32_t *d_argb,
-               float *d_depth, int32_t *d_shadow, hipStream_t st, const RastSeq *seq, long long *n_shaded)
+               float *d_depth, int32_t *d_shadow, hipStream_t st, const RastSeq *seq, long long *n_shaded, int pix)
 {
     hipError_t e;
     const size_t npx = (size_t)A.W * A.H, ne = n_ent > 0 ? (size_t)n_ent : 1;
@@ -892,7 +765,7 @@ int big_colour(cg_ctx *c, const RastArgs &A, const cg_rast_params *p, const RowR
     }
     if (d_argb) {   // null: a buffers call that asks for no picture
         KtScope kt(KT_RAST_BIG_POST, st);
-        launch_rast_post_direct(A, state, shadow, d_argb, st);
+        launch_rast_post_direct(A, state, shadow, d_argb, st, pix);
         if ((e = hipGetLastError()) != hipSuccess) return ctx_fail(c, e, "rast_post launch");
     }
     if (seq) {
@@ -905,10 +778,12 @@ int big_colour(cg_ctx *c, const RastArgs &A, const cg_rast_params *p, const RowR
 }
 
 // Span setup, row lists, fill and post over a clipped list whose length the host knows.
-// clip_ran: rast_clip_kernel initialised the first-fragment minimum on this stream.
+// clip_ran: rast_clip_kernel initialised the first-fragment minimum on this stream.  pix: d_argb's
+// pixel format (CG_PIX_RGBA_F32: float4 pixels from the post-pass's float kernels).
 int big_pipeline(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *p, cg_vec4 light,
                  const cg_vec4 *d_light, uint32_t *d_argb, float *d_depth, int32_t *d_shadow, hipStream_t st,
-                 cg_stats *stats, bool events_open, bool clip_ran, int tex_mask, const RastSeq *seq)
+                 cg_stats *stats, bool events_open, bool clip_ran, int tex_mask, const RastSeq *seq,
+                 int pix = CG_PIX_ARGB8888)
 {
     if (p->width <= 2 || p->height <= 2 || p->height > kRastMaxRows) return CG_E_INVALID;
     if (p->colour_mode != 0 && ctx_rast_forced_compact(c)) return ctx_invalid(c, kForcedColour);
@@ -1021,7 +896,7 @@ int big_pipeline(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *
     void *words = state;   // the ordered z-buffer's state words (RastFrame)
     if (colour) {
         const int rc = big_colour(c, A, p, recs, row_off, count, n_recs, rec_ent, n_ent, (float4 *)state, d_argb, d_depth,
-                                  d_shadow, st, seq, &n_shaded);
+                                  d_shadow, st, seq, &n_shaded, pix);
         if (rc) return rc;
         if (ctx_rast_want_owner(c)) {
             // the owner of a pixel is the ordered z-buffer's last writer whatever the colour mode
@@ -1051,7 +926,15 @@ int big_pipeline(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_params *
         if (d_argb) {   // null: a buffers call that asks for no picture
             KtScope kt(KT_RAST_BIG_POST, st);
             const int post_grid = xcd_grid(H, (W + kPostTW - 1) / kPostTW);
-            if (A.textured)
+            if (pix == CG_PIX_RGBA_F32 && A.textured)
+                hipLaunchKernelGGL(rast_big_post_f32_kernel<true>, dim3(post_grid), dim3(256), 0, st, d_tris, A,
+                                   (const void *)state, (const RowRec *)recs, (const u64 *)row_off, n_recs,
+                                   (float4 *)d_argb);
+            else if (pix == CG_PIX_RGBA_F32)
+                hipLaunchKernelGGL(rast_big_post_f32_kernel<false>, dim3(post_grid), dim3(256), 0, st, d_tris, A,
+                                   (const void *)state, (const RowRec *)recs, (const u64 *)row_off, n_recs,
+                                   (float4 *)d_argb);
+            else if (A.textured)
                 hipLaunchKernelGGL(rast_big_post_kernel<true>, dim3(post_grid), dim3(256), 0, st, d_tris, A,
                                    (const void *)state, (const RowRec *)recs, (const u64 *)row_off, n_recs, d_argb);
             else
@@ -1100,7 +983,7 @@ int rast_big_render(cg_ctx *c, const cg_rtri *d_tris, int n, const cg_rast_param
 // pipeline above over a list of exactly the clipped length.  *n_out: a device word that holds it.
 int rast_big_draw(cg_ctx *c, const cg_rtri *d_room, int n_room, const cg_rtri *d_boxes, int n_boxes,
                   const cg_rast_params *p, uint32_t *d_argb, float *d_depth, int32_t *d_shadow, hipStream_t st,
-                  cg_stats *stats, int **n_out, int tex_mask, const RastSeq *seq)
+                  cg_stats *stats, int **n_out, int tex_mask, const RastSeq *seq, int pix)
 {
     if (p->width <= 2 || p->height <= 2 || p->height > kRastMaxRows || p->focal == 0.0f) return CG_E_INVALID;
     if (p->colour_mode != 0 && ctx_rast_forced_compact(c)) return ctx_invalid(c, kForcedColour);
@@ -1143,7 +1026,7 @@ int rast_big_draw(cg_ctx *c, const cg_rtri *d_room, int n_room, const cg_rtri *d
     }
     if (n_out) *n_out = (int *)(pre + n_in);   // little-endian: the count's low word
     const int rc = big_pipeline(c, tris, n, p, cg_vec4{0, 0, 0, 1}, (const cg_vec4 *)(geo + 4), d_argb, d_depth, d_shadow,
-                                st, stats, true, n_in > 0, tex_mask, seq);
+                                st, stats, true, n_in > 0, tex_mask, seq, pix);
     if (rc == CG_OK) {   // clipped triangle -> input triangle: the counts and the prefix the gather used
         RastFrame &fr = *ctx_rast_frame(c);
         fr.counts = geo + 16;

@@ -16,7 +16,8 @@
 // reference tree); they are decoded like cv::imread does (cg_image_decode_jpeg).
 //
 //   rasteriser [--width W] [--height H] [--focal F] [--keys KEYS] [--out FILE]
-//              [--setting S] [--setting-boxes B] [--textures DIR] [--batch]
+//              [--setting S] [--setting-boxes B] [--textures DIR] [--batch] [--pfm FILE]
+//              [--auto-exposure PERMILLE[,TARGET]] [--tonemap linear|reinhard|reinhard-white:W]
 //
 // --batch: Update() runs over the whole key script first, each frame's globals
 // are recorded as a cg_rast_params, and one cg_rast_draw_sequence call renders
@@ -25,8 +26,17 @@
 // Draw carries from frame to frame besides, indirectLightPowerPerArea, follows
 // Draw's own rule while recording, with the frame's clipped triangle count
 // from cg_rast_prepare.
+// --pfm FILE: the last frame's picture before PutPixelSDL clamps it (cg_rast_draw_picture), as a
+// little-endian colour PFM: "PF", the size, "-1.0", then rows bottom-up of three floats a pixel.
+// --auto-exposure PERMILLE[,TARGET]: the run's frames go through one cg_rast_draw_exposed call (as
+// --batch records them): each frame's scale puts the upper edge of the luminance bin that holds its
+// PERMILLE-th thousandth of lit pixels at TARGET (default 1), no adaptation; the screenshot is the
+// last exposed frame and the scale of every frame is printed.
+// --tonemap: the curve between the scaled picture and PutPixelSDL (default linear; reinhard-white:W
+// maps W to white); with --tonemap alone the scale is 1.  Without these flags nothing changes.
 #include <cmath>
 #include <cstring>
+#include <fstream>
 #include <string>
 #include <vector>
 
@@ -55,6 +65,8 @@ vector<rast::Triangle> originalbox;                           // :85
 static cg_ctx *g_ctx = nullptr;
 static string g_keys;
 static size_t g_frame = 0;
+static cg_rast_params g_last;                                 // the latest frame drawn (--pfm)
+static bool g_drawn = false;
 
 static void die(int rc, const char *what)
 {
@@ -85,6 +97,8 @@ static cg_rast_params CurrentParams(const screen *screen)
 void Draw(screen *screen)
 {
     const cg_rast_params p = CurrentParams(screen);
+    g_last = p;
+    g_drawn = true;
     // geometry (shadow volumes + clip), fill and post-pass all on the GPU
     cg_stats st;
     int rc = cg_rast_draw(g_ctx, &p, screen->buffer, nullptr, nullptr, &st);
@@ -94,6 +108,26 @@ void Draw(screen *screen)
         if (st.n_tris > 0) indirectLightPowerPerArea = 0.2f * vec3(1, 1, 1);
     } else {
         randCalls += 3 * (uint64_t)st.n_shaded;              // :649-651 / :657-659 per fragment
+    }
+}
+
+// --pfm: the picture of the latest frame's parameters, unclamped
+static void SavePicturePFM(const char *path)
+{
+    const int W = g_last.width, H = g_last.height;
+    vector<float> rgba((size_t)W * H * 4);
+    int rc = cg_rast_draw_picture(g_ctx, &g_last, rgba.data(), nullptr);
+    if (rc) die(rc, "cg_rast_draw_picture");
+    ofstream f(path, ios::binary);
+    f << "PF\n" << W << " " << H << "\n-1.0\n";
+    vector<float> row((size_t)W * 3);
+    for (int y = H - 1; y >= 0; --y) {   // bottom row first
+        for (int x = 0; x < W; ++x) memcpy(&row[3 * x], &rgba[((size_t)y * W + x) * 4], 3 * sizeof(float));
+        f.write(reinterpret_cast<const char *>(row.data()), row.size() * sizeof(float));
+    }
+    if (!f) {
+        cerr << "cannot write " << path << endl;
+        exit(1);
     }
 }
 
@@ -162,9 +196,12 @@ static vector<uint8_t> read_map(const string &dir, const char *file, int n)
 
 int main(int argc, char *argv[])
 {
-    string out = "screenshot.bmp", tex_dir;
+    string out = "screenshot.bmp", tex_dir, pfm;
     int setting = 0, setting_boxes = 0;
-    bool batch = false;
+    bool batch = false, exposed = false;
+    cg_hdr_exposure_params expo{990, 1.0f, 1.0f, 1.0f, 1.0f};   // --tonemap alone: every scale is 1
+    int tone = CG_TONE_LINEAR;
+    float white2 = 1.0f;
     for (int i = 1; i < argc; i += 2) {
         string a = argv[i];
         if (a == "--batch") {
@@ -181,6 +218,29 @@ int main(int argc, char *argv[])
         else if (a == "--setting") setting = atoi(argv[i + 1]);
         else if (a == "--setting-boxes") setting_boxes = atoi(argv[i + 1]);
         else if (a == "--textures") tex_dir = argv[i + 1];
+        else if (a == "--pfm") pfm = argv[i + 1];
+        else if (a == "--auto-exposure") {
+            const string v = argv[i + 1];
+            const size_t comma = v.find(',');
+            expo.permille = atoi(v.substr(0, comma).c_str());
+            expo.target = comma == string::npos ? 1.0f : (float)atof(v.substr(comma + 1).c_str());
+            expo.scale_min = 1.0f / 65536.0f;
+            expo.scale_max = 65536.0f;
+            exposed = true;
+        } else if (a == "--tonemap") {
+            const string v = argv[i + 1];
+            if (v == "linear") tone = CG_TONE_LINEAR;
+            else if (v == "reinhard") tone = CG_TONE_REINHARD;
+            else if (v.rfind("reinhard-white:", 0) == 0) {
+                const float w = (float)atof(v.c_str() + 15);
+                tone = CG_TONE_REINHARD_WHITE;
+                white2 = w * w;
+            } else {
+                cerr << "--tonemap linear|reinhard|reinhard-white:W" << endl;
+                return 1;
+            }
+            exposed = true;
+        }
     }
     int rc = cg_create(0, &g_ctx);
     if (rc) die(rc, "cg_create");
@@ -204,7 +264,7 @@ int main(int argc, char *argv[])
     rc = cg_rast_set_scene(g_ctx, reinterpret_cast<const cg_rtri *>(originalroom.data()), (int)originalroom.size(),
                            reinterpret_cast<const cg_rtri *>(originalbox.data()), (int)originalbox.size());
     if (rc) die(rc, "cg_rast_set_scene");
-    if (batch) {
+    if (batch || exposed) {
         // the main loop's frames in one call: each Update()'s globals recorded, then every Draw()
         vector<cg_rast_params> ps;
         while (Update()) {
@@ -222,10 +282,21 @@ int main(int argc, char *argv[])
             const size_t px = (size_t)screen->width * screen->height;
             vector<uint32_t> frames(ps.size() * px);
             vector<cg_rast_seq_frame> info(ps.size() + 1);
-            rc = cg_rast_draw_sequence(g_ctx, ps.data(), (int)ps.size(), frames.data(), nullptr, nullptr, 0, 0,
-                                       info.data(), nullptr);
-            if (rc) die(rc, "cg_rast_draw_sequence");
+            if (exposed) {
+                vector<float> scales(ps.size());
+                rc = cg_rast_draw_exposed(g_ctx, ps.data(), (int)ps.size(), &expo, nullptr, tone, white2, frames.data(),
+                                          0, scales.data(), info.data(), nullptr);
+                if (rc) die(rc, "cg_rast_draw_exposed");
+                for (size_t f = 0; f < scales.size(); ++f) cout << "Exposure scale : " << scales[f] << endl;
+            } else {
+                rc = cg_rast_draw_sequence(g_ctx, ps.data(), (int)ps.size(), frames.data(), nullptr, nullptr, 0, 0,
+                                           info.data(), nullptr);
+                if (rc) die(rc, "cg_rast_draw_sequence");
+            }
             randCalls = info.back().rand_offset;
+            g_last = ps.back();                               // the last frame, at its chained index
+            g_last.rand_offset = info[ps.size() - 1].rand_offset;
+            g_drawn = true;
             memcpy(screen->buffer, frames.data() + (ps.size() - 1) * px, px * sizeof(uint32_t));
             SDL_Renderframe(screen);
         }
@@ -236,6 +307,7 @@ int main(int argc, char *argv[])
         }
     }
     SDL_SaveImage(screen, out.c_str());
+    if (!pfm.empty() && g_drawn) SavePicturePFM(pfm.c_str());
     KillSDL(screen);
     cg_destroy(g_ctx);
     return 0;

@@ -807,6 +807,65 @@ int cg_rast_draw_sequence_device(cg_ctx *ctx, const cg_rast_params *ps, int n_fr
  * n_frames == 0 returns CG_OK and touches nothing. */
 int cg_rast_draw_sequence(cg_ctx *ctx, const cg_rast_params *ps, int n_frames, uint32_t *argb, float *depth,
                           int32_t *shadow, size_t frame_stride, int chunk, cg_rast_seq_frame *info, cg_stats *stats);
+
+/* ---- The float picture (CG_PIX_RGBA_F32) and exposed frames ----
+ * The picture before PutPixelSDL clamps it: W * H pixels of four floats, 16-byte aligned.
+ * Interior pixel (1 <= x < W - 1, 1 <= y < H - 1): x, y, z the vec3 that antiAliasing(y, x)
+ * returns (skeleton.cpp:305, :1736-1753), evaluated in raster order as the reference does, w =
+ * 1.0f.  Border pixel: +0 four times -- the reference never calls PutPixelSDL there, and w = 0
+ * makes it "uncovered" for cg_hdr_histogram_device.  PutPixelSDL of the interior pixels is
+ * cg_rast_draw_device's frame.  It cannot be rebuilt from cg_rast_draw_buffers' planes: those
+ * hold every pixel's darkening, the picture's lower and right taps are from before theirs.
+ *
+ * One Draw; d_rgba is W * H float4.  Route, colour mode, rand_offset, indirect_first, textures
+ * and the waits per route are as cg_rast_draw_device; d_depth / d_shadow (may be NULL) too. */
+int cg_rast_draw_picture_device(cg_ctx *ctx, const cg_rast_params *p, float *d_rgba, float *d_depth,
+                                int32_t *d_shadow, void *stream);
+/* Host-memory form, synchronous: rgba is W * H * 4 floats. */
+int cg_rast_draw_picture(cg_ctx *ctx, const cg_rast_params *p, float *rgba, cg_stats *stats);
+/* cg_rast_draw_sequence_device with float frames: frame f at d_rgba + f * frame_stride pixels
+ * of 16 bytes (0 = W * H).  Same rand() chain, same d_info records, same lanes.  The one
+ * difference: a frame whose status is non-zero (CG_E_CAPACITY, dense route) gets all-zero pixels
+ * with w = 0 -- the plane is defined, not left as it was (its depth and shadow planes are left). */
+int cg_rast_draw_sequence_picture_device(cg_ctx *ctx, const cg_rast_params *ps, int n_frames, float *d_rgba,
+                                         float *d_depth, int32_t *d_shadow, size_t frame_stride,
+                                         cg_rast_seq_frame *d_info, void *stream);
+/* The rasteriser's pack: cg_rt_tonemap_pack_device (arguments, strides, errors) with two rules
+ * of its own.  Border rule: a pixel with !(w > 0.0f) packs to 0u (the raytracer's pack would
+ * write 0x80000000 there).  Clamp rule: each channel is c0 = c > 0.0f ? c : 0.0f before v = c0 *
+ * scale, so a NaN or a negative channel is black as PutPixelSDL shows it, whatever the scale and
+ * curve (Reinhard's v / (1 + v) has a pole at -1).  LINEAR with a scale of exactly 1.0f gives
+ * cg_rast_draw_device's frame bit for bit, border included.  Histogram and exposure of float
+ * pictures are cg_hdr_histogram_device (channels = 4: the border is uncovered, n_uncovered =
+ * 2 W + 2 H - 4; a pixel whose luminance is not positive is dark) and cg_hdr_exposure_device. */
+int cg_rast_tonemap_pack_device(cg_ctx *ctx, const float *d_rgba, size_t n_pixels, int n_frames, size_t src_stride,
+                                const float *d_scales, int op, float white2, uint32_t *d_argb, size_t dst_stride,
+                                void *stream);
+/* Host-only restatement of one pixel of it (no device, no context); NULL rgba gives 0. */
+uint32_t cg_rast_pack_pixel(const float rgba[4], float scale, int op, float white2);
+/* A key script rendered, exposed and packed without a host wait, as cg_rt_render_exposed_device:
+ * the frames of cg_rast_draw_sequence_picture_device in chunks of 8 into scratch the context
+ * owns (grow-only, 8 * W * H * 16 bytes), then histogram, exposure and the pack above per chunk.
+ * Frame f as ARGB8888 at d_argb + f * frame_stride pixels (0: W * H), its scale in d_scales[f]
+ * (device, n_frames floats, required), its record in d_info (device, n_frames + 1 records,
+ * required); the rand() index passes from chunk to chunk through d_info and is never read back.
+ * Frame 0 of the call takes d_prev (device, may be NULL) as its previous scale, frame 0 of a
+ * later chunk d_scales[f - 1], as cg_rt_render_exposed_device defines it.  A frame flagged
+ * CG_E_CAPACITY is the all-uncovered picture: an empty histogram, t_f = 1.0f clamped, ARGB 0; the
+ * call still returns CG_OK.  On the dense route, after the first call of a size it neither
+ * allocates nor waits for the device; on the compact route it waits where
+ * cg_rast_draw_sequence_device waits.  CG_E_NOSCENE before cg_rast_set_scene; CG_E_INVALID as
+ * cg_rast_draw_sequence_device and the cg_hdr_* calls; n_frames == 0 touches nothing. */
+int cg_rast_draw_exposed_device(cg_ctx *ctx, const cg_rast_params *ps, int n_frames,
+                                const cg_hdr_exposure_params *params, const float *d_prev, int op, float white2,
+                                uint32_t *d_argb, size_t frame_stride, float *d_scales,
+                                cg_rast_seq_frame *d_info, void *stream);
+/* Host-memory form, synchronous: the same frames, scales[n_frames] and (optional) info[n_frames +
+ * 1] in host memory, prev a host float or NULL; each chunk's download follows its render.
+ * Returns CG_E_CAPACITY, after delivering everything, if a frame was flagged. */
+int cg_rast_draw_exposed(cg_ctx *ctx, const cg_rast_params *ps, int n_frames, const cg_hdr_exposure_params *params,
+                         const float *prev, int op, float white2, uint32_t *argb, size_t frame_stride,
+                         float *scales, cg_rast_seq_frame *info, cg_stats *stats);
 /* Test hook: capacity of the materialised rand() stream in fragments (3 values each);
  * 0 = automatic, 4 * W * H. */
 int cg_rast_set_rand_capacity(cg_ctx *ctx, long long fragments);
