@@ -147,6 +147,7 @@ _SIGS = {
     "cg_destroy": (None, [P]),
     "cg_last_error": (C.c_char_p, [P]),
     "cg_device_count": (C.c_int, []),
+    "cg_debug_live": (C.c_int, [C.POINTER(C.c_longlong)]),
     "cg_rt_load_test_model": (C.c_int, [C.POINTER(Tri), C.c_int, C.POINTER(Sphere)]),
     "cg_glibc_rand": (C.c_int, [C.c_uint64, C.c_int, P]),
     "cg_starfield_init": (C.c_int, [P, C.c_int]),
@@ -897,6 +898,16 @@ class Dist:
                                                           P(d_frames) if d_frames else None, frame_stride,
                                                           P(stream) if stream else None),
                         "cg_rt_render_frames_dist")
+
+
+def debug_live():
+    """Test hook cg_debug_live: (device allocations, pinned allocations, events, streams) that the
+    process's contexts and cg_dist handles hold right now."""
+    out = (C.c_longlong * 4)()
+    rc = load().cg_debug_live(out)
+    if rc != 0:
+        raise RuntimeError(f"cg_debug_live failed ({rc})")
+    return tuple(out)
 
 
 class Context:

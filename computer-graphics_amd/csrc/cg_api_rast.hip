@@ -136,8 +136,8 @@ extern "C" int cg_rast_scratch_info(cg_ctx *c, uint64_t out[5])
         return b;
     };
     out[0] = held(c);
-    for (const cg_ctx *l : c->lanes)
-        if (l) out[0] += held(l);
+    for (const auto &l : c->lanes)
+        if (l) out[0] += held(l.get());
     out[1] = out[2] = out[3] = out[4] = 0;
     if (L.route < 0) return CG_OK;
     out[1] = (uint64_t)L.route;
@@ -204,7 +204,7 @@ extern "C" int cg_rast_draw_frames_device(cg_ctx *c, const cg_rast_params *ps, i
     CG_TRY(c, hipEventRecord(c->start_ev, st), "event");
     for (int k = 0; k < L; ++k) CG_TRY(c, hipStreamWaitEvent(c->lanes[k]->stream, c->start_ev, 0), "lane wait");
     for (int f = 0; f < n_frames; ++f) {
-        cg_ctx *l = c->lanes[f % L];
+        cg_ctx *l = c->lanes[f % L].get();
         const size_t o = (size_t)f * stride;
         int rc = rast_draw_device(l, (const cg_rtri *)l->rroom.p, l->n_room, (const cg_rtri *)l->rboxes.p, l->n_boxes,
                                   &ps[f], d_argb + o, d_depth ? d_depth + o : nullptr, d_shadow ? d_shadow + o : nullptr,
@@ -227,16 +227,18 @@ extern "C" int cg_rast_draw_frames_device(cg_ctx *c, const cg_rast_params *ps, i
 // device to device when it changed, which waits).
 static int rast_lanes_ready(cg_ctx *c, int L)
 {
-    if (!c->start_ev) CG_TRY(c, hipEventCreateWithFlags(&c->start_ev, hipEventDisableTiming), "event");
+    CG_TRY(c, c->start_ev.ensure(), "event");
     for (int k = 0; k < L; ++k) {
         if (!c->lanes[k]) {
-            int rc = cg_create(c->device, &c->lanes[k]);
+            cg_ctx *lane = nullptr;
+            int rc = cg_create(c->device, &lane);
             if (rc) return ctx_invalid(c, "lane context");
-            c->lanes[k]->tex_owner = c;
-            CG_TRY(c, hipEventCreateWithFlags(&c->lane_ev[k], hipEventDisableTiming), "event");
+            c->lanes[k].reset(lane);
+            lane->tex_owner = c;
+            CG_TRY(c, c->lane_ev[k].ensure(), "event");
             c->lane_gen[k] = c->scene_gen - 1;
         }
-        cg_ctx *l = c->lanes[k];
+        cg_ctx *l = c->lanes[k].get();
         l->rast_route = c->rast_route;          // the lanes follow their parent
         l->route_limit = c->route_limit;
         if (c->lane_gen[k] != c->scene_gen) {   // the parent's scene, device to device
@@ -337,10 +339,10 @@ static int rast_sequence_device(cg_ctx *c, const cg_rast_params *ps, int n_frame
     }
     uint32_t *win[cg_ctx::kRastLanes] = {};
     for (int k = 0; k < L; ++k) {
-        cg_ctx *l = L > 1 ? c->lanes[k] : c;
+        cg_ctx *l = L > 1 ? c->lanes[k].get() : c;
         hipError_t e;
         if (L > 1) {
-            if (!c->seq_ev[k]) CG_TRY(c, hipEventCreateWithFlags(&c->seq_ev[k], hipEventDisableTiming), "event");
+            CG_TRY(c, c->seq_ev[k].ensure(), "event");
             if (!(win[k] = (uint32_t *)ctx_buf(l, kBufSeq, 64 * sizeof(uint32_t), &e))) return ctx_fail(c, e, "alloc window");
         }
         if (!colour || compact) continue;
@@ -357,7 +359,7 @@ static int rast_sequence_device(cg_ctx *c, const cg_rast_params *ps, int n_frame
     const size_t wpp = pix == CG_PIX_RGBA_F32 ? 4 : 1;   // 4-byte words a pixel of d_argb takes
     for (int f = 0; f < n_frames; ++f) {
         const size_t o = (size_t)f * stride;
-        cg_ctx *l = L > 1 ? c->lanes[f % L] : c;
+        cg_ctx *l = L > 1 ? c->lanes[f % L].get() : c;
         q.info = d_info + f;
         q.first = f == 0 && !resume;
         q.win = win[f % L];
@@ -708,17 +710,14 @@ extern "C" int cg_rast_draw_sequence(cg_ctx *c, const cg_rast_params *ps, int n_
         return std::max(1, std::min(e ? std::atoi(e) : 2, (int)cg_ctx::kRastLanes));
     }();
     constexpr int NS = cg_ctx::kRastHostSlots;
-    if (!c->xfer) {
-        CG_TRY(c, hipStreamCreateWithFlags(&c->xfer, hipStreamNonBlocking), "copy stream");
-        for (int k = 0; k < 2; ++k) {
-            CG_TRY(c, hipEventCreateWithFlags(&c->ev_rdone[k], hipEventDisableTiming), "copy event");
-            CG_TRY(c, hipEventCreateWithFlags(&c->ev_cdone[k], hipEventDisableTiming), "copy event");
-        }
+    CG_TRY(c, c->xfer.ensure(hipStreamNonBlocking), "copy stream");
+    for (int k = 0; k < 2; ++k) {
+        CG_TRY(c, c->ev_rdone[k].ensure(), "copy event");
+        CG_TRY(c, c->ev_cdone[k].ensure(), "copy event");
     }
     for (int k = 0; k < NS; ++k) {
-        if (c->rs_rdone[k]) continue;
-        CG_TRY(c, hipEventCreateWithFlags(&c->rs_rdone[k], hipEventDisableTiming), "copy event");
-        CG_TRY(c, hipEventCreateWithFlags(&c->rs_cdone[k], hipEventDisableTiming), "copy event");
+        CG_TRY(c, c->rs_rdone[k].ensure(), "copy event");
+        CG_TRY(c, c->rs_cdone[k].ensure(), "copy event");
     }
     // Every return below, error or not, leaves nothing of this call running (rt_render_frames_host).
     struct Drain {
@@ -736,15 +735,9 @@ extern "C" int cg_rast_draw_sequence(cg_ctx *c, const cg_rast_params *ps, int n_
     }
     const size_t rec_bytes = ((size_t)n_frames + 1) * sizeof(cg_rast_seq_frame);
     CG_TRY(c, c->rs_info.ensure(rec_bytes), "alloc records");
-    if (c->rs_host_bytes < rec_bytes + sizeof(int)) {
-        if (c->rs_host) (void)hipHostFree(c->rs_host);
-        c->rs_host = nullptr;
-        c->rs_host_bytes = 0;
-        CG_TRY(c, hipHostMalloc(&c->rs_host, rec_bytes + sizeof(int), hipHostMallocDefault), "alloc host records");
-        c->rs_host_bytes = rec_bytes + sizeof(int);
-    }
-    cg_rast_seq_frame *d_info = (cg_rast_seq_frame *)c->rs_info.p, *rec = (cg_rast_seq_frame *)c->rs_host;
-    int *h_ntris = (int *)((char *)c->rs_host + rec_bytes);
+    CG_TRY(c, c->rs_host.ensure(rec_bytes + sizeof(int)), "alloc host records");
+    cg_rast_seq_frame *d_info = (cg_rast_seq_frame *)c->rs_info.p, *rec = (cg_rast_seq_frame *)c->rs_host.p;
+    int *h_ntris = (int *)((char *)c->rs_host.p + rec_bytes);
     const int nchunks = (n_frames + ch - 1) / ch;
     auto plane = [&](void *dst, const void *src, int f0, int nf) -> hipError_t {   // 4-byte pixels
         if (stride == px)

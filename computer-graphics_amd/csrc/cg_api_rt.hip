@@ -209,8 +209,8 @@ extern "C" int cg_rt_sequence_runs(const cg_rt_camera *cams, int n_frames, int n
 // second frame in flight of rt_render_frames).
 struct BigSlot {
     DevBuf *tc, *big, *frame;
-    unsigned long long **demand;
-    hipEvent_t *ev;
+    PinnedBuf *demand;   // unsigned long long [4]
+    Event *ev;
     bool *ev_live;
 };
 static BigSlot big_slot(cg_ctx *c, int q)
@@ -367,7 +367,7 @@ int rt_enqueue(cg_ctx *c, const RtFrame &Fin, void *d_out_v, hipStream_t st, int
 static bool big_observe(cg_ctx *c, bool sizing, int q)
 {
     const BigSlot b = big_slot(c, q);
-    std::memcpy(c->big_last, *b.demand, sizeof(c->big_last));
+    std::memcpy(c->big_last, b.demand->p, sizeof(c->big_last));
     const unsigned long long *d = c->big_last;
     long long *cap[4] = {&c->big_caps.sup, &c->big_caps.bin, &c->big_caps.sbin, &c->big_caps.sorted};
     bool over = false;
@@ -393,12 +393,11 @@ static bool big_observe(cg_ctx *c, bool sizing, int q)
 static int rt_big_enqueue(cg_ctx *c, const RtFrame &F, uint32_t *d_out, hipStream_t st, int slot)
 {
     const BigSlot S = big_slot(c, slot);
-    if (!*S.demand) {
-        CG_TRY(c, hipHostMalloc((void **)S.demand, 4 * sizeof(unsigned long long), hipHostMallocDefault),
-               "alloc pool demand");
-        std::memset(*S.demand, 0, 4 * sizeof(unsigned long long));
-        CG_TRY(c, hipEventCreateWithFlags(S.ev, hipEventDisableTiming), "pool event");
+    if (!S.demand->p) {
+        CG_TRY(c, S.demand->ensure(4 * sizeof(unsigned long long)), "alloc pool demand");
+        std::memset(S.demand->p, 0, 4 * sizeof(unsigned long long));
     }
+    CG_TRY(c, S.ev->ensure(), "pool event");
     if (c->big_caps.sup == 0) {   // first guess; the first frame corrects it
         const long long g = 2ll * F.n_tris + 65536;
         c->big_caps = BigCaps{g, g, 4096, 2 * g};
@@ -429,7 +428,7 @@ static int rt_big_enqueue(cg_ctx *c, const RtFrame &F, uint32_t *d_out, hipStrea
         CG_TRY(c, launch_rt_big(F, (RtTri *)S.tc->p, (const RtShade *)c->shade.p, (const RtSphere *)c->sph.p,
                                 c->grid, big.p, d_out, st, (const RtGeo *)c->geo.p, (const cg_tri *)c->tris.p,
                                 c->pend_cap, c->big_caps,
-                                *S.demand, dry),
+                                (unsigned long long *)S.demand->p, dry),
                "rt_big launch");
         CG_TRY(c, hipEventRecord(*S.ev, st), "pool event");
         *S.ev_live = true;
@@ -533,7 +532,7 @@ extern "C" int cg_rt_pixel_ray(const cg_rt_camera *cam, int x, int y, int sub_ra
 static bool hits_observe(cg_ctx *c, bool sizing)
 {
     cg_ctx::HitsSlot &S = c->hits;
-    std::memcpy(c->big_last, S.demand, sizeof(c->big_last));
+    std::memcpy(c->big_last, S.demand.p, sizeof(c->big_last));
     const unsigned long long *d = c->big_last;
     long long *cap[4] = {&S.caps.sup, &S.caps.bin, &S.caps.sbin, &S.caps.sorted};
     bool over = false;
@@ -554,12 +553,11 @@ static bool hits_observe(cg_ctx *c, bool sizing)
 static int rt_hits_big_enqueue(cg_ctx *c, const RtFrame &F, const RtHits &Hs, hipStream_t st)
 {
     cg_ctx::HitsSlot &S = c->hits;
-    if (!S.demand) {
-        CG_TRY(c, hipHostMalloc((void **)&S.demand, 4 * sizeof(unsigned long long), hipHostMallocDefault),
-               "alloc pool demand");
-        std::memset(S.demand, 0, 4 * sizeof(unsigned long long));
-        CG_TRY(c, hipEventCreateWithFlags(&S.ev, hipEventDisableTiming), "pool event");
+    if (!S.demand.p) {
+        CG_TRY(c, S.demand.ensure(4 * sizeof(unsigned long long)), "alloc pool demand");
+        std::memset(S.demand.p, 0, 4 * sizeof(unsigned long long));
     }
+    CG_TRY(c, S.ev.ensure(), "pool event");
     CG_TRY(c, S.tc.ensure((size_t)std::max(c->n_tris, 1) * sizeof(RtTri)), "alloc tri constants");
     if (c->big_fixed) {
         S.caps = c->big_caps;
@@ -586,7 +584,7 @@ static int rt_hits_big_enqueue(cg_ctx *c, const RtFrame &F, const RtHits &Hs, hi
         CG_TRY(c, S.big.ensure(need), "alloc hits scratch");
         CG_TRY(c, launch_rt_big(F, (RtTri *)S.tc.p, (const RtShade *)c->shade.p, (const RtSphere *)c->sph.p, c->grid,
                                 S.big.p, nullptr, st, (const RtGeo *)c->geo.p, (const cg_tri *)c->tris.p, 0, S.caps,
-                                S.demand, dry, &Hs),
+                                (unsigned long long *)S.demand.p, dry, &Hs),
                "rt_big hits launch");
         CG_TRY(c, hipEventRecord(S.ev, st), "pool event");
         S.ev_live = true;
@@ -792,13 +790,13 @@ static int rt_enqueue_lattice_batch(cg_ctx *c, const RtFrame &F0, const cg_rt_ca
             const char *pe = std::getenv("CG_AUX_PRIO");
             int lo = 0, hi = 0;
             if (pe && pe[0] == '1' && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess)
-                CG_TRY(c, hipStreamCreateWithPriority(&c->aux, hipStreamNonBlocking, hi), "aux stream");
+                CG_TRY(c, c->aux.ensure_priority(hipStreamNonBlocking, hi), "aux stream");
             else
-                CG_TRY(c, hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking), "aux stream");
+                CG_TRY(c, c->aux.ensure(hipStreamNonBlocking), "aux stream");
         }
         for (int k = 0; k < 2; ++k) {
-            CG_TRY(c, hipEventCreateWithFlags(&c->ev_cert[k], hipEventDisableTiming), "aux event");
-            CG_TRY(c, hipEventCreateWithFlags(&c->ev_lat[k], hipEventDisableTiming), "aux event");
+            CG_TRY(c, c->ev_cert[k].ensure(), "aux event");
+            CG_TRY(c, c->ev_lat[k].ensure(), "aux event");
             CG_TRY(c, hipEventRecord(c->ev_lat[k], c->aux), "aux event");
         }
     }
@@ -993,16 +991,14 @@ static int rt_enqueue_each(cg_ctx *c, int first, int count, bool big, uint8_t *o
 {
     const int ns = (count > 1 && big) ? std::min(big_slots(), count) : 1;
     if (ns > 1) {
-        if (!c->bev_start) CG_TRY(c, hipEventCreateWithFlags(&c->bev_start, hipEventDisableTiming), "slot event");
+        CG_TRY(c, c->bev_start.ensure(), "slot event");
         // the other slots start after what the caller queued before this
         // call (the scene, the lights just uploaded on st)
         CG_TRY(c, hipEventRecord(c->bev_start, st), "slot event");
         for (int q = 1; q < ns; ++q) {
             cg_ctx::ExtraSlot &x = c->xs[q - 1];
-            if (!x.st) {
-                CG_TRY(c, hipStreamCreateWithFlags(&x.st, hipStreamNonBlocking), "slot stream");
-                CG_TRY(c, hipEventCreateWithFlags(&x.done, hipEventDisableTiming), "slot event");
-            }
+            CG_TRY(c, x.st.ensure(hipStreamNonBlocking), "slot stream");
+            CG_TRY(c, x.done.ensure(), "slot event");
             CG_TRY(c, hipStreamWaitEvent(x.st, c->bev_start, 0), "slot wait");
         }
     }
@@ -1042,19 +1038,15 @@ static int rt_enqueue_sequence(cg_ctx *c, const RtFrame &F0, const cg_light *lig
     // the slot: lights (n_frames x n_lights RtLight), then the records
     const size_t lbytes = (size_t)n_frames * n_lights * sizeof(RtLight), rbytes = (size_t)n_frames * sizeof(RtFrameRec);
     const size_t bytes = lbytes + rbytes;
-    if (bytes > c->seq[0].dev.bytes || bytes > c->seq[0].host_bytes) {
+    if (bytes > c->seq[0].dev.bytes || bytes > c->seq[0].host.bytes) {
         const size_t grow = bytes + bytes / 2;   // a somewhat longer call later allocates nothing
         CG_TRY(c, hipDeviceSynchronize(), "drain before resizing sequence slots");
         for (auto &q : c->seq) {
             CG_TRY(c, q.dev.ensure(grow), "alloc sequence slot");
-            if (q.host) (void)hipHostFree(q.host);
-            q.host = nullptr;
-            q.host_bytes = 0;
-            CG_TRY(c, hipHostMalloc(&q.host, grow, hipHostMallocDefault), "alloc sequence staging");
-            q.host_bytes = grow;
-            if (!q.up) {
-                CG_TRY(c, hipEventCreateWithFlags(&q.up, hipEventDisableTiming), "sequence event");
-                CG_TRY(c, hipEventCreateWithFlags(&q.done, hipEventDisableTiming), "sequence event");
+            CG_TRY(c, q.host.ensure(grow), "alloc sequence staging");
+            if (!q.up || !q.done) {
+                CG_TRY(c, q.up.ensure(), "sequence event");
+                CG_TRY(c, q.done.ensure(), "sequence event");
                 CG_TRY(c, hipEventRecord(q.up, st), "sequence event");
                 CG_TRY(c, hipEventRecord(q.done, st), "sequence event");
             }
@@ -1075,8 +1067,8 @@ static int rt_enqueue_sequence(cg_ctx *c, const RtFrame &F0, const cg_light *lig
         hipStream_t st;
         ~Done() { (void)hipEventRecord(ev, st); }
     } done_on_exit{S.done, st};
-    RtLight *hl = (RtLight *)S.host;
-    RtFrameRec *hr = (RtFrameRec *)((uint8_t *)S.host + lbytes);
+    RtLight *hl = (RtLight *)S.host.p;
+    RtFrameRec *hr = (RtFrameRec *)((uint8_t *)S.host.p + lbytes);
     const RtLight *dl = (const RtLight *)S.dev.p;
     const RtFrameRec *dr = (const RtFrameRec *)((const uint8_t *)S.dev.p + lbytes);
     for (size_t l = 0; l < (size_t)n_frames * n_lights; ++l) hl[l] = rt_light_of(lights[l]);
@@ -1090,7 +1082,7 @@ static int rt_enqueue_sequence(cg_ctx *c, const RtFrame &F0, const cg_light *lig
         light_summary(hl + (size_t)f * n_lights, n_lights, r.lmin, r.lmax, r.lc, r.lrho);
         r.light_off = (uint32_t)((size_t)f * n_lights);
     }
-    CG_TRY(c, hipMemcpyAsync(S.dev.p, S.host, bytes, hipMemcpyHostToDevice, st), "upload sequence");
+    CG_TRY(c, hipMemcpyAsync(S.dev.p, S.host.p, bytes, hipMemcpyHostToDevice, st), "upload sequence");
     CG_TRY(c, hipEventRecord(S.up, st), "sequence event");
     // frame f as rt_enqueue and the lattice launches take it: its shape, the scene, its record
     auto frame_of = [&](int f, RtFrame &F) -> int {

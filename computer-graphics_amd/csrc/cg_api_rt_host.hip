@@ -354,12 +354,10 @@ static int rt_render_frames_host(cg_ctx *c, const cg_light *lights, int n_lights
     const size_t stride = frame_stride ? frame_stride : px;
     if (stride < px) return CG_E_INVALID;
     const int ch = chunk ? std::min(chunk, 64) : 8;
-    if (!c->xfer) {
-        CG_TRY(c, hipStreamCreateWithFlags(&c->xfer, hipStreamNonBlocking), "copy stream");
-        for (int k = 0; k < 2; ++k) {
-            CG_TRY(c, hipEventCreateWithFlags(&c->ev_rdone[k], hipEventDisableTiming), "copy event");
-            CG_TRY(c, hipEventCreateWithFlags(&c->ev_cdone[k], hipEventDisableTiming), "copy event");
-        }
+    CG_TRY(c, c->xfer.ensure(hipStreamNonBlocking), "copy stream");
+    for (int k = 0; k < 2; ++k) {
+        CG_TRY(c, c->ev_rdone[k].ensure(), "copy event");
+        CG_TRY(c, c->ev_cdone[k].ensure(), "copy event");
     }
     // Every return below, error or not, leaves nothing of this call running:
     // earlier chunks' downloads may still be writing into argb (asynchronous

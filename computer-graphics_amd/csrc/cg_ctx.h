@@ -1,5 +1,7 @@
 // cg_ctx.h -- struct cg_ctx and what it is made of, for cg_ctx.hip and the cg_api_*.hip files
-// alone: kernel files see the context through cg_host.h's accessors.
+// alone: kernel files see the context through cg_host.h's accessors.  Every device buffer,
+// pinned block, event and stream of the context is a member of an owning type (cg_own.h) and
+// is freed by that member's destructor; ~cg_ctx only waits for the work still in flight.
 #pragma once
 
 #include <algorithm>
@@ -14,28 +16,6 @@
 #include "cg_rt_grid.h"
 
 using namespace cg;
-
-// Grow-only device buffer.
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    hipError_t ensure(size_t n)
-    {
-        if (n <= bytes) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-        hipError_t e = hipMalloc(&p, n);
-        if (e == hipSuccess) bytes = n;
-        return e;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-};
 
 // Host threads that store the certified-black columns of frames delivered
 // into host memory (cg_rt_render / cg_rt_render_frames): a frame's 3.2 MB of
@@ -126,9 +106,20 @@ class HostFill {
 };
 
 struct cg_ctx {
+    // Members are destroyed in reverse order of declaration, after ~cg_ctx has waited for the
+    // work in flight.  So a stream is declared before the buffers and events used on it (it goes
+    // last), and a member that reads another at destruction is declared after that other.
+    ~cg_ctx();
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Stream stream;
+    // Batched lattice launches pipeline their certificate kernels on `aux`:
+    // call j+1's certificates run beside call j's lattice kernel, each call
+    // with its own slot of buffers (rt_enqueue_lattice_batch).
+    Stream aux;
+    // cg_rt_render_frames, cg_rast_draw_sequence (host output): chunks render into two device
+    // slots and download on `xfer` while the next chunk renders
+    Stream xfer;
+    Event ev0, ev1;   // timing events
     std::string err;
     // RT scene
     int n_tris = -1, n_sph = 0;
@@ -147,11 +138,7 @@ struct cg_ctx {
     } last_masks;
     // how the latest batched lattice call was launched, for cg_rt_lattice_path
     int last_path[4] = {0, 0, 0, 0};   // measured order, published certificates, forced uncertified, workgroups
-    // Batched lattice launches pipeline their certificate kernels on `aux`:
-    // call j+1's certificates run beside call j's lattice kernel, each call
-    // with its own slot of buffers (rt_enqueue_lattice_batch).
-    hipStream_t aux = nullptr;
-    hipEvent_t ev_cert[2] = {nullptr, nullptr}, ev_lat[2] = {nullptr, nullptr};
+    Event ev_cert[2], ev_lat[2];      // the aux pipeline's, per slot
     int slot = 0;
     DevBuf ptc[2], plat[2], psup[2], pumask[2];
     // measured lattice order (LatOrder, cg_internal.h): per slot, the recording
@@ -162,15 +149,14 @@ struct cg_ctx {
     uint32_t cert_gen = 0u;           // generation of the latest published call
     unsigned long long lrec_key[2] = {0ull, 0ull};   // geometry key of the slot's recording (0: none)
     unsigned rt_scene_gen = 0;                       // cg_rt_set_scene count (part of the key)
-    // cg_rt_render_frames (host output): chunks render into two device slots
-    // and download on `xfer` while the next chunk renders
-    hipStream_t xfer = nullptr;
-    hipEvent_t ev_rdone[2] = {nullptr, nullptr}, ev_cdone[2] = {nullptr, nullptr};
+    // cg_rt_render_frames (host output): the two device slots and their events on `xfer`
+    Event ev_rdone[2], ev_cdone[2];
     DevBuf hslot[2];
     // cg_rt_render_exposed_device: a chunk's CG_PIX_RGBA_F32 frames and histograms; the host form's
     // chunk of ARGB frames, its scales and previous scale
     DevBuf hdr_rgba, hdr_hist, hdr_argb, hdr_scales;
-    std::unique_ptr<HostFill> hfill;    // their black columns (created on first use)
+    // their black columns (created on first use); declared after hslot: the threads end first
+    std::unique_ptr<HostFill> hfill;
     RtGrid grid{};                      // large scenes only (n_tris > 64)
     GridBuild gbuild;                   // cg_rt_set_scene_device: the device builder's scratch and counts
     uint64_t grid_entries = 0;          // entries of the installed grid (either builder)
@@ -182,8 +168,8 @@ struct cg_ctx {
     bool big_sized = false;
     long long big_key = -1;                     // frame shape / path the pools were sized for
     bool big_fixed = false;                     // cg_rt_set_pool_caps: capacities pinned (test hook)
-    unsigned long long *big_demand = nullptr;   // pinned [4]: the latest frame's demand
-    hipEvent_t big_ev = nullptr;
+    PinnedBuf big_demand;                       // unsigned long long [4]: the latest frame's demand
+    Event big_ev;
     bool big_ev_live = false;
     unsigned long long big_last[4] = {};
     bool big_last_hits = false;                 // big_last came from a hits-only pass (its own capacities)
@@ -195,13 +181,13 @@ struct cg_ctx {
     // each other's gaps.
     static constexpr int kBigSlots = 4;
     struct ExtraSlot {
+        Stream st;
         DevBuf tc, big, frame;
-        unsigned long long *demand = nullptr;
-        hipEvent_t ev = nullptr, done = nullptr;
+        PinnedBuf demand;
+        Event ev, done;
         bool ev_live = false;
-        hipStream_t st = nullptr;
     } xs[kBigSlots - 1];
-    hipEvent_t bev_start = nullptr;
+    Event bev_start;
     // Hit planes (cg_rt_hits_device, cg_rt_pick).  A hits-only pass of a large scene has buffers of
     // its own -- the pass's RtTri, scratch, demand read-back -- so it never touches what a frame in
     // flight on another stream reads, and pool capacities and a sizing state of its own, so frames
@@ -211,8 +197,8 @@ struct cg_ctx {
         BigCaps caps{};
         bool sized = false;
         long long key = -1;
-        unsigned long long *demand = nullptr;
-        hipEvent_t ev = nullptr;
+        PinnedBuf demand;
+        Event ev;
         bool ev_live = false;
     } hits;
     // the scene's box (rt_scene_box, once per cg_rt_set_scene): cg_dist's column
@@ -227,9 +213,8 @@ struct cg_ctx {
     // copy is).  Both slots grow together, so only the first call of a size allocates.
     struct SeqSlot {
         DevBuf dev;
-        void *host = nullptr;
-        size_t host_bytes = 0;
-        hipEvent_t up = nullptr, done = nullptr;
+        PinnedBuf host;
+        Event up, done;
     } seq[2];
     int seq_slot = 0;
     // RAST scratch (owned by cg_rast.hip)
@@ -256,9 +241,8 @@ struct cg_ctx {
     // pinned host copy followed by one int for the last frame's clipped count
     static constexpr int kRastHostSlots = 2;
     DevBuf rs_argb[kRastHostSlots], rs_depth[kRastHostSlots], rs_shadow[kRastHostSlots], rs_info;
-    hipEvent_t rs_rdone[kRastHostSlots] = {}, rs_cdone[kRastHostSlots] = {};
-    void *rs_host = nullptr;
-    size_t rs_host_bytes = 0;
+    Event rs_rdone[kRastHostSlots], rs_cdone[kRastHostSlots];
+    PinnedBuf rs_host;
     DevBuf sstars, sframe;               // starfield (cg_starfield.hip)
     StarState star;                      // resident stars and frame runs (cg_starfield.hip)
     DevBuf iscratch;                     // JPEG decode (cg_image.hip)
@@ -271,10 +255,11 @@ struct cg_ctx {
     // cg_rast_draw_frames_device: frames overlap on `lanes` (child contexts,
     // each with its own stream and scratch; scene copied device to device)
     static constexpr int kRastLanes = 8;
-    cg_ctx *lanes[kRastLanes] = {};
-    hipEvent_t lane_ev[kRastLanes] = {};
-    hipEvent_t seq_ev[kRastLanes] = {};   // cg_rast_draw_sequence_device: a lane's latest chain step
-    hipEvent_t start_ev = nullptr;
+    // declared after the texture maps above: a lane reads its parent's and is destroyed first
+    std::unique_ptr<cg_ctx> lanes[kRastLanes];
+    Event lane_ev[kRastLanes];
+    Event seq_ev[kRastLanes];   // cg_rast_draw_sequence_device: a lane's latest chain step
+    Event start_ev;
     unsigned scene_gen = 0, lane_gen[kRastLanes] = {};
 };
 

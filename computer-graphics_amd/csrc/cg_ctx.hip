@@ -53,21 +53,6 @@ void ctx_events(cg_ctx *c, hipEvent_t *a, hipEvent_t *b)
     *a = c->ev0;
     *b = c->ev1;
 }
-void rast_release(cg_ctx *c)
-{
-    c->rtris.release(); c->rhdr.release(); c->rspan.release(); c->rpix.release();
-    c->rargb.release(); c->rdepth.release(); c->rshadow.release(); c->rcount.release();
-    c->rrecs.release(); c->rgeo.release(); c->rroom.release(); c->rboxes.release();
-    c->rpc.release(); c->rtl.release(); c->rrnd.release(); c->rjt.release();
-    c->rseq.release(); c->rhdr_rgba.release();
-    for (DevBuf &b : c->rbig) b.release();
-    for (DevBuf &b : c->rbuf) b.release();
-    c->rframe = RastFrame{};
-    c->sstars.release(); c->sframe.release();
-    c->tmarble.release(); c->tnoise.release(); c->twoven.release(); c->twoven_ao.release();
-    c->twoven_op.release(); c->twoven_nrm.release(); c->tgrill.release(); c->tgrill_op.release();
-    c->tgrill_nrm.release(); c->rtexel.release();
-}
 int ctx_rast_route(cg_ctx *c, long long cap, bool colour)
 {
     if (c->rast_route >= 0) return c->rast_route;
@@ -114,8 +99,8 @@ extern "C" int cg_create(int device, cg_ctx **out)
     cg_ctx *c = new (std::nothrow) cg_ctx;
     if (!c) return CG_E_INVALID;
     c->device = device;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) {
+    if (c->stream.ensure(hipStreamNonBlocking) != hipSuccess || c->ev0.ensure(hipEventDefault) != hipSuccess ||
+        c->ev1.ensure(hipEventDefault) != hipSuccess) {
         delete c;
         return CG_E_HIP;
     }
@@ -123,80 +108,33 @@ extern "C" int cg_create(int device, cg_ctx **out)
     return CG_OK;
 }
 
+// Waits for everything the context still has in flight, so that the members free nothing under
+// a running kernel or copy; the lanes do the same in their own destructors.
+cg_ctx::~cg_ctx()
+{
+    (void)hipSetDevice(device);
+    for (const Stream *st : {&stream, &aux, &xfer, &star.xfer})
+        if (*st) (void)hipStreamSynchronize(*st);
+    // on a caller's stream, perhaps: the frames' demand read-backs and the starfield's latest work
+    if (big_ev_live) (void)hipEventSynchronize(big_ev);
+    for (ExtraSlot &x : xs) {
+        if (x.st) (void)hipStreamSynchronize(x.st);
+        if (x.ev_live) (void)hipEventSynchronize(x.ev);
+    }
+    if (hits.ev_live) (void)hipEventSynchronize(hits.ev);
+    if (star.pending) (void)hipEventSynchronize(star.last);
+}
+
 extern "C" void cg_destroy(cg_ctx *c)
 {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    DevBuf *bufs[] = {&c->tris, &c->geo, &c->tc, &c->shade, &c->sph, &c->frame,
-                      &c->probe_a, &c->probe_b, &c->probe_c, &c->probe_d, &c->lights, &c->big,
-                      &c->gstart, &c->gtris, &c->objmask};
-    if (c->big_ev) {
-        (void)hipEventSynchronize(c->big_ev);
-        (void)hipEventDestroy(c->big_ev);
-    }
-    for (DevBuf *b : bufs) b->release();
-    if (c->big_demand) (void)hipHostFree(c->big_demand);
-    for (auto &x : c->xs) {
-        if (x.st) (void)hipStreamSynchronize(x.st);
-        if (x.ev) {
-            (void)hipEventSynchronize(x.ev);
-            (void)hipEventDestroy(x.ev);
-        }
-        if (x.done) (void)hipEventDestroy(x.done);
-        if (x.demand) (void)hipHostFree(x.demand);
-        x.tc.release(); x.big.release(); x.frame.release();
-        if (x.st) (void)hipStreamDestroy(x.st);
-    }
-    if (c->bev_start) (void)hipEventDestroy(c->bev_start);
-    if (c->hits.ev) {
-        (void)hipEventSynchronize(c->hits.ev);
-        (void)hipEventDestroy(c->hits.ev);
-    }
-    if (c->hits.demand) (void)hipHostFree(c->hits.demand);
-    c->hits.tc.release(); c->hits.big.release(); c->hits.planes.release(); c->hits.pick.release();
-    if (c->aux) (void)hipStreamSynchronize(c->aux);
-    for (int k = 0; k < cg_ctx::kRastLanes; ++k) {
-        if (c->lanes[k]) cg_destroy(c->lanes[k]);
-        if (c->lane_ev[k]) (void)hipEventDestroy(c->lane_ev[k]);
-        if (c->seq_ev[k]) (void)hipEventDestroy(c->seq_ev[k]);
-    }
-    if (c->start_ev) (void)hipEventDestroy(c->start_ev);
-    for (int k = 0; k < 2; ++k) {
-        c->ptc[k].release(); c->plat[k].release(); c->pflag[k].release(); c->psup[k].release();
-        c->pumask[k].release(); c->pobj[k].release();
-        if (c->ev_cert[k]) (void)hipEventDestroy(c->ev_cert[k]);
-        if (c->ev_lat[k]) (void)hipEventDestroy(c->ev_lat[k]);
-    }
-    if (c->aux) (void)hipStreamDestroy(c->aux);
-    if (c->xfer) (void)hipStreamSynchronize(c->xfer);
-    for (int k = 0; k < 2; ++k) {
-        c->hslot[k].release();
-        if (c->ev_rdone[k]) (void)hipEventDestroy(c->ev_rdone[k]);
-        if (c->ev_cdone[k]) (void)hipEventDestroy(c->ev_cdone[k]);
-    }
-    if (c->xfer) (void)hipStreamDestroy(c->xfer);
-    c->hdr_rgba.release(); c->hdr_hist.release(); c->hdr_argb.release(); c->hdr_scales.release();
-    c->rs_info.release();
-    for (int k = 0; k < cg_ctx::kRastHostSlots; ++k) {
-        c->rs_argb[k].release(); c->rs_depth[k].release(); c->rs_shadow[k].release();
-        if (c->rs_rdone[k]) (void)hipEventDestroy(c->rs_rdone[k]);
-        if (c->rs_cdone[k]) (void)hipEventDestroy(c->rs_cdone[k]);
-    }
-    if (c->rs_host) (void)hipHostFree(c->rs_host);
-    for (auto &q : c->seq) {
-        q.dev.release();
-        if (q.host) (void)hipHostFree(q.host);
-        if (q.up) (void)hipEventDestroy(q.up);
-        if (q.done) (void)hipEventDestroy(q.done);
-    }
-    rt_grid_release(c->gbuild);
-    rast_release(c);
-    star_release(&c->star);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    if (c) delete c;
+}
+
+extern "C" int cg_debug_live(long long out[4])
+{
+    if (!out) return CG_E_INVALID;
+    for (int k = 0; k < 4; ++k) out[k] = own_live[k].load();
+    return CG_OK;
 }
 
 extern "C" const char *cg_last_error(const cg_ctx *c) { return c ? c->err.c_str() : "no context"; }

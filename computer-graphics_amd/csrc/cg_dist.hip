@@ -55,27 +55,8 @@ namespace {
 
 constexpr int kBandAlign = kLatTileH;   // default band boundaries: whole lattice tile rows
 
-struct Mem {
-    void *p = nullptr;
-    size_t bytes = 0;
-    hipError_t ensure(size_t n)
-    {
-        if (n <= bytes) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-        hipError_t e = hipMalloc(&p, n);
-        if (e == hipSuccess) bytes = n;
-        return e;
-    }
-    ~Mem()
-    {
-        if (p) (void)hipFree(p);
-    }
-};
-
 struct TimedPair {
-    hipEvent_t a = nullptr, b = nullptr;
+    Event a, b;   // timing events
     int frames = 0;
 };
 
@@ -88,17 +69,17 @@ struct cg_dist {
     int nranks = 1, rank = 0;
     ncclComm_t comm = nullptr;        // RCCL transport
     LocalGroup *group = nullptr;      // in-process transport (tests)
-    hipStream_t xs = nullptr;         // transfer stream
+    Stream xs;                        // transfer stream (declared before what runs on it)
     int height = 0;                   // frame height the bands are for
     std::vector<int> row0, rows;      // band of every rank
     int chunk = 4;                    // frames per chunk
-    Mem sbuf[2], rbuf[2];             // send (ranks > 0) / receive (rank 0) slots
-    Mem sall;                         // local transport: a peer's whole call
-    hipEvent_t ev_rend[2] = {}, ev_sent[2] = {}, ev_recv[2] = {}, ev_asm[2] = {}, ev_done = nullptr;
-    std::vector<hipEvent_t> ev_chunk; // local transport: a peer's chunk j rendered
+    DevBuf sbuf[2], rbuf[2];          // send (ranks > 0) / receive (rank 0) slots
+    DevBuf sall;                      // local transport: a peer's whole call
+    Event ev_rend[2], ev_sent[2], ev_recv[2], ev_asm[2], ev_done;
+    std::vector<Event> ev_chunk;      // local transport: a peer's chunk j rendered
     std::vector<TimedPair> t_rend, t_asm;   // timing of the last call (reused event pool)
     size_t n_rend = 0, n_asm = 0;
-    Mem stats;                        // rebalance: gathered per-rank times (device)
+    DevBuf stats;                     // rebalance: gathered per-rank times (device)
     int last_pitch = 0;               // local transport: the peer's window pitch of its last call
     size_t last_frames = 0;
     // Signalled pipeline (when the device supports stream waits on memory):
@@ -106,19 +87,18 @@ struct cg_dist {
     // waits on per-frame completion counts (rt_render_frames' d_done).
     bool signals = false;
     unsigned calls = 0;               // call parity selects the slot below
-    uint32_t *done[2] = {nullptr, nullptr};
-    size_t done_cap[2] = {0, 0};
+    DevBuf done[2];                   // uint32_t per frame, uncached
     std::vector<uint32_t> target[2];
-    hipEvent_t ev_call[2] = {};       // ranks > 0: slot free again (its sends / copies done)
-    hipEvent_t ev_zero[2] = {};       // ranks > 0: the slot's counts zeroed for this call (on st)
-    hipEvent_t ev_start = nullptr;    // rank 0: the caller's stream at the start of the call
+    Event ev_call[2];                 // ranks > 0: slot free again (its sends / copies done)
+    Event ev_zero[2];                 // ranks > 0: the slot's counts zeroed for this call (on st)
+    Event ev_start;                   // rank 0: the caller's stream at the start of the call
     int cur = 0;                      // slot of the last call
     // bounded waits
     int timeout_ms = 60000;           // deadline of every host wait
     bool aborted = false;             // communicator aborted after an error / timeout
     bool leaked = false;              // the abort did not finish in time: device memory kept (see abort_comm)
     hipStream_t last_st = nullptr;    // render stream of the last call
-    hipEvent_t ev_wait[2] = {};       // cg_dist_wait: render stream, transfer stream
+    Event ev_wait[2];                 // cg_dist_wait: render stream, transfer stream
 };
 
 namespace {
@@ -245,7 +225,7 @@ int recv_group(cg_dist *d, uint8_t *buf, const size_t *bytes, int n)
 // last progress -- the start of the wait, or the latest event seen complete --
 // so a healthy rank that queued more than timeout_ms of work in several steps
 // is not aborted; a wait on ONE event still covers everything queued before it.
-int wait_events(cg_dist *d, const hipEvent_t *ev, int n, const char *what)
+int wait_events(cg_dist *d, const Event *ev, int n, const char *what)
 {
     const auto t0 = Clock::now();
     auto end = t0 + std::chrono::milliseconds(d->timeout_ms);
@@ -287,7 +267,7 @@ int drain(cg_dist *d, hipStream_t st, const char *what)
     if (!d->ev_done) return CG_OK;   // nothing enqueued yet
     DT(d, hipSetDevice(ctx_device(d->ctx)), "hipSetDevice");
     for (int k = 0; k < 2; ++k)
-        if (!d->ev_wait[k]) DT(d, hipEventCreateWithFlags(&d->ev_wait[k], hipEventDisableTiming), "event");
+        DT(d, d->ev_wait[k].ensure(), "event");
     if (!st) st = d->last_st ? d->last_st : ctx_stream(d->ctx);
     DT(d, hipEventRecord(d->ev_wait[0], st), "event");
     DT(d, hipEventRecord(d->ev_wait[1], d->xs), "event");
@@ -347,24 +327,24 @@ int ensure_events(cg_dist *d)
 {
     if (d->ev_done) return CG_OK;
     DT(d, hipSetDevice(ctx_device(d->ctx)), "hipSetDevice");
-    DT(d, hipStreamCreateWithFlags(&d->xs, hipStreamNonBlocking), "transfer stream");
+    DT(d, d->xs.ensure(hipStreamNonBlocking), "transfer stream");
     for (int k = 0; k < 2; ++k) {
-        DT(d, hipEventCreateWithFlags(&d->ev_rend[k], hipEventDisableTiming), "event");
-        DT(d, hipEventCreateWithFlags(&d->ev_sent[k], hipEventDisableTiming), "event");
-        DT(d, hipEventCreateWithFlags(&d->ev_recv[k], hipEventDisableTiming), "event");
-        DT(d, hipEventCreateWithFlags(&d->ev_asm[k], hipEventDisableTiming), "event");
+        DT(d, d->ev_rend[k].ensure(), "event");
+        DT(d, d->ev_sent[k].ensure(), "event");
+        DT(d, d->ev_recv[k].ensure(), "event");
+        DT(d, d->ev_asm[k].ensure(), "event");
         // recorded once so the first waits on them are satisfied
         DT(d, hipEventRecord(d->ev_sent[k], d->xs), "event");
         DT(d, hipEventRecord(d->ev_asm[k], d->xs), "event");
     }
-    DT(d, hipEventCreateWithFlags(&d->ev_done, hipEventDisableTiming), "event");
+    DT(d, d->ev_done.ensure(), "event");
     for (int k = 0; k < 2; ++k) {
-        DT(d, hipEventCreateWithFlags(&d->ev_call[k], hipEventDisableTiming), "event");
+        DT(d, d->ev_call[k].ensure(), "event");
         DT(d, hipEventRecord(d->ev_call[k], d->xs), "event");
-        DT(d, hipEventCreateWithFlags(&d->ev_zero[k], hipEventDisableTiming), "event");
+        DT(d, d->ev_zero[k].ensure(), "event");
         DT(d, hipEventRecord(d->ev_zero[k], d->xs), "event");
     }
-    DT(d, hipEventCreateWithFlags(&d->ev_start, hipEventDisableTiming), "event");
+    DT(d, d->ev_start.ensure(), "event");
     int wait_value = 0;
     d->signals = hipDeviceGetAttribute(&wait_value, hipDeviceAttributeCanUseStreamWaitValue, ctx_device(d->ctx)) ==
                      hipSuccess && wait_value != 0;
@@ -376,9 +356,9 @@ int timed(cg_dist *d, std::vector<TimedPair> &pool, size_t &n, TimedPair *&out)
 {
     if (n == pool.size()) {
         TimedPair t;
-        DT(d, hipEventCreate(&t.a), "event");
-        DT(d, hipEventCreate(&t.b), "event");
-        pool.push_back(t);
+        DT(d, t.a.ensure(hipEventDefault), "event");
+        DT(d, t.b.ensure(hipEventDefault), "event");
+        pool.push_back(std::move(t));
     }
     out = &pool[n++];
     return CG_OK;
@@ -529,31 +509,14 @@ extern "C" void cg_dist_destroy(cg_dist *d)
         }
     }
     if (d->comm) abort_comm(d);
-    for (hipEvent_t e : d->ev_wait)
-        if (e) (void)hipEventDestroy(e);
-    for (int k = 0; k < 2; ++k)
-        for (hipEvent_t e : {d->ev_rend[k], d->ev_sent[k], d->ev_recv[k], d->ev_asm[k]})
-            if (e) (void)hipEventDestroy(e);
-    if (d->ev_done) (void)hipEventDestroy(d->ev_done);
-    if (d->ev_start) (void)hipEventDestroy(d->ev_start);
-    for (int k = 0; k < 2; ++k) {
-        if (d->ev_call[k]) (void)hipEventDestroy(d->ev_call[k]);
-        if (d->ev_zero[k]) (void)hipEventDestroy(d->ev_zero[k]);
-        if (d->done[k] && !d->leaked) (void)hipFree(d->done[k]);
-    }
-    for (hipEvent_t e : d->ev_chunk) (void)hipEventDestroy(e);
-    for (auto *pool : {&d->t_rend, &d->t_asm})
-        for (TimedPair &t : *pool) {
-            (void)hipEventDestroy(t.a);
-            (void)hipEventDestroy(t.b);
-        }
     if (d->leaked) {
         // an abort that did not finish (abort_comm): keep every device buffer and
         // the transfer stream alive for the process's lifetime
-        for (Mem *m : {&d->sbuf[0], &d->sbuf[1], &d->rbuf[0], &d->rbuf[1], &d->sall, &d->stats}) m->p = nullptr;
-        d->xs = nullptr;
+        for (DevBuf *m : {&d->sbuf[0], &d->sbuf[1], &d->rbuf[0], &d->rbuf[1], &d->sall, &d->stats, &d->done[0],
+                          &d->done[1]})
+            m->leak();
+        d->xs.leak();
     }
-    if (d->xs) (void)hipStreamDestroy(d->xs);
     if (d->group) {   // the last member frees the group
         auto &m = d->group->members;
         m.erase(std::remove(m.begin(), m.end(), d), m.end());
@@ -738,22 +701,18 @@ static int render_signalled(cg_dist *d, const cg_light *lights, int n_lights, co
         hipEvent_t prev = d->group ? d->group->members[0]->ev_call[s] : d->ev_call[s];
         if (prev) DT(d, hipStreamWaitEvent(st, prev, 0), "wait");
         const size_t bytes = (size_t)n_frames * nr * row_bytes;
-        Mem &out = d->sbuf[s];   // the whole call's band (rank 0 pulls from it in the local transport)
+        DevBuf &out = d->sbuf[s];   // the whole call's band (rank 0 pulls from it in the local transport)
         DT(d, out.ensure(std::max<size_t>(bytes, 1)), "alloc send buffer");
-        if (d->done_cap[s] < (size_t)n_frames) {
+        if (d->done[s].bytes < (size_t)n_frames * sizeof(uint32_t)) {
             // bounded: st may wait on the slot's previous sends
             rc = drain(d, st, "grow signals");
             if (rc) return rc;
-            if (d->done[s]) DT(d, hipFree(d->done[s]), "free signals");
-            d->done[s] = nullptr;
             // uncached fine-grained device memory: the kernels' atomics land in
             // memory, where the command processor's waits poll them
-            DT(d, hipExtMallocWithFlags((void **)&d->done[s], (size_t)n_frames * sizeof(uint32_t),
-                                        hipDeviceMallocUncached), "alloc signals");
-            d->done_cap[s] = n_frames;
+            DT(d, d->done[s].ensure_uncached((size_t)n_frames * sizeof(uint32_t)), "alloc signals");
         }
         d->target[s].assign(n_frames, 0u);
-        DT(d, hipMemsetAsync(d->done[s], 0, (size_t)n_frames * sizeof(uint32_t), st), "zero signals");
+        DT(d, hipMemsetAsync(d->done[s].p, 0, (size_t)n_frames * sizeof(uint32_t), st), "zero signals");
         // The slot's counts still hold the totals of the call two calls ago,
         // and the targets repeat for the same frame size: every wait on them
         // (this rank's transfer stream, or rank 0's in the local transport)
@@ -768,7 +727,7 @@ static int render_signalled(cg_dist *d, const cg_light *lights, int n_lights, co
             for (const auto &ch : chunk_plan(n_frames, C)) gs.push_back(ch.first);
             gs.push_back(n_frames);
             rc = render_band(d, lights, n_lights, cams, n_frames, r0, nr, c0, cols, out.p, (size_t)nr * pitch,
-                             CG_PIX_RGB24, st, d->done[s], d->target[s].data(), &gs);
+                             CG_PIX_RGB24, st, (uint32_t *)d->done[s].p, d->target[s].data(), &gs);
             if (rc) return rc;
         } else {
             for (int f = 0; f < n_frames; ++f) d->target[s][f] = 0u;   // nothing to wait for
@@ -780,7 +739,7 @@ static int render_signalled(cg_dist *d, const cg_light *lights, int n_lights, co
             const int f0 = ch.first, nf = ch.second;
             for (int f = f0; f < f0 + nf; ++f)
                 if (d->target[s][f])
-                    DT(d, hipStreamWaitValue32(d->xs, d->done[s] + f, d->target[s][f], hipStreamWaitValueGte,
+                    DT(d, hipStreamWaitValue32(d->xs, (uint32_t *)d->done[s].p + f, d->target[s][f], hipStreamWaitValueGte,
                                                0xffffffffu), "wait frame");
             const size_t cb = (size_t)nf * nr * row_bytes;
             if (cb) DN(d, ncclSend((uint8_t *)out.p + (size_t)f0 * nr * row_bytes, cb, ncclUint8, 0, d->comm, d->xs),
@@ -825,7 +784,7 @@ static int render_signalled(cg_dist *d, const cg_light *lights, int n_lights, co
                     if (f0 == 0) DT(d, hipStreamWaitEvent(d->xs, m->ev_zero[s], 0), "wait");
                     for (int f = f0; f < f0 + nf; ++f)
                         if (m->target[s][f])
-                            DT(d, hipStreamWaitValue32(d->xs, m->done[s] + f, m->target[s][f],
+                            DT(d, hipStreamWaitValue32(d->xs, (uint32_t *)m->done[s].p + f, m->target[s][f],
                                                        hipStreamWaitValueGte, 0xffffffffu), "wait frame");
                     if (bytes)
                         DT(d, hipMemcpyAsync(cb + off, (const uint8_t *)m->sbuf[s].p + (size_t)f0 * d->rows[p] * row_bytes,
@@ -903,9 +862,9 @@ extern "C" int cg_rt_render_frames_dist(cg_dist *d, const cg_light *lights, int 
         const int chunks = (n_frames + C - 1) / C;
         DT(d, d->sall.ensure(std::max<size_t>(1, (size_t)n_frames * nr * row_bytes)), "alloc band");
         while ((int)d->ev_chunk.size() < chunks) {
-            hipEvent_t e;
-            DT(d, hipEventCreateWithFlags(&e, hipEventDisableTiming), "event");
-            d->ev_chunk.push_back(e);
+            Event e;
+            DT(d, e.ensure(), "event");
+            d->ev_chunk.push_back(std::move(e));
         }
         for (int j = 0; j < chunks; ++j) {
             const int f0 = j * C, nf = std::min(C, n_frames - f0);

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "cg_internal.h"
+#include "cg_own.h"
 
 #define CG_TRY(ctx, call, what)                       \
     do {                                              \
@@ -20,6 +21,24 @@ namespace cg {
 
 struct SceneBounds;   // cg_rt_grid.h; the rest: cg_rast_dev.h
 struct RastArgs; struct RastHdr; struct RastSeq; struct RastTexMaps; struct RastLast; struct RastFrame; struct RowRec;
+
+// The context's starfield state, used by cg_starfield.hip.  x and y never change; z alternates
+// between two buffers, because a launch's blocks replay from the state before it while its
+// last block stores the state after it.
+struct StarState {
+    int n = -1;                  // resident stars; -1: none set
+    int cap = 0;                 // stars the buffers hold
+    int cur = 0;                 // z[cur] is the resident state once everything enqueued has run
+    // cg_starfield_run (host output): chunks render into two device slots and download on
+    // `xfer` while the next chunk renders
+    Stream xfer;
+    DevBuf xy, z[2];             // float2 and float per star
+    Event last;                  // after the latest enqueued starfield work
+    bool pending = false;        // `last` has been recorded
+    Event rdone[2], cdone[2];
+    DevBuf slot[2];              // uint32_t pixels
+    size_t slot_px = 0;
+};
 
 // ---- the context (cg_ctx.hip) ----
 // ctx_buf slots: the context's grow-only scratch buffers by name.  Three ranges: the named
@@ -58,7 +77,6 @@ RastFrame *ctx_rast_frame(cg_ctx *c);
 bool ctx_rast_want_owner(cg_ctx *c);
 // the device texture maps and which textures are renderable (bit k: texture k)
 int rast_tex_maps(cg_ctx *c, RastTexMaps *m);
-void rast_release(cg_ctx *ctx);
 
 // ---- raytracer kernels' launches and host helpers ----
 // cg_rt.hip

@@ -238,26 +238,6 @@ constexpr int kStarBlockFrames = 8;
 struct StarSteps {
     double d[kStarLaunchFrames];
 };
-// The context's starfield state, owned by cg_starfield.hip (star_release frees it).  x and y
-// never change; z alternates between two buffers, because a launch's blocks replay from the
-// state before it while its last block stores the state after it.
-struct StarState {
-    int n = -1;                  // resident stars; -1: none set
-    int cap = 0;                 // stars the buffers hold
-    int cur = 0;                 // z[cur] is the resident state once everything enqueued has run
-    float2 *xy = nullptr;
-    float *z[2] = {nullptr, nullptr};
-    hipEvent_t last = nullptr;   // after the latest enqueued starfield work
-    bool pending = false;        // `last` has been recorded
-    // cg_starfield_run (host output): chunks render into two device slots and download on
-    // `xfer` while the next chunk renders
-    hipStream_t xfer = nullptr;
-    hipEvent_t rdone[2] = {nullptr, nullptr}, cdone[2] = {nullptr, nullptr};
-    uint32_t *slot[2] = {nullptr, nullptr};
-    size_t slot_px = 0;
-};
-void star_release(StarState *s);
-
 // ---- live kernel timing (cg_ktime.hip, cg_kernel_timing) ---------------
 enum KtId {
     KT_RT_PREPARE, KT_RT_TILE_CERT, KT_RT_LATTICE_UNITS, KT_RT_LATTICE, KT_RT_LATTICE_LIGHTS, KT_RT_PIXEL,

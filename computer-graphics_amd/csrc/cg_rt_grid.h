@@ -10,6 +10,7 @@
 #include <functional>
 
 #include "cg_internal.h"
+#include "cg_own.h"
 
 namespace cg {
 
@@ -120,9 +121,8 @@ struct SceneBounds {
 
 // Device builder (cg_rt_grid.hip).  Its scratch is grow-only and lives with the context.
 struct GridBuild {
-    void *mem[3] = {nullptr, nullptr, nullptr};   // bounds partials + totals; per-triangle and per-cell; per-candidate
-    size_t bytes[3] = {0, 0, 0};
-    hipEvent_t ev[10] = {};                       // events 2p, 2p + 1 bracket phase p (created on first use)
+    DevBuf mem[3];                                // bounds partials + totals; per-triangle and per-cell; per-candidate
+    Event ev[10];                                 // events 2p, 2p + 1 bracket phase p (created on first use)
     unsigned phase_live = 0;                      // bit p: the latest build recorded phase p
     uint64_t cells = 0, entries = 0, cands = 0;   // of the latest build (cands 0: host build)
 };
@@ -140,6 +140,5 @@ hipError_t rt_grid_build_device(GridBuild &gb, const cg_tri *d_tris, int n, cons
 size_t rt_grid_scratch_bytes(const GridBuild &gb);
 // Device time of the latest build's phases in ms (-1: not recorded).  Waits for the build.
 hipError_t rt_grid_phase_ms(GridBuild &gb, double out[kGridPhases]);
-void rt_grid_release(GridBuild &gb);
 
 }  // namespace cg

@@ -387,17 +387,6 @@ __global__ __launch_bounds__(kGridThreads) void rt_grid_sort_long_kernel(const i
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-hipError_t grow(GridBuild &gb, int k, size_t need)
-{
-    if (need <= gb.bytes[k]) return hipSuccess;
-    if (gb.mem[k]) (void)hipFree(gb.mem[k]);
-    gb.mem[k] = nullptr;
-    gb.bytes[k] = 0;
-    const hipError_t e = hipMalloc(&gb.mem[k], need);
-    if (e == hipSuccess) gb.bytes[k] = need;
-    return e;
-}
-
 }  // namespace
 
 bool rt_grid_dims(const float vmin[3], const float vmax[3], int n, GridDims &d)
@@ -429,11 +418,10 @@ bool rt_grid_dims(const float vmin[3], const float vmax[3], int n, GridDims &d)
 
 static hipError_t grid_events(GridBuild &gb)
 {
-    for (hipEvent_t &e : gb.ev)
-        if (!e) {
-            const hipError_t r = hipEventCreate(&e);
-            if (r != hipSuccess) return r;
-        }
+    for (Event &e : gb.ev) {
+        const hipError_t r = e.ensure(hipEventDefault);   // timing events
+        if (r != hipSuccess) return r;
+    }
     return hipSuccess;
 }
 
@@ -444,11 +432,11 @@ static hipError_t grid_events(GridBuild &gb)
     } while (0)
 
 // mem[0]: bounds partials [kBoundsBlocks][8], the seven results, four 64-bit totals
-static float *small_part(GridBuild &gb) { return (float *)gb.mem[0]; }
-static float *small_out(GridBuild &gb) { return (float *)gb.mem[0] + kBoundsBlocks * 8; }
+static float *small_part(GridBuild &gb) { return (float *)gb.mem[0].p; }
+static float *small_out(GridBuild &gb) { return (float *)gb.mem[0].p + kBoundsBlocks * 8; }
 static unsigned long long *small_totals(GridBuild &gb)
 {
-    return (unsigned long long *)((char *)gb.mem[0] + kBoundsBlocks * 8 * 4 + 64);
+    return (unsigned long long *)((char *)gb.mem[0].p + kBoundsBlocks * 8 * 4 + 64);
 }
 
 hipError_t rt_grid_bounds_device(GridBuild &gb, const cg_tri *d_tris, int n, SceneBounds &out, hipStream_t st)
@@ -458,7 +446,7 @@ hipError_t rt_grid_bounds_device(GridBuild &gb, const cg_tri *d_tris, int n, Sce
     gb.cells = gb.entries = gb.cands = 0;
     if (n <= 0) return hipSuccess;
     GRID_TRY(grid_events(gb));
-    GRID_TRY(grow(gb, 0, (size_t)kBoundsBlocks * 8 * 4 + 64 + 64));
+    GRID_TRY(gb.mem[0].ensure((size_t)kBoundsBlocks * 8 * 4 + 64 + 64));
     const int nb = std::min(kBoundsBlocks, (n + kGridThreads - 1) / kGridThreads);
     GRID_TRY(hipEventRecord(gb.ev[0], st));
     hipLaunchKernelGGL(rt_grid_bounds_kernel, dim3(nb), dim3(kGridThreads), 0, st, d_tris, n, small_part(gb));
@@ -485,7 +473,7 @@ hipError_t rt_grid_build_device(GridBuild &gb, const cg_tri *d_tris, int n, cons
     built = false;
     if (n <= 0) return hipSuccess;
     GRID_TRY(grid_events(gb));
-    GRID_TRY(grow(gb, 0, (size_t)kBoundsBlocks * 8 * 4 + 64 + 64));
+    GRID_TRY(gb.mem[0].ensure((size_t)kBoundsBlocks * 8 * 4 + 64 + 64));
     const uint64_t cells = (uint64_t)d.res[0] * d.res[1] * d.res[2];
     const uint64_t N = (uint64_t)n;
     const int nbT = (int)((N + kScanTile - 1) / kScanTile), nbC = (int)((cells + kScanTile - 1) / kScanTile);
@@ -497,8 +485,8 @@ hipError_t rt_grid_build_device(GridBuild &gb, const cg_tri *d_tris, int n, cons
     const size_t o_bsT = off; off = align256(off + (size_t)nbT * 8);
     const size_t o_bsC = off; off = align256(off + (size_t)nbC * 8);
     const size_t o_cnt = off; off = align256(off + cells * 4);
-    GRID_TRY(grow(gb, 1, off));
-    char *m1 = (char *)gb.mem[1];
+    GRID_TRY(gb.mem[1].ensure(off));
+    char *m1 = (char *)gb.mem[1].p;
     uint64_t *rng = (uint64_t *)(m1 + o_rng), *coff = (uint64_t *)(m1 + o_coff);
     uint64_t *bsT = (uint64_t *)(m1 + o_bsT), *bsC = (uint64_t *)(m1 + o_bsC);
     int *cnt = (int *)(m1 + o_cnt);
@@ -530,9 +518,9 @@ hipError_t rt_grid_build_device(GridBuild &gb, const cg_tri *d_tris, int n, cons
     const uint64_t nmask = (B + 63) / 64;
     const uint64_t list_cap = std::min<uint64_t>(cells, B / (kSortSmall + 1) + 1);
     const size_t o_list = align256(std::max<uint64_t>(nmask, 1) * 8);
-    GRID_TRY(grow(gb, 2, o_list + align256(list_cap * 4)));
-    unsigned long long *mask = (unsigned long long *)gb.mem[2];
-    int *list = (int *)((char *)gb.mem[2] + o_list);
+    GRID_TRY(gb.mem[2].ensure(o_list + align256(list_cap * 4)));
+    unsigned long long *mask = (unsigned long long *)gb.mem[2].p;
+    int *list = (int *)((char *)gb.mem[2].p + o_list);
     const unsigned cblocks = (unsigned)((B + kGridThreads - 1) / kGridThreads);
     GRID_TRY(hipEventRecord(gb.ev[4], st));
     GRID_TRY(hipMemsetAsync(cnt, 0, cells * 4, st));
@@ -578,7 +566,7 @@ hipError_t rt_grid_build_device(GridBuild &gb, const cg_tri *d_tris, int n, cons
     return hipSuccess;
 }
 
-size_t rt_grid_scratch_bytes(const GridBuild &gb) { return gb.bytes[0] + gb.bytes[1] + gb.bytes[2]; }
+size_t rt_grid_scratch_bytes(const GridBuild &gb) { return gb.mem[0].bytes + gb.mem[1].bytes + gb.mem[2].bytes; }
 
 hipError_t rt_grid_phase_ms(GridBuild &gb, double out[kGridPhases])
 {
@@ -591,21 +579,6 @@ hipError_t rt_grid_phase_ms(GridBuild &gb, double out[kGridPhases])
         out[p] = ms;
     }
     return hipSuccess;
-}
-
-void rt_grid_release(GridBuild &gb)
-{
-    for (int k = 0; k < 3; ++k) {
-        if (gb.mem[k]) (void)hipFree(gb.mem[k]);
-        gb.mem[k] = nullptr;
-        gb.bytes[k] = 0;
-    }
-    for (hipEvent_t &e : gb.ev)
-        if (e) {
-            (void)hipEventDestroy(e);
-            e = nullptr;
-        }
-    gb.phase_live = 0;
 }
 
 }  // namespace cg

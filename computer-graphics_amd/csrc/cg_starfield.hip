@@ -150,22 +150,6 @@ __global__ __launch_bounds__(256) void star_advance_kernel(float *__restrict__ z
     z[i] = v;
 }
 
-void star_release(StarState *s)
-{
-    if (s->pending) (void)hipEventSynchronize(s->last);
-    if (s->xfer) (void)hipStreamSynchronize(s->xfer);
-    if (s->xy) (void)hipFree(s->xy);
-    for (int k = 0; k < 2; ++k) {
-        if (s->z[k]) (void)hipFree(s->z[k]);
-        if (s->slot[k]) (void)hipFree(s->slot[k]);
-        if (s->rdone[k]) (void)hipEventDestroy(s->rdone[k]);
-        if (s->cdone[k]) (void)hipEventDestroy(s->cdone[k]);
-    }
-    if (s->last) (void)hipEventDestroy(s->last);
-    if (s->xfer) (void)hipStreamDestroy(s->xfer);
-    *s = StarState{};
-}
-
 }  // namespace cg
 
 #define STAR_TRY(ctx, call, what)                                \
@@ -211,8 +195,8 @@ static int star_enqueue(cg_ctx *c, StarState *S, const float *dts, int n_updates
             const int nf = std::min(kStarLaunchFrames, n_frames - F0), nu = std::min(nf, n_updates - F0);
             star_steps(steps, dts ? dts + F0 : nullptr, nu);
             const dim3 grid((unsigned)((n + 255) / 256), (unsigned)((nf + kStarBlockFrames - 1) / kStarBlockFrames));
-            hipLaunchKernelGGL(star_run_kernel, grid, dim3(256), 0, st, (const float2 *)S->xy,
-                               (const float *)S->z[S->cur], S->z[S->cur ^ 1], n, nf, nu, W, H,
+            hipLaunchKernelGGL(star_run_kernel, grid, dim3(256), 0, st, (const float2 *)S->xy.p,
+                               (const float *)S->z[S->cur].p, (float *)S->z[S->cur ^ 1].p, n, nf, nu, W, H,
                                d_argb + (size_t)F0 * stride, stride, steps);
             S->cur ^= 1;
         }
@@ -220,8 +204,8 @@ static int star_enqueue(cg_ctx *c, StarState *S, const float *dts, int n_updates
         for (int U0 = 0; U0 < n_updates; U0 += kStarLaunchFrames) {
             const int nu = std::min(kStarLaunchFrames, n_updates - U0);
             star_steps(steps, dts + U0, nu);
-            hipLaunchKernelGGL(star_advance_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S->z[S->cur], n,
-                               nu, steps);
+            hipLaunchKernelGGL(star_advance_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                               (float *)S->z[S->cur].p, n, nu, steps);
         }
     }
     STAR_TRY(c, hipGetLastError(), "starfield launch");
@@ -244,19 +228,17 @@ extern "C" int cg_starfield_set(cg_ctx *c, const float *stars, int n)
     STAR_TRY(c, hipSetDevice(ctx_device(c)), "hipSetDevice");
     StarState *S = ctx_star(c);
     if (S->pending) STAR_TRY(c, hipEventSynchronize(S->last), "starfield wait");   // earlier runs read the old set
-    if (!S->last) STAR_TRY(c, hipEventCreateWithFlags(&S->last, hipEventDisableTiming), "starfield event");
-    if (n > S->cap || !S->xy) {
+    STAR_TRY(c, S->last.ensure(), "starfield event");
+    if (n > S->cap || !S->xy.p) {
         const int cap = std::max(n, 1);
-        if (S->xy) (void)hipFree(S->xy);
-        for (int k = 0; k < 2; ++k)
-            if (S->z[k]) (void)hipFree(S->z[k]);
-        S->xy = nullptr;
-        S->z[0] = S->z[1] = nullptr;
+        S->xy.release();
+        S->z[0].release();
+        S->z[1].release();
         S->cap = 0;
         S->n = -1;
-        STAR_TRY(c, hipMalloc((void **)&S->xy, (size_t)cap * sizeof(float2)), "alloc stars");
-        STAR_TRY(c, hipMalloc((void **)&S->z[0], (size_t)cap * sizeof(float)), "alloc stars");
-        STAR_TRY(c, hipMalloc((void **)&S->z[1], (size_t)cap * sizeof(float)), "alloc stars");
+        STAR_TRY(c, S->xy.ensure((size_t)cap * sizeof(float2)), "alloc stars");
+        STAR_TRY(c, S->z[0].ensure((size_t)cap * sizeof(float)), "alloc stars");
+        STAR_TRY(c, S->z[1].ensure((size_t)cap * sizeof(float)), "alloc stars");
         S->cap = cap;
     }
     if (n) {
@@ -267,8 +249,8 @@ extern "C" int cg_starfield_set(cg_ctx *c, const float *stars, int n)
             z[i] = stars[3 * (size_t)i + 2];
         }
         hipStream_t st = ctx_stream(c);
-        STAR_TRY(c, hipMemcpyAsync(S->xy, xy.data(), xy.size() * sizeof(float), hipMemcpyHostToDevice, st), "upload stars");
-        STAR_TRY(c, hipMemcpyAsync(S->z[0], z.data(), z.size() * sizeof(float), hipMemcpyHostToDevice, st), "upload stars");
+        STAR_TRY(c, hipMemcpyAsync(S->xy.p, xy.data(), xy.size() * sizeof(float), hipMemcpyHostToDevice, st), "upload stars");
+        STAR_TRY(c, hipMemcpyAsync(S->z[0].p, z.data(), z.size() * sizeof(float), hipMemcpyHostToDevice, st), "upload stars");
         STAR_TRY(c, hipStreamSynchronize(st), "upload stars");
     }
     S->cur = 0;
@@ -289,8 +271,8 @@ extern "C" int cg_starfield_get(cg_ctx *c, float *stars, int cap)
     if (S->pending) STAR_TRY(c, hipEventSynchronize(S->last), "starfield wait");
     std::vector<float> xy(2 * (size_t)n), z((size_t)n);
     hipStream_t st = ctx_stream(c);
-    STAR_TRY(c, hipMemcpyAsync(xy.data(), S->xy, xy.size() * sizeof(float), hipMemcpyDeviceToHost, st), "download stars");
-    STAR_TRY(c, hipMemcpyAsync(z.data(), S->z[S->cur], z.size() * sizeof(float), hipMemcpyDeviceToHost, st),
+    STAR_TRY(c, hipMemcpyAsync(xy.data(), S->xy.p, xy.size() * sizeof(float), hipMemcpyDeviceToHost, st), "download stars");
+    STAR_TRY(c, hipMemcpyAsync(z.data(), S->z[S->cur].p, z.size() * sizeof(float), hipMemcpyDeviceToHost, st),
              "download stars");
     STAR_TRY(c, hipStreamSynchronize(st), "download stars");
     for (int i = 0; i < n; ++i) {
@@ -342,12 +324,10 @@ extern "C" int cg_starfield_run(cg_ctx *c, const float *dts, int n_updates, int 
     STAR_TRY(c, hipSetDevice(ctx_device(c)), "hipSetDevice");
     const int ch = std::min(chunk ? std::min(chunk, 64) : 8, n_frames);
     hipStream_t st = ctx_stream(c);
-    if (!S->xfer) {
-        STAR_TRY(c, hipStreamCreateWithFlags(&S->xfer, hipStreamNonBlocking), "copy stream");
-        for (int k = 0; k < 2; ++k) {
-            STAR_TRY(c, hipEventCreateWithFlags(&S->rdone[k], hipEventDisableTiming), "copy event");
-            STAR_TRY(c, hipEventCreateWithFlags(&S->cdone[k], hipEventDisableTiming), "copy event");
-        }
+    STAR_TRY(c, S->xfer.ensure(hipStreamNonBlocking), "copy stream");
+    for (int k = 0; k < 2; ++k) {
+        STAR_TRY(c, S->rdone[k].ensure(), "copy event");
+        STAR_TRY(c, S->cdone[k].ensure(), "copy event");
     }
     // every return below leaves nothing of this call running
     struct Drain {
@@ -361,13 +341,9 @@ extern "C" int cg_starfield_run(cg_ctx *c, const float *dts, int n_updates, int 
     if (S->slot_px < (size_t)ch * px) {
         STAR_TRY(c, hipStreamSynchronize(S->xfer), "copy stream");
         STAR_TRY(c, hipStreamSynchronize(st), "starfield stream");
-        for (int k = 0; k < 2; ++k) {
-            if (S->slot[k]) (void)hipFree(S->slot[k]);
-            S->slot[k] = nullptr;
-        }
+        for (DevBuf &b : S->slot) b.release();
         S->slot_px = 0;
-        for (int k = 0; k < 2; ++k)
-            STAR_TRY(c, hipMalloc((void **)&S->slot[k], (size_t)ch * px * sizeof(uint32_t)), "alloc frame slots");
+        for (DevBuf &b : S->slot) STAR_TRY(c, b.ensure((size_t)ch * px * sizeof(uint32_t)), "alloc frame slots");
         S->slot_px = (size_t)ch * px;
     }
     const int nchunks = (n_frames + ch - 1) / ch;
@@ -375,11 +351,11 @@ extern "C" int cg_starfield_run(cg_ctx *c, const float *dts, int n_updates, int 
         const int s = j & 1, f0 = j * ch, nf = std::min(ch, n_frames - f0);
         STAR_TRY(c, hipStreamWaitEvent(S->xfer, S->rdone[s], 0), "copy wait");
         if (stride == px) {
-            STAR_TRY(c, hipMemcpyAsync(argb + (size_t)f0 * stride, S->slot[s], (size_t)nf * px * sizeof(uint32_t),
+            STAR_TRY(c, hipMemcpyAsync(argb + (size_t)f0 * stride, S->slot[s].p, (size_t)nf * px * sizeof(uint32_t),
                                        hipMemcpyDeviceToHost, S->xfer), "download frames");
         } else {
             for (int f = 0; f < nf; ++f)
-                STAR_TRY(c, hipMemcpyAsync(argb + (size_t)(f0 + f) * stride, S->slot[s] + (size_t)f * px,
+                STAR_TRY(c, hipMemcpyAsync(argb + (size_t)(f0 + f) * stride, (uint32_t *)S->slot[s].p + (size_t)f * px,
                                            px * sizeof(uint32_t), hipMemcpyDeviceToHost, S->xfer), "download frames");
         }
         STAR_TRY(c, hipEventRecord(S->cdone[s], S->xfer), "copy event");
@@ -391,7 +367,8 @@ extern "C" int cg_starfield_run(cg_ctx *c, const float *dts, int n_updates, int 
     for (int j = 0; j < nchunks; ++j) {
         const int s = j & 1, f0 = j * ch, nf = std::min(ch, n_frames - f0);
         if (j >= 2) STAR_TRY(c, hipStreamWaitEvent(st, S->cdone[s], 0), "slot wait");   // chunk j - 2 downloaded
-        int rc = star_enqueue(c, S, dts ? dts + f0 : nullptr, std::min(nf, n_updates - f0), nf, width, height, S->slot[s],
+        int rc = star_enqueue(c, S, dts ? dts + f0 : nullptr, std::min(nf, n_updates - f0), nf, width, height,
+                              (uint32_t *)S->slot[s].p,
                               px, st);
         if (rc) return rc;
         STAR_TRY(c, hipEventRecord(S->rdone[s], st), "render event");

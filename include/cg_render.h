@@ -127,6 +127,10 @@ void cg_destroy(cg_ctx *ctx);
 const char *cg_last_error(const cg_ctx *ctx);
 /* Number of visible HIP devices (0 without a GPU); never fails loudly. */
 int  cg_device_count(void);
+/* Test hook: what the process's contexts and cg_dist handles hold right now -- out[0] device
+ * allocations, out[1] pinned host allocations, out[2] events, out[3] streams.  A destroyed
+ * context or handle leaves none behind. */
+int  cg_debug_live(long long out[4]);
 
 /* ---- raytracer -------------------------------------------------------- */
 /* LoadTestModel (raytracer/Source/TestModelH.h:121-279): 28 triangles +
