@@ -79,6 +79,17 @@ def hdr_params(permille=990, target=1.0, scale_min=2.0 ** -16, scale_max=2.0 ** 
     return HdrExposureParams(permille, target, scale_min, scale_max, rate)
 
 
+BLOOM_MAX_LEVELS, BLOOM_RULE_RT, BLOOM_RULE_RAST = 6, 0, 1   # cg_render.h CG_BLOOM_*
+
+
+class HdrBloomParams(C.Structure):     # cg_hdr_bloom_params, 16 B
+    _fields_ = [("levels", C.c_int), ("threshold", C.c_float), ("cap", C.c_float), ("intensity", C.c_float)]
+
+
+def hdr_bloom_params(levels=4, threshold=1.0, cap=64.0, intensity=0.25):
+    return HdrBloomParams(levels, threshold, cap, intensity)
+
+
 class RTri(C.Structure):       # rasteriser Triangle, 84 B
     _fields_ = [("v0", Vec4), ("v1", Vec4), ("v2", Vec4), ("normal", Vec4), ("color", Vec3),
                 ("texture", C.c_int), ("index", C.c_int)]
@@ -208,6 +219,21 @@ _SIGS = {
     "cg_rt_render_exposed": (C.c_int, [P, C.POINTER(Light), C.c_int, C.POINTER(RtCamera), C.c_int, C.c_int,
                                        C.POINTER(HdrExposureParams), P, C.c_int, C.c_float, P, C.c_size_t, P,
                                        C.POINTER(Stats)]),
+    "cg_hdr_bloom_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                      C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "cg_hdr_bloom": (C.c_int, [P, C.c_int, C.c_int, C.c_float, C.POINTER(HdrBloomParams), P]),
+    "cg_hdr_bloom_pack": (C.c_int, [P, P, C.c_int, C.c_int, C.c_float, C.POINTER(HdrBloomParams), C.c_int, C.c_int,
+                                    C.c_float, P]),
+    "cg_hdr_bloom_device": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, C.c_size_t, P, C.POINTER(HdrBloomParams), P,
+                                      C.c_size_t, P]),
+    "cg_hdr_bloom_pack_device": (C.c_int, [P, P, P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, P,
+                                           C.POINTER(HdrBloomParams), C.c_int, C.c_int, C.c_float, P, C.c_size_t, P]),
+    "cg_rt_render_exposed_bloom_device": (C.c_int, [P, C.POINTER(Light), C.c_int, C.POINTER(RtCamera), C.c_int,
+                                                    C.c_int, C.POINTER(HdrExposureParams), P, C.c_int, C.c_float,
+                                                    C.POINTER(HdrBloomParams), P, C.c_size_t, P, P]),
+    "cg_rt_render_exposed_bloom": (C.c_int, [P, C.POINTER(Light), C.c_int, C.POINTER(RtCamera), C.c_int, C.c_int,
+                                             C.POINTER(HdrExposureParams), P, C.c_int, C.c_float,
+                                             C.POINTER(HdrBloomParams), P, C.c_size_t, P, C.POINTER(Stats)]),
     "cg_rt_render_sequence": (C.c_int, [P, C.POINTER(Light), C.c_int, C.POINTER(RtCamera), C.c_int, P,
                                         C.c_size_t, C.c_int, C.POINTER(Stats)]),
     "cg_rt_sequence_runs": (C.c_int, [C.POINTER(RtCamera), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RtShard),
@@ -258,6 +284,12 @@ _SIGS = {
                                               C.c_int, C.c_float, P, C.c_size_t, P, P, P]),
     "cg_rast_draw_exposed": (C.c_int, [P, C.POINTER(RastParams), C.c_int, C.POINTER(HdrExposureParams), P, C.c_int,
                                        C.c_float, P, C.c_size_t, P, C.POINTER(RastSeqFrame), C.POINTER(Stats)]),
+    "cg_rast_draw_exposed_bloom_device": (C.c_int, [P, C.POINTER(RastParams), C.c_int, C.POINTER(HdrExposureParams),
+                                                    P, C.c_int, C.c_float, C.POINTER(HdrBloomParams), P, C.c_size_t, P,
+                                                    P, P]),
+    "cg_rast_draw_exposed_bloom": (C.c_int, [P, C.POINTER(RastParams), C.c_int, C.POINTER(HdrExposureParams), P,
+                                             C.c_int, C.c_float, C.POINTER(HdrBloomParams), P, C.c_size_t, P,
+                                             C.POINTER(RastSeqFrame), C.POINTER(Stats)]),
     "cg_rast_route": (C.c_int, [C.c_longlong]),
     "cg_rast_set_route": (C.c_int, [P, C.c_int]),
     "cg_rast_set_route_limit": (C.c_int, [P, C.c_longlong]),
@@ -428,6 +460,58 @@ def hdr_exposure(hist, params=None, prev=None, **kw):
     if rc:
         raise ValueError(f"cg_hdr_exposure: {rc}")
     return scales
+
+
+def hdr_bloom_layout(width, height, levels):
+    """cg_hdr_bloom_layout: (widths, heights, offsets, total) of levels 1 .. levels, offsets and total
+    in pixels (host-only; no GPU needed)."""
+    n = max(int(levels), 1)
+    w, h, off, total = (C.c_int * n)(), (C.c_int * n)(), (C.c_size_t * n)(), C.c_size_t(0)
+    rc = load().cg_hdr_bloom_layout(width, height, levels, w, h, off, C.byref(total))
+    if rc < 1 or rc != levels:
+        raise ValueError(f"cg_hdr_bloom_layout: {rc}")
+    return list(w), list(h), list(off), total.value
+
+
+def _bloom_arg(bloom, kw):
+    return hdr_bloom_params(**kw) if bloom is None else bloom
+
+
+def hdr_bloom(rgba, scale=1.0, bloom=None, **kw):
+    """cg_hdr_bloom: the pyramid float32[total, 4] of one frame float32[H, W, 4] (bloom: HdrBloomParams,
+    or hdr_bloom_params' keywords).  The scale passes by bit pattern (host-only; no GPU needed)."""
+    bloom = _bloom_arg(bloom, kw)
+    px = np.ascontiguousarray(rgba, np.float32)
+    if px.ndim != 3 or px.shape[2] != 4:
+        raise ValueError("a frame float32[H, W, 4]")
+    H, W = px.shape[:2]
+    total = hdr_bloom_layout(W, H, bloom.levels)[3]
+    pyr = np.empty((total, 4), np.float32)
+    rc = load().cg_hdr_bloom(px.ctypes.data_as(P), W, H, _f32_arg(np.float32(scale).view(np.uint32)), C.byref(bloom),
+                             pyr.ctypes.data_as(P))
+    if rc:
+        raise ValueError(f"cg_hdr_bloom: {rc}")
+    return pyr
+
+
+def hdr_bloom_pack(rgba, pyr, scale=1.0, bloom=None, rule=BLOOM_RULE_RT, op=TONE_LINEAR, white2=1.0, **kw):
+    """cg_hdr_bloom_pack: the composite uint32[H, W] of one frame float32[H, W, 4] and its pyramid."""
+    bloom = _bloom_arg(bloom, kw)
+    px = np.ascontiguousarray(rgba, np.float32)
+    if px.ndim != 3 or px.shape[2] != 4:
+        raise ValueError("a frame float32[H, W, 4]")
+    H, W = px.shape[:2]
+    total = hdr_bloom_layout(W, H, bloom.levels)[3]
+    pyr = np.ascontiguousarray(pyr, np.float32)
+    if pyr.size < total * 4:
+        raise ValueError("a pyramid of float32[total, 4]")
+    out = np.empty((H, W), np.uint32)
+    rc = load().cg_hdr_bloom_pack(px.ctypes.data_as(P), pyr.ctypes.data_as(P), W, H,
+                                  _f32_arg(np.float32(scale).view(np.uint32)), C.byref(bloom), rule, op, white2,
+                                  out.ctypes.data_as(P))
+    if rc:
+        raise ValueError(f"cg_hdr_bloom_pack: {rc}")
+    return out
 
 
 ROUTES = ("pixel", "lattice", "lattice_yaw", "lights", "lights_yaw", "big_pixel", "big_lattice", "big_lattice_yaw")
@@ -1125,6 +1209,55 @@ class Context:
                                                   C.byref(st)), "cg_rt_render_exposed")
         return out, scales
 
+    def hdr_bloom_device(self, d_rgba, width, height, n_frames, d_scales, bloom, d_pyr, src_stride=0, pyr_stride=0,
+                         stream=None):
+        """cg_hdr_bloom_device: the pyramids of n_frames frames into d_pyr + f * pyr_stride pixels."""
+        self._check(self.lib.cg_hdr_bloom_device(self.h, P(d_rgba), width, height, n_frames, src_stride, P(d_scales),
+                                                 C.byref(bloom), P(d_pyr), pyr_stride,
+                                                 P(stream) if stream else None), "cg_hdr_bloom_device")
+
+    def hdr_bloom_pack_device(self, d_rgba, d_pyr, width, height, n_frames, d_scales, bloom, d_argb,
+                              rule=BLOOM_RULE_RT, op=TONE_LINEAR, white2=1.0, src_stride=0, pyr_stride=0, dst_stride=0,
+                              stream=None):
+        """cg_hdr_bloom_pack_device: d_argb = PutPixelSDL(tone(op, base * s + intensity * up(U_1))) per frame."""
+        self._check(self.lib.cg_hdr_bloom_pack_device(self.h, P(d_rgba), P(d_pyr), width, height, n_frames, src_stride,
+                                                      pyr_stride, P(d_scales), C.byref(bloom), rule, op, white2,
+                                                      P(d_argb), dst_stride, P(stream) if stream else None),
+                    "cg_hdr_bloom_pack_device")
+
+    def rt_render_exposed_bloom_device(self, cams, d_argb, d_scales, params, bloom, lights=None,
+                                       per_frame_lights=False, d_prev=None, op=TONE_LINEAR, white2=1.0, frame_stride=0,
+                                       stream=None):
+        """cg_rt_render_exposed_bloom_device: rt_render_exposed_device with bloom between exposure and
+        the tone curve (bloom None: that call itself)."""
+        larr, n = self._exposed_lights(cams, lights, per_frame_lights)
+        arr = (RtCamera * max(len(cams), 1))(*cams)
+        self._check(self.lib.cg_rt_render_exposed_bloom_device(
+            self.h, larr, n, arr, len(cams), int(bool(per_frame_lights)), C.byref(params),
+            P(d_prev) if d_prev else None, op, white2, C.byref(bloom) if bloom is not None else None, P(d_argb),
+            frame_stride, P(d_scales), P(stream) if stream else None), "cg_rt_render_exposed_bloom_device")
+
+    def rt_render_exposed_bloom(self, cams, bloom, lights=None, per_frame_lights=False, permille=990, target=1.0,
+                                scale_min=2.0 ** -16, scale_max=2.0 ** 16, rate=1.0, prev=None, op=TONE_LINEAR,
+                                white2=1.0):
+        """cg_rt_render_exposed_bloom: (frames uint32[n, H, W], scales float32[n]) in host memory."""
+        n = len(cams)
+        if n == 0:
+            return np.zeros((0, 0, 0), np.uint32), np.zeros(0, np.float32)
+        larr, nl = self._exposed_lights(cams, lights, per_frame_lights)
+        arr = (RtCamera * n)(*cams)
+        params = hdr_params(permille, target, scale_min, scale_max, rate)
+        out = np.zeros((n, cams[0].height, cams[0].width), np.uint32)
+        scales = np.zeros(n, np.float32)
+        pv = None if prev is None else np.array([prev], np.float32)
+        st = Stats()
+        self._check(self.lib.cg_rt_render_exposed_bloom(
+            self.h, larr, nl, arr, n, int(bool(per_frame_lights)), C.byref(params),
+            pv.ctypes.data_as(P) if pv is not None else None, op, white2,
+            C.byref(bloom) if bloom is not None else None, out.ctypes.data_as(P), 0, scales.ctypes.data_as(P),
+            C.byref(st)), "cg_rt_render_exposed_bloom")
+        return out, scales
+
     def rt_render_frames(self, cams, out=None, chunk=0, lights=None, frame_stride=0):
         """cg_rt_render_frames: len(cams) frames into host memory `out` at f * frame_stride pixels
         (uint32; pageable or pinned, allocated pageable when None; frame_stride 0 = W * H),
@@ -1591,6 +1724,39 @@ class Context:
                                            C.cast(info.ctypes.data, C.POINTER(RastSeqFrame)), C.byref(st))
         if rc != CG_E_CAPACITY:
             self._check(rc, "cg_rast_draw_exposed")
+        return out, scales, info, rc
+
+    def rast_draw_exposed_bloom_device(self, params_list, d_argb, d_scales, params, bloom, d_info, d_prev=None,
+                                       op=TONE_LINEAR, white2=1.0, frame_stride=0, stream=None):
+        """cg_rast_draw_exposed_bloom_device: rast_draw_exposed_device with bloom (rule RAST) between
+        exposure and the tone curve (bloom None: that call itself)."""
+        arr = (RastParams * max(len(params_list), 1))(*params_list)
+        self._check(self.lib.cg_rast_draw_exposed_bloom_device(
+            self.h, arr, len(params_list), C.byref(params), P(d_prev) if d_prev else None, op, white2,
+            C.byref(bloom) if bloom is not None else None, P(d_argb), frame_stride, P(d_scales),
+            P(d_info) if d_info else None, P(stream) if stream else None), "cg_rast_draw_exposed_bloom_device")
+
+    def rast_draw_exposed_bloom(self, params_list, bloom, permille=990, target=1.0, scale_min=2.0 ** -16,
+                                scale_max=2.0 ** 16, rate=1.0, prev=None, op=TONE_LINEAR, white2=1.0):
+        """cg_rast_draw_exposed_bloom: (frames uint32[n, H, W], scales float32[n], info, rc) in host memory,
+        as rast_draw_exposed."""
+        n = len(params_list)
+        if n == 0:
+            return np.zeros((0, 0, 0), np.uint32), np.zeros(0, np.float32), np.zeros(1, RAST_SEQ_DTYPE), CG_OK
+        arr = (RastParams * n)(*params_list)
+        params = hdr_params(permille, target, scale_min, scale_max, rate)
+        out = np.zeros((n, params_list[0].height, params_list[0].width), np.uint32)
+        scales = np.zeros(n, np.float32)
+        info = np.zeros(n + 1, RAST_SEQ_DTYPE)
+        pv = None if prev is None else np.array([prev], np.float32)
+        st = Stats()
+        rc = self.lib.cg_rast_draw_exposed_bloom(self.h, arr, n, C.byref(params),
+                                                 pv.ctypes.data_as(P) if pv is not None else None, op, white2,
+                                                 C.byref(bloom) if bloom is not None else None,
+                                                 out.ctypes.data_as(P), 0, scales.ctypes.data_as(P),
+                                                 C.cast(info.ctypes.data, C.POINTER(RastSeqFrame)), C.byref(st))
+        if rc != CG_E_CAPACITY:
+            self._check(rc, "cg_rast_draw_exposed_bloom")
         return out, scales, info, rc
 
     def rast_set_route(self, route):

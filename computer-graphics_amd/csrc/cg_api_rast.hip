@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "cg_bloom.h"
 #include "cg_ctx.h"
 #include "cg_hdr.h"
 
@@ -898,10 +899,11 @@ constexpr int kRastHdrChunkFrames = 8;   // frames of cg_rast_draw_exposed_devic
 
 // what both forms of cg_rast_draw_exposed check before anything is enqueued (the sequence checks the rest)
 static int rast_exposed_check(cg_ctx *c, const cg_rast_params *ps, int n_frames, const cg_hdr_exposure_params *params,
-                              int op, float white2, size_t frame_stride)
+                              int op, float white2, size_t frame_stride, const cg_hdr_bloom_params *bloom)
 {
     if (!c || n_frames < 0 || (n_frames && !ps)) return CG_E_INVALID;
     if (!hdr_params_ok(params)) return ctx_invalid(c, "draw_exposed: exposure parameters");
+    if (bloom && !bloom_params_ok(bloom)) return ctx_invalid(c, "draw_exposed: bloom parameters");
     if (!hdr_tone_ok(op, white2)) return ctx_invalid(c, "draw_exposed: tone curve");
     if (c->n_room < 0) {
         c->err = "draw before cg_rast_set_scene";
@@ -919,10 +921,11 @@ static int rast_exposed_check(cg_ctx *c, const cg_rast_params *ps, int n_frames,
 
 // Frames f0 .. f0 + nf - 1 (nf <= kRastHdrChunkFrames) of an exposed call: the float sequence into
 // the context's scratch (resuming at d_info[0] when f0 > 0), then histogram, exposure (previous
-// scale *d_prev) and pack, all on st.  d_info: the chunk's first record.
+// scale *d_prev) and pack, all on st.  d_info: the chunk's first record.  With bloom: the chunk's
+// pyramids into scratch after the exposure, and the composite (rule RAST) for the pack.
 static int rast_exposed_chunk(cg_ctx *c, const cg_rast_params *ps, int f0, int nf,
                               const cg_hdr_exposure_params &params, const float *d_prev, int op, float white2,
-                              uint32_t *d_argb, size_t stride, float *d_scales, cg_rast_seq_frame *d_info,
+                              const cg_hdr_bloom_params *bloom, uint32_t *d_argb, size_t stride, float *d_scales, cg_rast_seq_frame *d_info,
                               hipStream_t st)
 {
     const size_t px = (size_t)ps[0].width * ps[0].height;
@@ -936,16 +939,30 @@ static int rast_exposed_chunk(cg_ctx *c, const cg_rast_params *ps, int f0, int n
     uint32_t *hist = (uint32_t *)c->hdr_hist.p;
     CG_TRY(c, launch_hdr_histogram(rgba, 4, px, nf, px, hist, nullptr, st), "histogram launch");
     CG_TRY(c, launch_hdr_exposure(hist, nf, params, d_prev, d_scales, st), "exposure launch");
+    if (bloom) {
+        BloomLayout L;
+        if (!bloom_layout(ps[0].width, ps[0].height, bloom->levels, &L)) return CG_E_INVALID;
+        CG_TRY(c, c->bloom_planes.ensure(kRastHdrChunkFrames * L.total * 16), "alloc bloom planes");
+        CG_TRY(c, c->bloom_pyr.ensure(kRastHdrChunkFrames * L.total * 16), "alloc bloom pyramids");
+        float *pyr = (float *)c->bloom_pyr.p;
+        CG_TRY(c, launch_bloom_pyramid(rgba, L, nf, px, d_scales, *bloom, (float *)c->bloom_planes.p, pyr, L.total, st),
+               "bloom launch");
+        CG_TRY(c, launch_bloom_pack(rgba, pyr, L, nf, px, L.total, d_scales, *bloom, CG_BLOOM_RULE_RAST, op, white2,
+                                    d_argb, stride, st),
+               "bloom pack launch");
+        return CG_OK;
+    }
     CG_TRY(c, launch_rast_tonemap_pack(rgba, px, nf, px, d_scales, op, white2, d_argb, stride, st), "tonemap pack launch");
     return CG_OK;
 }
 
-extern "C" int cg_rast_draw_exposed_device(cg_ctx *c, const cg_rast_params *ps, int n_frames,
-                                           const cg_hdr_exposure_params *params, const float *d_prev, int op,
-                                           float white2, uint32_t *d_argb, size_t frame_stride, float *d_scales,
-                                           cg_rast_seq_frame *d_info, void *stream)
+extern "C" int cg_rast_draw_exposed_bloom_device(cg_ctx *c, const cg_rast_params *ps, int n_frames,
+                                                 const cg_hdr_exposure_params *params, const float *d_prev, int op,
+                                                 float white2, const cg_hdr_bloom_params *bloom, uint32_t *d_argb,
+                                                 size_t frame_stride, float *d_scales, cg_rast_seq_frame *d_info,
+                                                 void *stream)
 {
-    if (int rc = rast_exposed_check(c, ps, n_frames, params, op, white2, frame_stride)) return rc;
+    if (int rc = rast_exposed_check(c, ps, n_frames, params, op, white2, frame_stride, bloom)) return rc;
     if (n_frames == 0) return CG_OK;
     if (!d_argb || ((uintptr_t)d_argb & 3) || !d_scales || ((uintptr_t)d_scales & 3) || ((uintptr_t)d_prev & 3))
         return CG_E_INVALID;
@@ -955,22 +972,31 @@ extern "C" int cg_rast_draw_exposed_device(cg_ctx *c, const cg_rast_params *ps, 
     const size_t stride = frame_stride ? frame_stride : (size_t)ps[0].width * ps[0].height;
     for (int f0 = 0; f0 < n_frames; f0 += kRastHdrChunkFrames) {
         const int nf = std::min(kRastHdrChunkFrames, n_frames - f0);
-        if (int rc = rast_exposed_chunk(c, ps, f0, nf, *params, f0 ? d_scales + f0 - 1 : d_prev, op, white2,
+        if (int rc = rast_exposed_chunk(c, ps, f0, nf, *params, f0 ? d_scales + f0 - 1 : d_prev, op, white2, bloom,
                                         d_argb + (size_t)f0 * stride, stride, d_scales + f0, d_info + f0, st))
             return rc;
     }
     return CG_OK;
 }
 
+extern "C" int cg_rast_draw_exposed_device(cg_ctx *c, const cg_rast_params *ps, int n_frames,
+                                           const cg_hdr_exposure_params *params, const float *d_prev, int op,
+                                           float white2, uint32_t *d_argb, size_t frame_stride, float *d_scales,
+                                           cg_rast_seq_frame *d_info, void *stream)
+{
+    return cg_rast_draw_exposed_bloom_device(c, ps, n_frames, params, d_prev, op, white2, nullptr, d_argb, frame_stride,
+                                             d_scales, d_info, stream);
+}
+
 // Host-memory form: the device form's chunks into context scratch, each chunk's frames downloaded
 // after its render; the scales (and the caller's previous scale) live in one device array,
 // [0] the previous scale, [1 + f] frame f's; the records in the host sequence's device array.
-extern "C" int cg_rast_draw_exposed(cg_ctx *c, const cg_rast_params *ps, int n_frames,
-                                    const cg_hdr_exposure_params *params, const float *prev, int op, float white2,
-                                    uint32_t *argb, size_t frame_stride, float *scales, cg_rast_seq_frame *info,
-                                    cg_stats *stats)
+extern "C" int cg_rast_draw_exposed_bloom(cg_ctx *c, const cg_rast_params *ps, int n_frames,
+                                          const cg_hdr_exposure_params *params, const float *prev, int op, float white2,
+                                          const cg_hdr_bloom_params *bloom, uint32_t *argb, size_t frame_stride,
+                                          float *scales, cg_rast_seq_frame *info, cg_stats *stats)
 {
-    if (int rc = rast_exposed_check(c, ps, n_frames, params, op, white2, frame_stride)) return rc;
+    if (int rc = rast_exposed_check(c, ps, n_frames, params, op, white2, frame_stride, bloom)) return rc;
     if (n_frames == 0) return CG_OK;
     if (!argb || !scales) return CG_E_INVALID;
     auto t0 = std::chrono::steady_clock::now();
@@ -989,7 +1015,7 @@ extern "C" int cg_rast_draw_exposed(cg_ctx *c, const cg_rast_params *ps, int n_f
     for (int f0 = 0; f0 < n_frames; f0 += kRastHdrChunkFrames) {
         const int nf = std::min(kRastHdrChunkFrames, n_frames - f0);
         CG_TRY(c, hipEventRecord(c->ev0, c->stream), "event");
-        if (int rc = rast_exposed_chunk(c, ps, f0, nf, *params, f0 || prev ? d_s + f0 : nullptr, op, white2, d_a, px,
+        if (int rc = rast_exposed_chunk(c, ps, f0, nf, *params, f0 || prev ? d_s + f0 : nullptr, op, white2, bloom, d_a, px,
                                         d_s + 1 + f0, d_info + f0, c->stream))
             return rc;
         CG_TRY(c, hipEventRecord(c->ev1, c->stream), "event");
@@ -1020,4 +1046,13 @@ extern "C" int cg_rast_draw_exposed(cg_ctx *c, const cg_rast_params *ps, int n_f
         stats->n_shaded = shaded;
     }
     return rc_out;
+}
+
+extern "C" int cg_rast_draw_exposed(cg_ctx *c, const cg_rast_params *ps, int n_frames,
+                                    const cg_hdr_exposure_params *params, const float *prev, int op, float white2,
+                                    uint32_t *argb, size_t frame_stride, float *scales, cg_rast_seq_frame *info,
+                                    cg_stats *stats)
+{
+    return cg_rast_draw_exposed_bloom(c, ps, n_frames, params, prev, op, white2, nullptr, argb, frame_stride, scales,
+                                      info, stats);
 }

@@ -1,8 +1,10 @@
 // cg_api_rt_host.hip -- raytracer frames delivered into host memory (cg_rt_render*, the HostFill
-// threads) and the exposure chain's entry points (cg_hdr_*, cg_rt_render_exposed*).  Host code only.
+// threads) and the exposure chain's entry points with bloom (cg_hdr_*, cg_rt_render_exposed*).  Host
+// code only.
 #include <chrono>
 #include <cstdlib>
 
+#include "cg_bloom.h"
 #include "cg_ctx.h"
 #include "cg_hdr.h"
 
@@ -169,11 +171,66 @@ extern "C" int cg_rt_tonemap_pack_device(cg_ctx *c, const float *d_rgba, size_t 
 
 constexpr int kHdrChunkFrames = 8;   // frames of cg_rt_render_exposed_device's scratch
 
+// ---- bloom (kernels: cg_bloom.hip; arithmetic: cg_bloom.h) ----
+// what both device bloom calls check of a frame set: size, strides (0: the plane) and alignment
+static bool bloom_frames_ok(int W, int H, const cg_hdr_bloom_params *bloom, BloomLayout *L, const float *d_rgba,
+                            size_t *sstride, const float *d_pyr, size_t *pstride, const float *d_scales)
+{
+    if (!bloom_params_ok(bloom) || !bloom_layout(W, H, bloom->levels, L) || (size_t)W * H >= ((size_t)1 << 32))
+        return false;
+    if (!*sstride) *sstride = (size_t)W * H;
+    if (!*pstride) *pstride = L->total;
+    return d_rgba && !((uintptr_t)d_rgba & 15) && d_pyr && !((uintptr_t)d_pyr & 15) && d_scales &&
+           !((uintptr_t)d_scales & 3) && *sstride >= (size_t)W * H && *pstride >= L->total;
+}
+
+extern "C" int cg_hdr_bloom_device(cg_ctx *c, const float *d_rgba, int width, int height, int n_frames,
+                                   size_t src_stride, const float *d_scales, const cg_hdr_bloom_params *bloom,
+                                   float *d_pyr, size_t pyr_stride, void *stream)
+{
+    if (!c || n_frames < 0 || !bloom_params_ok(bloom) || width <= 0 || height <= 0) return CG_E_INVALID;
+    if (n_frames == 0) return CG_OK;
+    BloomLayout L;
+    if (!bloom_frames_ok(width, height, bloom, &L, d_rgba, &src_stride, d_pyr, &pyr_stride, d_scales)) return CG_E_INVALID;
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    // the unblurred planes of kHdrChunkFrames frames at a time
+    CG_TRY(c, c->bloom_planes.ensure((size_t)std::min(n_frames, kHdrChunkFrames) * L.total * 16), "alloc bloom planes");
+    for (int f0 = 0; f0 < n_frames; f0 += kHdrChunkFrames)
+        CG_TRY(c, launch_bloom_pyramid(d_rgba + (size_t)f0 * src_stride * 4, L, std::min(kHdrChunkFrames, n_frames - f0),
+                                       src_stride, d_scales + f0, *bloom, (float *)c->bloom_planes.p,
+                                       d_pyr + (size_t)f0 * pyr_stride * 4, pyr_stride, st),
+               "bloom launch");
+    return CG_OK;
+}
+
+extern "C" int cg_hdr_bloom_pack_device(cg_ctx *c, const float *d_rgba, const float *d_pyr, int width, int height,
+                                        int n_frames, size_t src_stride, size_t pyr_stride, const float *d_scales,
+                                        const cg_hdr_bloom_params *bloom, int rule, int op, float white2,
+                                        uint32_t *d_argb, size_t dst_stride, void *stream)
+{
+    if (!c || n_frames < 0 || !bloom_params_ok(bloom) || !bloom_rule_ok(rule) || !hdr_tone_ok(op, white2) ||
+        width <= 0 || height <= 0)
+        return CG_E_INVALID;
+    if (n_frames == 0) return CG_OK;
+    BloomLayout L;
+    if (!bloom_frames_ok(width, height, bloom, &L, d_rgba, &src_stride, d_pyr, &pyr_stride, d_scales)) return CG_E_INVALID;
+    const size_t ds = dst_stride ? dst_stride : (size_t)width * height;
+    if (!d_argb || ((uintptr_t)d_argb & 3) || ds < (size_t)width * height) return CG_E_INVALID;
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    CG_TRY(c, launch_bloom_pack(d_rgba, d_pyr, L, n_frames, src_stride, pyr_stride, d_scales, *bloom, rule, op, white2,
+                                d_argb, ds, stream ? (hipStream_t)stream : c->stream),
+           "bloom pack launch");
+    return CG_OK;
+}
+
 // what both forms of cg_rt_render_exposed check before anything is enqueued
 static int rt_exposed_check(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams, int n_frames,
-                            const cg_hdr_exposure_params *params, int op, float white2, size_t frame_stride)
+                            const cg_hdr_exposure_params *params, int op, float white2, size_t frame_stride,
+                            const cg_hdr_bloom_params *bloom)
 {
     if (!c || n_frames < 0 || (n_frames && !cams) || !hdr_params_ok(params) || !hdr_tone_ok(op, white2) ||
+        (bloom && !bloom_params_ok(bloom)) ||
         n_lights < 0 || n_lights > kMaxLights || (n_lights && !lights))
         return CG_E_INVALID;
     if (n_frames == 0) return CG_OK;
@@ -191,9 +248,11 @@ static int rt_exposed_check(cg_ctx *c, const cg_light *lights, int n_lights, con
 
 // Frames f0 .. f0 + nf - 1 (nf <= kHdrChunkFrames) of an exposed call: rendered as CG_PIX_RGBA_F32
 // into the context's scratch, then histogram, exposure (previous scale *d_prev) and pack, all on st.
+// With bloom: the chunk's pyramids into scratch after the exposure, and the composite for the pack.
 static int rt_exposed_chunk(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams, int f0, int nf,
                             int per_frame_lights, const cg_hdr_exposure_params &params, const float *d_prev, int op,
-                            float white2, uint32_t *d_argb, size_t stride, float *d_scales, hipStream_t st)
+                            float white2, const cg_hdr_bloom_params *bloom, uint32_t *d_argb, size_t stride,
+                            float *d_scales, hipStream_t st)
 {
     const int H = cams[0].height;
     const size_t px = (size_t)cams[0].width * H;
@@ -209,16 +268,30 @@ static int rt_exposed_chunk(cg_ctx *c, const cg_light *lights, int n_lights, con
     uint32_t *hist = (uint32_t *)c->hdr_hist.p;
     CG_TRY(c, launch_hdr_histogram(rgba, 4, px, nf, px, hist, nullptr, st), "histogram launch");
     CG_TRY(c, launch_hdr_exposure(hist, nf, params, d_prev, d_scales, st), "exposure launch");
+    if (bloom) {
+        BloomLayout L;
+        if (!bloom_layout(cams[0].width, H, bloom->levels, &L)) return CG_E_INVALID;
+        CG_TRY(c, c->bloom_planes.ensure(kHdrChunkFrames * L.total * 16), "alloc bloom planes");
+        CG_TRY(c, c->bloom_pyr.ensure(kHdrChunkFrames * L.total * 16), "alloc bloom pyramids");
+        float *pyr = (float *)c->bloom_pyr.p;
+        CG_TRY(c, launch_bloom_pyramid(rgba, L, nf, px, d_scales, *bloom, (float *)c->bloom_planes.p, pyr, L.total, st),
+               "bloom launch");
+        CG_TRY(c, launch_bloom_pack(rgba, pyr, L, nf, px, L.total, d_scales, *bloom, CG_BLOOM_RULE_RT, op, white2, d_argb,
+                                    stride, st),
+               "bloom pack launch");
+        return CG_OK;
+    }
     CG_TRY(c, launch_rt_tonemap_pack(rgba, px, nf, px, d_scales, op, white2, d_argb, stride, st), "tonemap pack launch");
     return CG_OK;
 }
 
-extern "C" int cg_rt_render_exposed_device(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
-                                           int n_frames, int per_frame_lights, const cg_hdr_exposure_params *params,
-                                           const float *d_prev, int op, float white2, uint32_t *d_argb,
-                                           size_t frame_stride, float *d_scales, void *stream)
+extern "C" int cg_rt_render_exposed_bloom_device(cg_ctx *c, const cg_light *lights, int n_lights,
+                                                 const cg_rt_camera *cams, int n_frames, int per_frame_lights,
+                                                 const cg_hdr_exposure_params *params, const float *d_prev, int op,
+                                                 float white2, const cg_hdr_bloom_params *bloom, uint32_t *d_argb,
+                                                 size_t frame_stride, float *d_scales, void *stream)
 {
-    if (int rc = rt_exposed_check(c, lights, n_lights, cams, n_frames, params, op, white2, frame_stride)) return rc;
+    if (int rc = rt_exposed_check(c, lights, n_lights, cams, n_frames, params, op, white2, frame_stride, bloom)) return rc;
     if (n_frames == 0) return CG_OK;
     if (!d_argb || ((uintptr_t)d_argb & 3) || !d_scales || ((uintptr_t)d_scales & 3) || ((uintptr_t)d_prev & 3))
         return CG_E_INVALID;
@@ -228,22 +301,31 @@ extern "C" int cg_rt_render_exposed_device(cg_ctx *c, const cg_light *lights, in
     for (int f0 = 0; f0 < n_frames; f0 += kHdrChunkFrames) {
         const int nf = std::min(kHdrChunkFrames, n_frames - f0);
         if (int rc = rt_exposed_chunk(c, lights, n_lights, cams, f0, nf, per_frame_lights, *params,
-                                      f0 ? d_scales + f0 - 1 : d_prev, op, white2, d_argb + (size_t)f0 * stride, stride,
-                                      d_scales + f0, st))
+                                      f0 ? d_scales + f0 - 1 : d_prev, op, white2, bloom, d_argb + (size_t)f0 * stride,
+                                      stride, d_scales + f0, st))
             return rc;
     }
     return CG_OK;
 }
 
+extern "C" int cg_rt_render_exposed_device(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
+                                           int n_frames, int per_frame_lights, const cg_hdr_exposure_params *params,
+                                           const float *d_prev, int op, float white2, uint32_t *d_argb,
+                                           size_t frame_stride, float *d_scales, void *stream)
+{
+    return cg_rt_render_exposed_bloom_device(c, lights, n_lights, cams, n_frames, per_frame_lights, params, d_prev, op,
+                                             white2, nullptr, d_argb, frame_stride, d_scales, stream);
+}
+
 // Host-memory form: the device form's chunks into context scratch, each chunk's frames downloaded
 // after its render; the scales (and the caller's previous scale) live in one device array,
 // [0] the previous scale, [1 + f] frame f's.
-extern "C" int cg_rt_render_exposed(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
-                                    int n_frames, int per_frame_lights, const cg_hdr_exposure_params *params,
-                                    const float *prev, int op, float white2, uint32_t *argb, size_t frame_stride,
-                                    float *scales, cg_stats *stats)
+extern "C" int cg_rt_render_exposed_bloom(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
+                                          int n_frames, int per_frame_lights, const cg_hdr_exposure_params *params,
+                                          const float *prev, int op, float white2, const cg_hdr_bloom_params *bloom,
+                                          uint32_t *argb, size_t frame_stride, float *scales, cg_stats *stats)
 {
-    if (int rc = rt_exposed_check(c, lights, n_lights, cams, n_frames, params, op, white2, frame_stride)) return rc;
+    if (int rc = rt_exposed_check(c, lights, n_lights, cams, n_frames, params, op, white2, frame_stride, bloom)) return rc;
     if (n_frames == 0) return CG_OK;
     if (!argb || !scales) return CG_E_INVALID;
     auto t0 = std::chrono::steady_clock::now();
@@ -260,7 +342,8 @@ extern "C" int cg_rt_render_exposed(cg_ctx *c, const cg_light *lights, int n_lig
         const int nf = std::min(kHdrChunkFrames, n_frames - f0);
         CG_TRY(c, hipEventRecord(c->ev0, c->stream), "event");
         if (int rc = rt_exposed_chunk(c, lights, n_lights, cams, f0, nf, per_frame_lights, *params,
-                                      f0 || prev ? d_s + f0 : nullptr, op, white2, d_a, px, d_s + 1 + f0, c->stream))
+                                      f0 || prev ? d_s + f0 : nullptr, op, white2, bloom, d_a, px, d_s + 1 + f0,
+                                      c->stream))
             return rc;
         CG_TRY(c, hipEventRecord(c->ev1, c->stream), "event");
         CG_TRY(c, download_frames(argb + (size_t)f0 * stride, stride, d_a, cams[0].width, cams[0].height, nf, 0,
@@ -279,6 +362,15 @@ extern "C" int cg_rt_render_exposed(cg_ctx *c, const cg_light *lights, int n_lig
         stats->n_spans = 0;
     }
     return CG_OK;
+}
+
+extern "C" int cg_rt_render_exposed(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
+                                    int n_frames, int per_frame_lights, const cg_hdr_exposure_params *params,
+                                    const float *prev, int op, float white2, uint32_t *argb, size_t frame_stride,
+                                    float *scales, cg_stats *stats)
+{
+    return cg_rt_render_exposed_bloom(c, lights, n_lights, cams, n_frames, per_frame_lights, params, prev, op, white2,
+                                      nullptr, argb, frame_stride, scales, stats);
 }
 
 extern "C" int cg_rt_render(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cam,

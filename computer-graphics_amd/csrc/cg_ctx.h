@@ -155,6 +155,9 @@ struct cg_ctx {
     // cg_rt_render_exposed_device: a chunk's CG_PIX_RGBA_F32 frames and histograms; the host form's
     // chunk of ARGB frames, its scales and previous scale
     DevBuf hdr_rgba, hdr_hist, hdr_argb, hdr_scales;
+    // the bloom calls (cg_hdr_bloom_device, cg_*_exposed_bloom*): the unblurred planes B_k of up to 8
+    // frames, and the exposed calls' pyramids of a chunk
+    DevBuf bloom_planes, bloom_pyr;
     // their black columns (created on first use); declared after hslot: the threads end first
     std::unique_ptr<HostFill> hfill;
     RtGrid grid{};                      // large scenes only (n_tris > 64)

@@ -20,6 +20,7 @@
 namespace cg {
 
 struct SceneBounds;   // cg_rt_grid.h; the rest: cg_rast_dev.h
+struct BloomLayout;   // cg_bloom.h
 struct RastArgs; struct RastHdr; struct RastSeq; struct RastTexMaps; struct RastLast; struct RastFrame; struct RowRec;
 
 // The context's starfield state, used by cg_starfield.hip.  x and y never change; z alternates
@@ -139,6 +140,13 @@ hipError_t launch_rt_tonemap_pack(const float *, size_t, int, size_t, const floa
                                   hipStream_t);
 hipError_t launch_rast_tonemap_pack(const float *, size_t, int, size_t, const float *, int, float, uint32_t *, size_t,
                                     hipStream_t);
+// cg_bloom.hip: a chunk's pyramids (B_k into d_planes, n_frames * L.total pixels; U_k into d_pyr), and the composite
+hipError_t launch_bloom_pyramid(const float *d_rgba, const BloomLayout &L, int n_frames, size_t sstride,
+                                const float *d_scales, const cg_hdr_bloom_params &p, float *d_planes, float *d_pyr,
+                                size_t pstride, hipStream_t st);
+hipError_t launch_bloom_pack(const float *d_rgba, const float *d_pyr, const BloomLayout &L, int n_frames,
+                             size_t sstride, size_t pstride, const float *d_scales, const cg_hdr_bloom_params &p,
+                             int rule, int op, float white2, uint32_t *d_argb, size_t dstride, hipStream_t st);
 // cg_api_rt.hip: cg_rt_render_frames_device, plus per-frame completion signals for cg_dist
 int rt_render_frames(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams, int n_frames,
                      const cg_rt_shard *shard, void *d_out, size_t frame_stride, int pix_format, void *stream,

@@ -10,6 +10,7 @@
 //
 //   raytracer [--width W] [--height H] [--focal F] [--keys KEYS] [--out FILE] [--batch] [--pfm FILE]
 //             [--auto-exposure PERMILLE[,TARGET]] [--tonemap linear|reinhard|reinhard-white:W]
+//             [--bloom THRESHOLD,INTENSITY[,LEVELS[,CAP]]]
 //
 // --batch: Update() runs over the whole key script first, each frame's globals
 // are recorded, and one cg_rt_render_sequence call renders every frame; the
@@ -23,6 +24,9 @@
 // screenshot is the last exposed frame and the scale of every frame is printed.
 // --tonemap: the curve between the scaled radiance and PutPixelSDL (default linear; reinhard-white:W
 // maps radiance W to white); with --tonemap alone the scale is 1.
+// --bloom THRESHOLD,INTENSITY[,LEVELS[,CAP]]: the run goes through cg_rt_render_exposed_bloom -- glare
+// around what exceeds THRESHOLD after the scale, added INTENSITY times before the curve (levels 4 and
+// cap 64 unless given); without --auto-exposure every scale is 1.  Without the flag nothing changes.
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -32,6 +36,7 @@
 
 #include "SDLauxiliary.h"
 #include "TestModelH.h"
+#include "bloom_arg.h"
 #include "cg_render.h"
 
 using namespace std;
@@ -184,6 +189,8 @@ int main(int argc, char *argv[])
     cg_hdr_exposure_params expo{990, 1.0f, 1.0f, 1.0f, 1.0f};   // --tonemap alone: every scale is 1
     int tone = CG_TONE_LINEAR;
     float white2 = 1.0f;
+    bool bloomed = false;
+    cg_hdr_bloom_params bloom{4, 1.0f, 64.0f, 0.25f};          // --bloom: levels and cap unless given
     for (int i = 1; i < argc; i += 2) {
         string a = argv[i];
         if (a == "--batch") {
@@ -191,7 +198,13 @@ int main(int argc, char *argv[])
             --i;
             continue;
         }
-        if (i + 1 >= argc) break;
+        if (i + 1 >= argc) {
+            if (a == "--bloom") {   // a flag without its value
+                cerr << BLOOM_USAGE << endl;
+                return 1;
+            }
+            break;
+        }
         if (a == "--width") SCREEN_WIDTH = atoi(argv[i + 1]);
         else if (a == "--height") SCREEN_HEIGHT = atoi(argv[i + 1]);
         else if (a == "--focal") focalLength = (float)atof(argv[i + 1]);
@@ -219,6 +232,12 @@ int main(int argc, char *argv[])
                 return 1;
             }
             exposed = true;
+        } else if (a == "--bloom") {
+            if (!ParseBloomArg(argv[i + 1], &bloom)) {
+                cerr << BLOOM_USAGE << endl;
+                return 1;
+            }
+            bloomed = exposed = true;
         }
     }
     int rc = cg_create(0, &g_ctx);
@@ -243,10 +262,17 @@ int main(int argc, char *argv[])
             vector<uint32_t> frames(cams.size() * px);
             if (exposed) {
                 vector<float> scales(cams.size());
-                rc = cg_rt_render_exposed(g_ctx, reinterpret_cast<const cg_light *>(seq.data()), (int)lights.size(),
-                                          cams.data(), (int)cams.size(), 1, &expo, nullptr, tone, white2, frames.data(),
-                                          0, scales.data(), nullptr);
-                if (rc) die(rc, "cg_rt_render_exposed");
+                if (bloomed) {
+                    rc = cg_rt_render_exposed_bloom(g_ctx, reinterpret_cast<const cg_light *>(seq.data()),
+                                                    (int)lights.size(), cams.data(), (int)cams.size(), 1, &expo, nullptr,
+                                                    tone, white2, &bloom, frames.data(), 0, scales.data(), nullptr);
+                    if (rc) die(rc, "cg_rt_render_exposed_bloom");
+                } else {
+                    rc = cg_rt_render_exposed(g_ctx, reinterpret_cast<const cg_light *>(seq.data()), (int)lights.size(),
+                                              cams.data(), (int)cams.size(), 1, &expo, nullptr, tone, white2,
+                                              frames.data(), 0, scales.data(), nullptr);
+                    if (rc) die(rc, "cg_rt_render_exposed");
+                }
                 for (size_t f = 0; f < scales.size(); ++f) cout << "Exposure scale : " << scales[f] << endl;
             } else {
                 rc = cg_rt_render_sequence(g_ctx, reinterpret_cast<const cg_light *>(seq.data()), (int)lights.size(),

@@ -299,6 +299,96 @@ int main(int argc, char **argv)
             cg_hdr_exposure(hist.data(), 0, nullptr, nullptr, nullptr) != CG_E_INVALID)
             fail("cg_hdr_exposure refusals", -1);
     }
+    // the bloom pyramid's host-only restatements, in buffers of exactly the sizes the layout names
+    // (the index clamps at odd sizes and 1 x 1 levels are where host code could read outside them):
+    // layout, pyramid and composite on 1 x 1, 2 x 1, 5 x 4 and 33 x 17 with levels 1 and 6, the
+    // contract's two hand pins, the refusals
+    {
+        const int sizes[4][2] = {{1, 1}, {2, 1}, {5, 4}, {33, 17}};
+        for (const auto &sz : sizes)
+            for (int levels : {1, 6}) {
+                const int W = sz[0], H = sz[1];
+                std::vector<int> ws(levels), hs(levels);
+                std::vector<size_t> off(levels);
+                size_t total = 0;
+                if (cg_hdr_bloom_layout(W, H, levels, ws.data(), hs.data(), off.data(), &total) != levels)
+                    fail("cg_hdr_bloom_layout", levels);
+                size_t run = 0;
+                for (int k = 0, w = W, h = H; k < levels; ++k) {
+                    w = (w + 1) / 2, h = (h + 1) / 2;
+                    if (ws[k] != w || hs[k] != h || off[k] != run) fail("cg_hdr_bloom_layout level", k);
+                    run += (size_t)w * h;
+                }
+                if (run != total) fail("cg_hdr_bloom_layout total", (int)total);
+                std::vector<float> rgba((size_t)W * H * 4, 2.0f), pyr(total * 4, -1.0f);   // bright pass: 1.0 everywhere
+                std::vector<uint32_t> argb((size_t)W * H, 0u);
+                cg_hdr_bloom_params bp{levels, 1.0f, 64.0f, 0.25f};
+                if (int rc = cg_hdr_bloom(rgba.data(), W, H, 1.0f, &bp, pyr.data())) fail("cg_hdr_bloom", rc);
+                for (int k = 0; k < levels; ++k)   // a constant 1.0 gives U_k == levels - k + 1 exactly
+                    for (size_t i = 0; i < (size_t)ws[k] * hs[k]; ++i) {
+                        const float *p = &pyr[(off[k] + i) * 4];
+                        const float want = (float)(levels - k);
+                        if (p[0] != want || p[1] != want || p[2] != want || p[3] != 0.0f) fail("cg_hdr_bloom constant plane", k);
+                    }
+                for (int rule : {CG_BLOOM_RULE_RT, CG_BLOOM_RULE_RAST})
+                    for (int op : {CG_TONE_LINEAR, CG_TONE_REINHARD, CG_TONE_REINHARD_WHITE}) {
+                        if (int rc = cg_hdr_bloom_pack(rgba.data(), pyr.data(), W, H, 1.0f, &bp, rule, op, 4.0f, argb.data()))
+                            fail("cg_hdr_bloom_pack", rc);
+                        if ((argb[0] >> 24) != 128u || argb.back() != argb[0]) fail("cg_hdr_bloom_pack of a constant frame", rule);
+                    }
+            }
+        // 16 x 16, bright 4.0 on (8..9, 8..9), one level: U_1[2..6][2..6] = 4 outer(k, k), k = (1, 4, 6, 4, 1) / 16
+        std::vector<float> rgba(16 * 16 * 4, 0.0f), pyr(8 * 8 * 4);
+        for (size_t i = 0; i < 256; ++i) rgba[i * 4 + 3] = 1.0f;
+        for (int y = 8; y < 10; ++y)
+            for (int x = 8; x < 10; ++x)
+                for (int c = 0; c < 3; ++c) rgba[((size_t)y * 16 + x) * 4 + c] = 4.0f;
+        cg_hdr_bloom_params one{1, 0.0f, 64.0f, 0.0f};
+        if (int rc = cg_hdr_bloom(rgba.data(), 16, 16, 1.0f, &one, pyr.data())) fail("cg_hdr_bloom", rc);
+        const float k5[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+        float sum = 0.0f;
+        for (int y = 0; y < 8; ++y)
+            for (int x = 0; x < 8; ++x) {
+                const bool in = x >= 2 && x < 7 && y >= 2 && y < 7;
+                const float want = in ? 4.0f * (k5[y - 2] * k5[x - 2]) : 0.0f;
+                if (pyr[((size_t)y * 8 + x) * 4] != want) fail("cg_hdr_bloom binomial pin", y * 8 + x);
+                sum += pyr[((size_t)y * 8 + x) * 4];
+            }
+        if (pyr[(4 * 8 + 4) * 4] != 0.5625f || sum != 4.0f) fail("cg_hdr_bloom binomial centre and sum", -1);
+        // a single bright pixel of 4.0 at (8, 8): U_1(4, 4) = 0.140625 with one level, 0.17016602 with two
+        for (int y = 8; y < 10; ++y)
+            for (int x = 8; x < 10; ++x)
+                for (int c = 0; c < 3; ++c) rgba[((size_t)y * 16 + x) * 4 + c] = x == 8 && y == 8 ? 4.0f : 0.0f;
+        std::vector<float> pyr2((8 * 8 + 4 * 4) * 4);
+        cg_hdr_bloom_params two{2, 0.0f, 64.0f, 0.0f};
+        if (cg_hdr_bloom(rgba.data(), 16, 16, 1.0f, &one, pyr.data()) || pyr[(4 * 8 + 4) * 4] != 0.140625f ||
+            cg_hdr_bloom(rgba.data(), 16, 16, 1.0f, &two, pyr2.data()) || pyr2[(4 * 8 + 4) * 4] != 0.17016602f)
+            fail("cg_hdr_bloom single pixel pin", -1);
+        // refusals
+        uint32_t px = 0;
+        const float nan = std::nanf("");
+        cg_hdr_bloom_params bad[] = {{0, 1, 64, 0.25f}, {7, 1, 64, 0.25f}, {4, -1, 64, 0.25f}, {4, nan, 64, 0.25f},
+                                     {4, 1, 0, 0.25f}, {4, 1, nan, 0.25f}, {4, 1, 0x1p+65f, 0.25f}, {4, 1, 64, -1},
+                                     {4, 1, 64, nan}, {4, 1, 64, 0x1p+33f}};
+        for (const auto &b : bad)
+            if (cg_hdr_bloom(rgba.data(), 16, 16, 1.0f, &b, pyr2.data()) != CG_E_INVALID ||
+                cg_hdr_bloom_pack(rgba.data(), pyr2.data(), 16, 16, 1.0f, &b, 0, 0, 1.0f, &px) != CG_E_INVALID)
+                fail("bloom parameters accepted", b.levels);
+        if (cg_hdr_bloom(nullptr, 16, 16, 1.0f, &one, pyr.data()) != CG_E_INVALID ||
+            cg_hdr_bloom(rgba.data(), 16, 16, 1.0f, nullptr, pyr.data()) != CG_E_INVALID ||
+            cg_hdr_bloom(rgba.data(), 16, 16, 1.0f, &one, nullptr) != CG_E_INVALID ||
+            cg_hdr_bloom(rgba.data(), 0, 16, 1.0f, &one, pyr.data()) != CG_E_INVALID ||
+            cg_hdr_bloom_pack(rgba.data(), pyr.data(), 1, 1, 1.0f, &one, 2, 0, 1.0f, &px) != CG_E_INVALID ||
+            cg_hdr_bloom_pack(rgba.data(), pyr.data(), 1, 1, 1.0f, &one, 0, 3, 1.0f, &px) != CG_E_INVALID ||
+            cg_hdr_bloom_pack(rgba.data(), pyr.data(), 1, 1, 1.0f, &one, 0, 2, 0.0f, &px) != CG_E_INVALID ||
+            cg_hdr_bloom_pack(rgba.data(), pyr.data(), 1, 1, 1.0f, &one, 0, 0, 1.0f, nullptr) != CG_E_INVALID ||
+            cg_hdr_bloom_pack(rgba.data(), nullptr, 1, 1, 1.0f, &one, 0, 0, 1.0f, &px) != CG_E_INVALID ||
+            cg_hdr_bloom_layout(0, 1, 1, nullptr, nullptr, nullptr, nullptr) != CG_E_INVALID ||
+            cg_hdr_bloom_layout(1, 1, 0, nullptr, nullptr, nullptr, nullptr) != CG_E_INVALID ||
+            cg_hdr_bloom_layout(1, 1, 7, nullptr, nullptr, nullptr, nullptr) != CG_E_INVALID ||
+            cg_hdr_bloom_layout(33, 17, 6, nullptr, nullptr, nullptr, nullptr) != 6)
+            fail("bloom refusals", -1);
+    }
     const int malformed = malformed_jpegs();
     printf("sanitized host code: %d JPEGs, %d malformed JPEGs rejected, %ld clipped triangles, clean\n", checked,
            malformed, tris);

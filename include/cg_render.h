@@ -333,6 +333,86 @@ int cg_rt_render_exposed(cg_ctx *ctx, const cg_light *lights, int n_lights, cons
                          int per_frame_lights, const cg_hdr_exposure_params *params, const float *prev, int op,
                          float white2, uint32_t *argb, size_t frame_stride, float *scales, cg_stats *stats);
 
+/* ---- Bloom (cg_bloom.hip; arithmetic in csrc/cg_bloom.h) ----
+ * Glare around whatever exceeds the display range, between exposure and the tone curve.  A frame
+ * is W x H pixels of CG_PIX_RGBA_F32 (x, y, z, w) with scale s.  Every line below is one IEEE
+ * float32 operation or a select written as a ternary (a NaN takes the branch `false` names), in
+ * the order stated; no FMA is formed, so kernels and host helpers agree bit for bit.
+ *
+ * Parameters  valid when 1 <= levels <= 6, threshold >= 0, 0 < cap <= 0x1p+64f and
+ *             0 <= intensity <= 0x1p+32f (a NaN fails each comparison).  Under these limits every
+ *             pyramid value and intensity * g are finite whatever the pixels and the scale hold.
+ * 1 Bright    per channel c: c0 = c > 0.0f ? c : 0.0f; v = c0 * s; e = v - threshold;
+ *             b = e > 0.0f ? e : 0.0f; b = b < cap ? b : cap.  A pixel with !(w > 0.0f) has b = 0
+ *             in all three channels.  b is finite and in [0, cap]: a NaN gives 0, +inf gives cap.
+ * 2 Sizes     W_0 = W, W_k = (W_{k-1} + 1) / 2, likewise H, k = 1 .. levels.  A level may be
+ *             1 x 1, and the levels past it stay 1 x 1.
+ * 3 Box       B_k(X, Y) = 0.25f * ((p(x0, y0) + p(x1, y0)) + (p(x0, y1) + p(x1, y1))) with
+ *             x0 = 2X, x1 = min(2X + 1, W_{k-1} - 1), y0 = 2Y, y1 = min(2Y + 1, H_{k-1} - 1); p is
+ *             b for k = 1 and B_{k-1} otherwise.
+ * 4 Blur      separable, indices clamped to the level; t(d) the sample at offset d:
+ *             a = t(-2) + t(2); q = t(-1) + t(1); r = (a * 0.0625f + q * 0.25f) + t(0) * 0.375f,
+ *             each product and sum rounded on its own.  The horizontal pass runs over B_k, the
+ *             vertical pass over its result and gives G_k.
+ * 5 Up        from a coarse plane u (w x h) to fine pixel (X, Y): cx = X >> 1;
+ *             nx = (X & 1) ? min(cx + 1, w - 1) : max(cx - 1, 0); likewise cy, ny;
+ *             up = (0.5625f * u(cx, cy) + 0.1875f * u(nx, cy)) + (0.1875f * u(cx, ny) + 0.0625f * u(nx, ny)).
+ * 6 Pyramid   U_levels = G_levels; U_k = G_k + up(U_{k+1}) for k = levels - 1 .. 1.  A pyramid
+ *             pixel is four floats, the fourth +0.0f.  The pyramid of a frame is U_1, U_2, ...,
+ *             U_levels one after the other: level k starts at sum_{j<k} W_j * H_j pixels.
+ * 7 Composite of pixel (x, y): g = up(U_1) at (x, y) from W_1 x H_1; per channel v = base * s;
+ *             m = intensity * g; v2 = v + m; then tone(op, v2, white2) and PutPixelSDL unchanged.
+ *             CG_BLOOM_RULE_RT: base = c and every pixel is packed -- glow spills onto the
+ *             background, so a pixel with w = 0 is no longer necessarily 0x80000000.
+ *             CG_BLOOM_RULE_RAST: base = c > 0.0f ? c : 0.0f and a pixel with !(w > 0.0f) packs to
+ *             0u: the border the reference never writes stays 0.  With intensity == 0 either rule
+ *             gives cg_rt_tonemap_pack_device's / cg_rast_tonemap_pack_device's frame bit for bit. */
+#define CG_BLOOM_MAX_LEVELS 6
+#define CG_BLOOM_RULE_RT 0
+#define CG_BLOOM_RULE_RAST 1
+typedef struct { int levels; float threshold, cap, intensity; } cg_hdr_bloom_params;  /* 16 bytes */
+/* Host-only (no device, no context).  cg_hdr_bloom_layout: widths / heights / offsets (pixels) of
+ * levels 1 .. levels into arrays of `levels` entries and the pyramid's pixels into *total; any
+ * pointer may be NULL; returns `levels`, or CG_E_INVALID for sizes <= 0 or levels outside 1..6.
+ * cg_hdr_bloom: one frame's whole pyramid, total * 4 floats.  cg_hdr_bloom_pack: step 7 for one
+ * frame; only level 1 of `pyr` is read.  Both: CG_E_INVALID for NULL pointers, invalid
+ * parameters, sizes <= 0, an unknown rule or tone op. */
+int cg_hdr_bloom_layout(int width, int height, int levels, int *widths, int *heights, size_t *offsets, size_t *total);
+int cg_hdr_bloom(const float *rgba, int width, int height, float scale, const cg_hdr_bloom_params *bloom, float *pyr);
+int cg_hdr_bloom_pack(const float *rgba, const float *pyr, int width, int height, float scale,
+                      const cg_hdr_bloom_params *bloom, int rule, int op, float white2, uint32_t *argb);
+/* The pyramids of n_frames frames, enqueued on `stream` (NULL: the context's) without a host
+ * wait.  Frame f is read at d_rgba + f * src_stride pixels and its pyramid goes to d_pyr + f *
+ * pyr_stride pixels (strides in 16-byte pixels; 0: W * H and `total`); its scale is read on the
+ * device from d_scales[f].  The unblurred planes B_k live in grow-only scratch the context owns.
+ * That scratch (and the pyramids of the exposed calls below) is one set of buffers per context, used
+ * on whatever stream a call names: calls on one context that use it must be ordered among
+ * themselves, by one stream or by events; calls on different contexts are independent.
+ * Pixels between frames are neither read nor written.  CG_E_INVALID as the cg_hdr_* calls, and
+ * for invalid bloom parameters, a stride below its plane, W * H >= 2^32; n_frames == 0 returns
+ * CG_OK and touches nothing. */
+int cg_hdr_bloom_device(cg_ctx *ctx, const float *d_rgba, int width, int height, int n_frames, size_t src_stride,
+                        const float *d_scales, const cg_hdr_bloom_params *bloom, float *d_pyr, size_t pyr_stride,
+                        void *stream);
+/* Step 7 over n_frames frames: d_argb[f * dst_stride + p] from d_rgba[f * src_stride + p] and
+ * level 1 of the pyramid at d_pyr + f * pyr_stride (strides as above; dst_stride in pixels, 0: W * H). */
+int cg_hdr_bloom_pack_device(cg_ctx *ctx, const float *d_rgba, const float *d_pyr, int width, int height, int n_frames,
+                             size_t src_stride, size_t pyr_stride, const float *d_scales,
+                             const cg_hdr_bloom_params *bloom, int rule, int op, float white2, uint32_t *d_argb,
+                             size_t dst_stride, void *stream);
+/* cg_rt_render_exposed_device / cg_rt_render_exposed with bloom: a chunk of 8 frames is rendered
+ * float, then histogram, exposure, bloom and the composite (rule RT), the pyramids in scratch the
+ * context owns.  The scales are exactly those of the call without bloom.  bloom == NULL runs that
+ * call's chunk unchanged.  After the first call of a size it neither allocates nor waits. */
+int cg_rt_render_exposed_bloom_device(cg_ctx *ctx, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
+                                      int n_frames, int per_frame_lights, const cg_hdr_exposure_params *params,
+                                      const float *d_prev, int op, float white2, const cg_hdr_bloom_params *bloom,
+                                      uint32_t *d_argb, size_t frame_stride, float *d_scales, void *stream);
+int cg_rt_render_exposed_bloom(cg_ctx *ctx, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
+                               int n_frames, int per_frame_lights, const cg_hdr_exposure_params *params,
+                               const float *prev, int op, float white2, const cg_hdr_bloom_params *bloom,
+                               uint32_t *argb, size_t frame_stride, float *scales, cg_stats *stats);
+
 /* Frame assembly after a transfer of band shards: d_src holds n_blocks row
  * blocks in order, block b = n_frames x rows[b] rows of `width` pixels in
  * pix_format, landing at frame rows row0[b] .. row0[b] + rows[b] - 1 (rows
@@ -870,6 +950,18 @@ int cg_rast_draw_exposed_device(cg_ctx *ctx, const cg_rast_params *ps, int n_fra
 int cg_rast_draw_exposed(cg_ctx *ctx, const cg_rast_params *ps, int n_frames, const cg_hdr_exposure_params *params,
                          const float *prev, int op, float white2, uint32_t *argb, size_t frame_stride,
                          float *scales, cg_rast_seq_frame *info, cg_stats *stats);
+/* cg_rast_draw_exposed_device / cg_rast_draw_exposed with bloom (the Bloom section above, rule
+ * RAST): both routes, every colour mode, the rand() index passing from chunk to chunk; a frame
+ * flagged CG_E_CAPACITY is the all-uncovered picture, ARGB 0.  bloom == NULL runs the call without
+ * bloom unchanged. */
+int cg_rast_draw_exposed_bloom_device(cg_ctx *ctx, const cg_rast_params *ps, int n_frames,
+                                      const cg_hdr_exposure_params *params, const float *d_prev, int op, float white2,
+                                      const cg_hdr_bloom_params *bloom, uint32_t *d_argb, size_t frame_stride,
+                                      float *d_scales, cg_rast_seq_frame *d_info, void *stream);
+int cg_rast_draw_exposed_bloom(cg_ctx *ctx, const cg_rast_params *ps, int n_frames,
+                               const cg_hdr_exposure_params *params, const float *prev, int op, float white2,
+                               const cg_hdr_bloom_params *bloom, uint32_t *argb, size_t frame_stride, float *scales,
+                               cg_rast_seq_frame *info, cg_stats *stats);
 /* Test hook: capacity of the materialised rand() stream in fragments (3 values each);
  * 0 = automatic, 4 * W * H. */
 int cg_rast_set_rand_capacity(cg_ctx *ctx, long long fragments);
