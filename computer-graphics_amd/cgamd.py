@@ -90,6 +90,13 @@ def hdr_bloom_params(levels=4, threshold=1.0, cap=64.0, intensity=0.25):
     return HdrBloomParams(levels, threshold, cap, intensity)
 
 
+class JpegParams(C.Structure):         # cg_jpeg_params
+    _fields_ = [("quality", C.c_int), ("subsampling", C.c_int)]
+
+
+JPEG_444, JPEG_420 = 0, 2                  # Pillow's subsampling numbers
+
+
 class RTri(C.Structure):       # rasteriser Triangle, 84 B
     _fields_ = [("v0", Vec4), ("v1", Vec4), ("v2", Vec4), ("normal", Vec4), ("color", Vec3),
                 ("texture", C.c_int), ("index", C.c_int)]
@@ -327,6 +334,20 @@ _SIGS = {
     "cg_image_jpeg_check": (C.c_int, [P, C.c_size_t]),
     "cg_image_decode_jpeg": (C.c_int, [P, P, C.c_size_t, P, C.c_size_t]),
     "cg_image_decode_jpeg_device": (C.c_int, [P, P, C.c_size_t, P, C.c_size_t, P]),
+    "cg_image_encode_jpeg_host": (C.c_int, [P, C.c_int, C.c_int, C.c_size_t, C.POINTER(JpegParams), P, C.c_size_t,
+                                            C.POINTER(C.c_size_t)]),
+    "cg_image_jpeg_header": (C.c_int, [C.c_int, C.c_int, C.POINTER(JpegParams), P, C.c_size_t]),
+    "cg_image_jpeg_bound": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    "cg_image_jpeg_enc_limits": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "cg_image_encode_jpeg_device": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(JpegParams), P,
+                                              C.c_size_t, P, P]),
+    "cg_image_encode_jpeg": (C.c_int, [P, P, C.c_int, C.c_int, C.c_size_t, C.POINTER(JpegParams), P, C.c_size_t,
+                                       C.POINTER(C.c_size_t)]),
+    "cg_rt_render_sequence_jpeg": (C.c_int, [P, C.POINTER(Light), C.c_int, C.POINTER(RtCamera), C.c_int,
+                                             C.POINTER(JpegParams), P, C.c_size_t, C.POINTER(C.c_size_t), C.c_int,
+                                             C.POINTER(Stats)]),
+    "cg_rast_draw_sequence_jpeg": (C.c_int, [P, C.POINTER(RastParams), C.c_int, C.POINTER(JpegParams), P, C.c_size_t,
+                                             C.POINTER(C.c_size_t), C.c_int, C.POINTER(RastSeqFrame), C.POINTER(Stats)]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -872,6 +893,60 @@ def jpeg_info(data: bytes):
         raise ValueError("not a supported JPEG")
     return w.value, h.value, ch.value
 
+
+def image_jpeg_bound(width, height, subsampling=JPEG_420) -> int:
+    """cg_image_jpeg_bound: a length no JPEG file of the size can exceed (host-only)."""
+    n = load().cg_image_jpeg_bound(width, height, subsampling)
+    if n < 0:
+        raise ValueError(f"cg_image_jpeg_bound({width}, {height}, {subsampling}) failed ({n})")
+    return n
+
+
+def image_jpeg_header(width, height, quality=75, subsampling=JPEG_420) -> bytes:
+    """cg_image_jpeg_header: the bytes before the scan (host-only)."""
+    buf = np.zeros(1024, np.uint8)
+    prm = JpegParams(quality, subsampling)
+    n = load().cg_image_jpeg_header(width, height, C.byref(prm), buf.ctypes.data_as(P), buf.size)
+    if n < 0:
+        raise ValueError(f"cg_image_jpeg_header failed ({n})")
+    return buf[:n].tobytes()
+
+
+def image_jpeg_enc_limits():
+    """cg_image_jpeg_enc_limits: (lanes of an entropy workgroup, bytes of an interval it holds in LDS)."""
+    t, b = C.c_int(), C.c_int()
+    load().cg_image_jpeg_enc_limits(C.byref(t), C.byref(b))
+    return t.value, b.value
+
+
+def _jpeg_frame(argb):
+    a = np.ascontiguousarray(argb, dtype=np.uint32)
+    if a.ndim != 2 or a.size == 0:
+        raise ValueError("argb: a uint32 array (H, W)")
+    return a
+
+
+def _jpeg_encode(fn, what, argb, quality, subsampling):
+    a = _jpeg_frame(argb)
+    h, w = a.shape
+    prm = JpegParams(quality, subsampling)
+    n = C.c_size_t()
+    out = np.empty(max(4096, w * h), np.uint8)
+    rc = fn(a.ctypes.data_as(P), w, h, 0, C.byref(prm), out.ctypes.data_as(P), out.size, C.byref(n))
+    if rc == CG_E_CAPACITY:
+        out = np.empty(n.value, np.uint8)
+        rc = fn(a.ctypes.data_as(P), w, h, 0, C.byref(prm), out.ctypes.data_as(P), out.size, C.byref(n))
+    if rc != CG_OK:
+        raise ValueError(f"{what} failed ({rc})")
+    return out[:n.value].tobytes()
+
+
+def image_encode_jpeg_host(argb, quality=75, subsampling=JPEG_420) -> bytes:
+    """cg_image_encode_jpeg_host: the baseline JPEG file of a uint32 (H, W) ARGB8888 frame, the bytes
+    Pillow writes at that quality and subsampling with restart_marker_rows=1 (host-only, no GPU)."""
+    return _jpeg_encode(load().cg_image_encode_jpeg_host, "cg_image_encode_jpeg_host", argb, quality, subsampling)
+
+
 DIST_ID_BYTES = 128   # cg_dist_id (an RCCL unique id)
 DIST_SIGNALLED, DIST_CHUNKED = 0, 1   # cg_dist_set_pipeline
 
@@ -1336,6 +1411,84 @@ class Context:
                     "cg_rt_render_sequence")
         return out, st
 
+    def _sequence_jpeg(self, call, what, n, width, height, quality, subsampling, out, cap):
+        """A compressed delivery call: `call(params, out pointer, cap, offsets)` -> its status.  Without
+        `out` the buffer starts at n * W * H / 4 bytes and the call is repeated once at the capacity it
+        asks for.  -> (rc, out, offsets uint64[n + 1])."""
+        prm = JpegParams(quality, subsampling)
+        offsets = np.zeros(n + 1, np.uint64)
+        op = C.cast(offsets.ctypes.data, C.POINTER(C.c_size_t))
+        own = out is None
+        if own:
+            out = np.empty(max(4096, n * width * height // 4) if cap is None else cap, np.uint8)
+        size = out.nbytes if isinstance(out, np.ndarray) else out.numel() * out.element_size()
+        cap = size if cap is None else cap
+        if cap > size:
+            raise ValueError(f"cap {cap} > the {size} bytes of out")
+        ptr = lambda a: P(a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr())  # noqa: E731
+        rc = call(C.byref(prm), ptr(out), cap, op)
+        if rc == CG_E_CAPACITY and own and cap == size:
+            out = np.empty(int(offsets[n]), np.uint8)
+            rc = call(C.byref(prm), ptr(out), out.size, op)
+        if rc != CG_E_CAPACITY:
+            self._check(rc, what)
+        return rc, out, offsets
+
+    @staticmethod
+    def _jpeg_files(rc, out, offsets, cap):
+        """The files of a delivery as bytes; after CG_E_CAPACITY those that fit whole before the first that does not."""
+        host = out if isinstance(out, np.ndarray) else out.cpu().numpy()
+        files = []
+        for f in range(len(offsets) - 1):
+            if rc == CG_E_CAPACITY and int(offsets[f + 1]) > cap:
+                break
+            files.append(host[int(offsets[f]):int(offsets[f + 1])].tobytes())
+        return files
+
+    def rt_render_sequence_jpeg(self, cams, lights, quality=75, subsampling=JPEG_420, chunk=0, out=None, cap=None,
+                                full=False):
+        """cg_rt_render_sequence_jpeg: rt_render_sequence's frames as JPEG files -> list[bytes].  out /
+        cap supply the destination (a numpy array or a pinned tensor) and its capacity; full=True
+        returns (rc, files that fit, offsets, stats) and does not raise on CG_E_CAPACITY."""
+        if len(lights) != len(cams):
+            raise ValueError("one light list per frame")
+        if not cams:
+            return ([] if not full else (CG_OK, [], np.zeros(1, np.uint64), Stats()))
+        larr, n = sequence_lights(lights)
+        arr = (RtCamera * len(cams))(*cams)
+        st = Stats()
+        call = lambda prm, o, c, offs: self.lib.cg_rt_render_sequence_jpeg(  # noqa: E731
+            self.h, larr, n, arr, len(cams), prm, o, c, offs, chunk, C.byref(st))
+        rc, buf, offsets = self._sequence_jpeg(call, "cg_rt_render_sequence_jpeg", len(cams), cams[0].width,
+                                               cams[0].height, quality, subsampling, out, cap)
+        size = buf.nbytes if isinstance(buf, np.ndarray) else buf.numel() * buf.element_size()
+        files = self._jpeg_files(rc, buf, offsets, size if cap is None else cap)
+        if full:
+            return rc, files, offsets, st
+        self._check(rc, "cg_rt_render_sequence_jpeg")
+        return files
+
+    def rast_draw_sequence_jpeg(self, params_list, quality=75, subsampling=JPEG_420, chunk=0, out=None, cap=None,
+                                full=False):
+        """cg_rast_draw_sequence_jpeg: rast_draw_sequence's frames as JPEG files -> (list[bytes], info);
+        full=True returns (rc, files that fit, offsets, info, stats) and does not raise on CG_E_CAPACITY."""
+        n = len(params_list)
+        arr = (RastParams * max(n, 1))(*params_list)
+        info = np.zeros(n + 1, RAST_SEQ_DTYPE)
+        st = Stats()
+        if not n:
+            return ([], info) if not full else (CG_OK, [], np.zeros(1, np.uint64), info, st)
+        call = lambda prm, o, c, offs: self.lib.cg_rast_draw_sequence_jpeg(  # noqa: E731
+            self.h, arr, n, prm, o, c, offs, chunk, C.cast(info.ctypes.data, C.POINTER(RastSeqFrame)), C.byref(st))
+        rc, buf, offsets = self._sequence_jpeg(call, "cg_rast_draw_sequence_jpeg", n, params_list[0].width,
+                                               params_list[0].height, quality, subsampling, out, cap)
+        size = buf.nbytes if isinstance(buf, np.ndarray) else buf.numel() * buf.element_size()
+        files = self._jpeg_files(rc, buf, offsets, size if cap is None else cap)
+        if full:
+            return rc, files, offsets, info, st
+        self._check(rc, "cg_rast_draw_sequence_jpeg")
+        return files, info
+
     def rt_assemble_device(self, d_src, pix_format, row0, rows, width, height, nframes, d_frames, frame_stride=0,
                            stream=None, col0=0, cols=0):
         """cg_rt_assemble_device: row blocks (row0[b], rows[b]) of nframes frames -> frames."""
@@ -1532,6 +1685,22 @@ class Context:
         if rc != CG_E_CAPACITY:
             self._check(rc, "cg_image_decode_jpeg_device")
         return rc
+
+    def image_encode_jpeg(self, argb, quality=75, subsampling=JPEG_420) -> bytes:
+        """cg_image_encode_jpeg: image_encode_jpeg_host's file, encoded on this context's GPU."""
+        fn = lambda *a: self.lib.cg_image_encode_jpeg(self.h, *a)   # noqa: E731
+        return _jpeg_encode(fn, "cg_image_encode_jpeg", argb, quality, subsampling)
+
+    def image_encode_jpeg_device(self, d_argb, width, height, n_frames, d_out, slot_bytes, d_bytes, quality=75,
+                                 subsampling=JPEG_420, frame_stride=0, stream=None):
+        """cg_image_encode_jpeg_device: n_frames ARGB8888 frames at the device address d_argb (frame_stride
+        pixels apart; 0: width * height) to files at d_out + f * slot_bytes, their lengths (or
+        CG_E_CAPACITY) to the int64 array d_bytes; enqueued on `stream` (None: the context's)."""
+        prm = JpegParams(quality, subsampling)
+        self._check(self.lib.cg_image_encode_jpeg_device(self.h, P(d_argb), width, height, n_frames, frame_stride,
+                                                         C.byref(prm), P(d_out), slot_bytes, P(d_bytes),
+                                                         P(stream) if stream else None),
+                    "cg_image_encode_jpeg_device")
 
     def load_textures_jpeg(self, directory: str) -> dict:
         """Decode the reference's texture files found in `directory` (names as

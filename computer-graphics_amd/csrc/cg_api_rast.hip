@@ -821,6 +821,135 @@ extern "C" int cg_rast_draw_sequence(cg_ctx *c, const cg_rast_params *ps, int n_
     return rc_out;
 }
 
+// cg_rast_draw_sequence's frames delivered compressed: its chunks of the device sequence (ARGB only),
+// each encoded on the context's stream behind its render and copied while the next chunk renders
+// (JpegDelivery, cg_ctx.h).  The records and the rand() index chain are the device sequence's, so
+// they equal cg_rast_draw_sequence's.  A frame the stream's capacity could not hold is repaired
+// after the last chunk as there -- drawn alone from its record -- encoded, and put in its place
+// among the files, which are laid out again behind it.
+extern "C" int cg_rast_draw_sequence_jpeg(cg_ctx *c, const cg_rast_params *ps, int n_frames,
+                                          const cg_jpeg_params *params, uint8_t *out, size_t cap, size_t *offsets,
+                                          int chunk, cg_rast_seq_frame *info, cg_stats *stats)
+{
+    if (!c || !offsets || n_frames < 0 || (n_frames && !ps) || (!out && cap) || !params || params->quality < 1 ||
+        params->quality > 100 || (params->subsampling != CG_JPEG_444 && params->subsampling != CG_JPEG_420))
+        return CG_E_INVALID;
+    if (chunk < 0 || chunk > 64) return ctx_invalid(c, "draw_sequence_jpeg: chunk 0 .. 64");
+    if (c->n_room < 0) {
+        c->err = "draw before cg_rast_set_scene";
+        return CG_E_NOSCENE;
+    }
+    offsets[0] = 0;
+    if (n_frames == 0) return CG_OK;
+    const int W = ps[0].width, H = ps[0].height;
+    if (W <= 2 || H <= 2 || W > 65535 || H > 65535) return ctx_invalid(c, "draw_sequence_jpeg: frame size");
+    const size_t px = (size_t)W * H;
+    for (int f = 0; f < n_frames; ++f)
+        if (ps[f].colour_mode < 0 || ps[f].colour_mode > 2 || ps[f].width != W || ps[f].height != H)
+            return ctx_invalid(c, "draw_sequence_jpeg: colour modes 0-2, frames of one size");
+    auto t0 = std::chrono::steady_clock::now();
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    const int ch = std::min(chunk ? chunk : 8, n_frames);
+    static const int host_lanes = [] {   // cg_rast_draw_sequence's
+        const char *e = std::getenv("CG_RAST_HOST_LANES");
+        return std::max(1, std::min(e ? std::atoi(e) : 2, (int)cg_ctx::kRastLanes));
+    }();
+    struct Drain {
+        cg_ctx *c;
+        ~Drain()
+        {
+            (void)hipStreamSynchronize(c->xfer);
+            (void)hipStreamSynchronize(c->stream);
+        }
+    } drain_on_exit{c};
+    JpegDelivery D{c, W, H, n_frames, ch, *params, out, cap, offsets};
+    if (int rc = D.begin()) return rc;
+    for (int k = 0; k < 2; ++k) CG_TRY(c, c->rs_argb[k].ensure((size_t)ch * px * sizeof(uint32_t)), "alloc frame slots");
+    const size_t rec_bytes = ((size_t)n_frames + 1) * sizeof(cg_rast_seq_frame);
+    CG_TRY(c, c->rs_info.ensure(rec_bytes), "alloc records");
+    CG_TRY(c, c->rs_host.ensure(rec_bytes + sizeof(int)), "alloc host records");
+    cg_rast_seq_frame *d_info = (cg_rast_seq_frame *)c->rs_info.p, *rec = (cg_rast_seq_frame *)c->rs_host.p;
+    int *h_ntris = (int *)((char *)c->rs_host.p + rec_bytes);
+    const int nchunks = (n_frames + ch - 1) / ch;
+    CG_TRY(c, hipEventRecord(c->ev0, c->stream), "event");
+    for (int j = 0; j < nchunks; ++j) {
+        const int s = j & 1, f0 = j * ch, nf = std::min(ch, n_frames - f0);
+        int rc = D.slot_wait(j);
+        if (rc) return rc;
+        rc = rast_sequence_device(c, ps + f0, nf, (uint32_t *)c->rs_argb[s].p, nullptr, nullptr, px, d_info + f0, c->stream,
+                                  j > 0, host_lanes);
+        if (rc) return rc;
+        if ((rc = D.encode(j, (const uint32_t *)c->rs_argb[s].p, px))) return rc;
+        if (j >= 1 && (rc = D.deliver(j - 1))) return rc;
+    }
+    CG_TRY(c, hipEventRecord(c->ev1, c->stream), "event");
+    if (int rc = D.deliver(nchunks - 1)) return rc;
+    CG_TRY(c, hipMemcpyAsync(rec, d_info, rec_bytes, hipMemcpyDeviceToHost, c->stream), "d2h records");
+    *h_ntris = (int)std::max(c->rlast.n, 0ll);
+    if (stats && c->rlast.n < 0 && c->rlast.n_dev)
+        CG_TRY(c, hipMemcpyAsync(h_ntris, c->rlast.n_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream), "d2h count");
+    int rc_out = D.finish();
+    if (rc_out != CG_OK && rc_out != CG_E_CAPACITY) return rc_out;
+    float kernel_ms = 0.f;
+    (void)hipEventElapsedTime(&kernel_ms, c->ev0, c->ev1);
+    long long shaded = -1;
+    bool flagged = false;
+    for (int f = 0; f < n_frames; ++f) {
+        if (ps[f].colour_mode != 0) shaded = std::max(shaded, 0ll) + rec[f].n_shaded;
+        flagged = flagged || rec[f].status != 0;
+    }
+    if (flagged) {
+        // what `out` holds of the first pass, then every file again in order: a repaired frame's from
+        // its own encoding, the others' from the copy
+        std::vector<size_t> old(offsets, offsets + n_frames + 1);
+        size_t have = 0;   // frames of the first pass that are whole in `out`
+        while (have < (size_t)n_frames && old[have + 1] <= cap) ++have;
+        const std::vector<uint8_t> first(out, out + old[have]);
+        const bool last_flagged = rec[n_frames - 1].status != 0;
+        bool kept = false, stop = false;
+        RastLast last;
+        std::vector<uint32_t> frame(px);
+        std::vector<uint8_t> file;
+        for (int f = 0; f < n_frames; ++f) {
+            const uint8_t *src = (size_t)f < have ? first.data() + old[f] : nullptr;
+            size_t len = old[f + 1] - old[f];
+            if (rec[f].status == CG_E_CAPACITY) {
+                if (!kept && !last_flagged) {   // cg_rast_scratch_info reports the call's last frame
+                    if (const int rc = rast_last_resolve(c)) return rc;
+                    last = c->rlast;
+                    kept = true;
+                }
+                cg_rast_params p = ps[f];
+                p.rand_offset = rec[f].rand_offset;
+                int rc = cg_rast_draw(c, &p, frame.data(), nullptr, nullptr, nullptr);
+                if (rc) return rc;
+                file.resize((size_t)cg_image_jpeg_bound(W, H, params->subsampling));
+                if ((rc = cg_image_encode_jpeg(c, frame.data(), W, H, 0, params, file.data(), file.size(), &len))) return rc;
+                src = file.data();
+                rec[f].status = 0;
+            } else if (rec[f].status != 0) {
+                return rec[f].status;
+            }
+            offsets[f + 1] = offsets[f] + len;
+            stop = stop || !src || offsets[f + 1] > cap;
+            if (!stop) std::memcpy(out + offsets[f], src, len);
+        }
+        if (kept) c->rlast = last;
+        // a first pass that did not fit left files missing: the capacity asked for holds both passes
+        if (have < (size_t)n_frames) offsets[n_frames] = std::max(offsets[n_frames], old[n_frames]);
+        rc_out = offsets[n_frames] > cap ? CG_E_CAPACITY : CG_OK;
+    }
+    if (info) std::memcpy(info, rec, rec_bytes);
+    if (stats) {
+        stats->kernel_ms = kernel_ms;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->n_tris = *h_ntris;
+        stats->n_spans = 0;
+        stats->n_shaded = shaded;
+    }
+    return rc_out;
+}
+
 // ---- the float picture (CG_PIX_RGBA_F32) and exposed frames (kernels: the post-pass's *_f32
 // variants, cg_hdr.hip's rast_tonemap_pack_kernel) ----
 extern "C" int cg_rast_draw_picture_device(cg_ctx *c, const cg_rast_params *p, float *d_rgba, float *d_depth,

@@ -518,3 +518,146 @@ static int rt_render_frames_host(cg_ctx *c, const cg_light *lights, int n_lights
     }
     return CG_OK;
 }
+
+// ---- frames delivered compressed (kernels: cg_jpeg_enc.hip) ----
+int JpegDelivery::begin()
+{
+    slot_bytes = (size_t)W * H;   // a frame's device slot: a file this long is rare and is encoded again alone
+    CG_TRY(c, c->xfer.ensure(hipStreamNonBlocking), "copy stream");
+    for (int k = 0; k < 2; ++k) {
+        CG_TRY(c, c->jpeg_rdone[k].ensure(), "copy event");
+        CG_TRY(c, c->jpeg_cdone[k].ensure(), "copy event");
+        CG_TRY(c, c->jpeg_out[k].ensure(256 * (((size_t)ch * 8 + 255) / 256) + (size_t)ch * slot_bytes), "alloc file slots");
+    }
+    CG_TRY(c, c->jpeg_len_host.ensure(2 * (size_t)ch * 8), "alloc host lengths");
+    offsets[0] = 0;
+    full = false;
+    return CG_OK;
+}
+
+int JpegDelivery::slot_wait(int j)
+{
+    if (j >= 2) CG_TRY(c, hipStreamWaitEvent(c->stream, c->jpeg_cdone[j & 1], 0), "slot wait");
+    return CG_OK;
+}
+
+int JpegDelivery::encode(int j, const uint32_t *d_frames, size_t frame_stride)
+{
+    const int s = j & 1, nf = std::min(ch, n_frames - j * ch);
+    frames[s] = d_frames;
+    fstride[s] = frame_stride;
+    uint8_t *base = (uint8_t *)c->jpeg_out[s].p;
+    const size_t lens_b = 256 * (((size_t)ch * 8 + 255) / 256);
+    if (int rc = cg_image_encode_jpeg_device(c, d_frames, W, H, nf, frame_stride, &prm, base + lens_b, slot_bytes,
+                                             (int64_t *)base, c->stream))
+        return rc;
+    CG_TRY(c, hipEventRecord(c->jpeg_rdone[s], c->stream), "encode event");
+    return CG_OK;
+}
+
+int JpegDelivery::deliver(int j)
+{
+    const int s = j & 1, f0 = j * ch, nf = std::min(ch, n_frames - f0);
+    const uint8_t *base = (const uint8_t *)c->jpeg_out[s].p;
+    const size_t lens_b = 256 * (((size_t)ch * 8 + 255) / 256);
+    int64_t *h_len = (int64_t *)c->jpeg_len_host.p + (size_t)s * ch;
+    CG_TRY(c, hipStreamWaitEvent(c->xfer, c->jpeg_rdone[s], 0), "copy wait");
+    CG_TRY(c, hipMemcpyAsync(h_len, base, (size_t)nf * 8, hipMemcpyDeviceToHost, c->xfer), "d2h lengths");
+    CG_TRY(c, hipStreamSynchronize(c->xfer), "jpeg lengths");
+    for (int f = 0; f < nf; ++f) {
+        int64_t len = h_len[f];
+        const uint8_t *src = base + lens_b + (size_t)f * slot_bytes;
+        const bool again = len == CG_E_CAPACITY;
+        if (again) {   // longer than W * H bytes: alone, into a slot no file can exceed, behind what the stream holds
+            const size_t bound = (size_t)cg_image_jpeg_bound(W, H, prm.subsampling);
+            CG_TRY(c, c->jpeg_big.ensure(256 + bound), "alloc file slot");
+            uint8_t *big = (uint8_t *)c->jpeg_big.p;
+            if (int rc = cg_image_encode_jpeg_device(c, frames[s] + (size_t)f * fstride[s], W, H, 1, 0, &prm, big + 256, bound,
+                                                     (int64_t *)big, c->stream))
+                return rc;
+            CG_TRY(c, hipMemcpyAsync(&len, big, 8, hipMemcpyDeviceToHost, c->stream), "d2h length");
+            CG_TRY(c, hipStreamSynchronize(c->stream), "jpeg frame");
+            src = big + 256;
+        }
+        if (len < 0) return ctx_invalid(c, "jpeg delivery: a file longer than its bound");
+        const size_t at = offsets[f0 + f];
+        offsets[f0 + f + 1] = at + (size_t)len;
+        if (at + (size_t)len > cap) full = true;
+        if (full) continue;
+        if (again) CG_TRY(c, hipMemcpy(out + at, src, (size_t)len, hipMemcpyDeviceToHost), "download file");
+        else CG_TRY(c, hipMemcpyAsync(out + at, src, (size_t)len, hipMemcpyDeviceToHost, c->xfer), "download file");
+    }
+    CG_TRY(c, hipEventRecord(c->jpeg_cdone[s], c->xfer), "copy event");
+    return CG_OK;
+}
+
+int JpegDelivery::finish()
+{
+    CG_TRY(c, hipStreamSynchronize(c->xfer), "download files");
+    CG_TRY(c, hipStreamSynchronize(c->stream), "frames");
+    return offsets[n_frames] > cap ? CG_E_CAPACITY : CG_OK;
+}
+
+static bool jpeg_params_ok(const cg_jpeg_params *p)
+{
+    return p && p->quality >= 1 && p->quality <= 100 && (p->subsampling == CG_JPEG_444 || p->subsampling == CG_JPEG_420);
+}
+
+// cg_rt_render_sequence's chunks (rt_render_frames_host above), each encoded on the context's stream
+// behind its render; chunk j's files are copied while chunk j + 1 renders.
+extern "C" int cg_rt_render_sequence_jpeg(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
+                                          int n_frames, const cg_jpeg_params *params, uint8_t *out, size_t cap,
+                                          size_t *offsets, int chunk, cg_stats *stats)
+{
+    if (!c || !offsets || n_frames < 0 || (n_frames && !cams) || chunk < 0 || (!out && cap) || !jpeg_params_ok(params) ||
+        n_lights < 0 || n_lights > kMaxLights || (n_lights && !lights))
+        return CG_E_INVALID;
+    offsets[0] = 0;
+    if (n_frames == 0) return CG_OK;
+    auto t0 = std::chrono::steady_clock::now();
+    CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    const int W = cams[0].width, H = cams[0].height;
+    if (W <= 0 || H <= 0 || W > 65535 || H > 65535) return CG_E_INVALID;
+    for (int f = 1; f < n_frames; ++f)
+        if (cams[f].width != W || cams[f].height != H) return CG_E_INVALID;
+    const int ch = std::min(chunk ? std::min(chunk, 64) : 8, n_frames);
+    struct Drain {
+        cg_ctx *c;
+        ~Drain()
+        {
+            (void)hipStreamSynchronize(c->xfer);
+            (void)hipStreamSynchronize(c->stream);
+        }
+    } drain_on_exit{c};
+    JpegDelivery D{c, W, H, n_frames, ch, *params, out, cap, offsets};
+    if (int rc = D.begin()) return rc;
+    const size_t spx = (size_t)cg_rt_shard_rows(H, nullptr) * W;
+    for (int k = 0; k < 2; ++k) CG_TRY(c, c->hslot[k].ensure((size_t)ch * spx * sizeof(uint32_t)), "alloc frame slots");
+    const int nchunks = (n_frames + ch - 1) / ch;
+    const int light_stride = std::max(n_lights, 1);
+    CG_TRY(c, hipEventRecord(c->ev0, c->stream), "event");
+    for (int j = 0; j < nchunks; ++j) {
+        const int s = j & 1, f0 = j * ch, nf = std::min(ch, n_frames - f0);
+        int rc = D.slot_wait(j);
+        if (rc) return rc;
+        rc = rt_render_frames(c, lights ? lights + (size_t)f0 * n_lights : lights, n_lights, cams + f0, nf, nullptr,
+                              c->hslot[s].p, spx, CG_PIX_ARGB8888, c->stream, nullptr, nullptr, nullptr, 0, light_stride);
+        if (rc) return rc;
+        if ((rc = D.encode(j, (const uint32_t *)c->hslot[s].p, spx))) return rc;
+        if (j >= 1 && (rc = D.deliver(j - 1))) return rc;
+    }
+    CG_TRY(c, hipEventRecord(c->ev1, c->stream), "event");
+    if (int rc = D.deliver(nchunks - 1)) return rc;
+    const int rc = D.finish();
+    if (rc != CG_OK && rc != CG_E_CAPACITY) return rc;
+    if (stats) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
+        stats->kernel_ms = ms;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->n_tris = c->n_tris;
+        stats->n_spans = 0;
+        stats->n_shaded = -1;
+    }
+    return rc;
+}

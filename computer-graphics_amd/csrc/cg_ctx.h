@@ -249,6 +249,15 @@ struct cg_ctx {
     DevBuf sstars, sframe;               // starfield (cg_starfield.hip)
     StarState star;                      // resident stars and frame runs (cg_starfield.hip)
     DevBuf iscratch;                     // JPEG decode (cg_image.hip)
+    // JPEG encode (cg_jpeg_enc.hip): the coefficients, interval lengths, offsets and staged intervals
+    // of up to 8 frames; the host-memory form's uploaded frame, file slot and length
+    DevBuf jpeg_enc, jpeg_enc_io;
+    // cg_rt_render_sequence_jpeg, cg_rast_draw_sequence_jpeg (JpegDelivery below): per slot set a
+    // chunk's lengths and file slots, the slot of a frame encoded again alone, the lengths' pinned
+    // host copy, and the events of the copies on `xfer`
+    DevBuf jpeg_out[2], jpeg_big;
+    PinnedBuf jpeg_len_host;
+    Event jpeg_rdone[2], jpeg_cdone[2];
     int n_room = -1, n_boxes = 0;
     int scene_tex = 0;                   // bit k: the uploaded room/boxes carry texture k
     // texture modes 1-3 (cg_rast_set_textures): device copies of the maps
@@ -271,3 +280,28 @@ struct cg_ctx {
 int fill_frame(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cam, const cg_rt_shard *shard,
                hipStream_t st, RtFrame &F);
 int rt_enqueue(cg_ctx *c, const RtFrame &Fin, void *d_out_v, hipStream_t st, int slot = 0);
+
+// cg_api_rt_host.hip's, used by cg_api_rast.hip too: the compressed delivery of a frame sequence.
+// Chunks of `ch` frames are rendered by the caller into device memory on the context's stream;
+// encode(j, ..) enqueues chunk j's encoding into slot set j & 1 (a frame's slot is W * H bytes),
+// deliver(j) waits for it, reads the chunk's lengths and copies exactly those bytes into `out` back
+// to back on `xfer` -- called after chunk j + 1 is enqueued, it overlaps that chunk's render.  A
+// frame that did not fit its slot is encoded again alone into a slot of cg_image_jpeg_bound.
+// offsets[f] .. offsets[f + 1] is frame f's file; once a frame does not fit below `cap` nothing
+// more is copied and the offsets count on, so offsets[n_frames] is the capacity needed.
+struct JpegDelivery {
+    cg_ctx *c;
+    int W, H, n_frames, ch;
+    cg_jpeg_params prm;
+    uint8_t *out;
+    size_t cap, *offsets;
+    size_t slot_bytes = 0;
+    bool full = false;                       // a frame did not fit: nothing more is copied
+    const uint32_t *frames[2] = {};          // the slot sets' rendered chunks, for the frames encoded again
+    size_t fstride[2] = {};
+    int begin();
+    int slot_wait(int j);                    // before chunk j >= 2 is rendered: chunk j - 2 is copied
+    int encode(int j, const uint32_t *d_frames, size_t frame_stride);
+    int deliver(int j);
+    int finish();                            // waits for the copies; CG_E_CAPACITY if `out` was short
+};

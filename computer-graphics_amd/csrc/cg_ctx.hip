@@ -22,7 +22,7 @@ void *ctx_buf(cg_ctx *c, int which, size_t bytes, hipError_t *e)
         &cg_ctx::rtris, &cg_ctx::rhdr,   &cg_ctx::rspan,  &cg_ctx::rpix,   &cg_ctx::rargb,    &cg_ctx::rdepth, &cg_ctx::rshadow,
         &cg_ctx::rcount, &cg_ctx::rrecs, &cg_ctx::rgeo,   &cg_ctx::rpc,    &cg_ctx::rtl,      &cg_ctx::rrnd,   &cg_ctx::rjt,
         &cg_ctx::sstars, &cg_ctx::sframe, &cg_ctx::rtexel, &cg_ctx::iscratch, &cg_ctx::rseq,
-        &cg_ctx::rhdr_rgba};
+        &cg_ctx::rhdr_rgba, &cg_ctx::jpeg_enc, &cg_ctx::jpeg_enc_io};
     static_assert(sizeof(fields) / sizeof(fields[0]) == kBufFieldsEnd && kBufFieldsEnd <= kBufBig0, "named slots");
     static_assert(sizeof(c->rbig) / sizeof(c->rbig[0]) == kBufBigEnd - kBufBig0 && kBufBigEnd <= kBufOwner, "rbig slots");
     static_assert(sizeof(c->rbuf) / sizeof(c->rbuf[0]) == kBufOwnerEnd - kBufOwner, "rbuf slots");

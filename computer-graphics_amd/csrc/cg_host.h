@@ -51,8 +51,9 @@ enum {
     kBufStars, kBufStarFrame,            // cg_starfield.hip
     kBufTexel, kBufImage, kBufSeq,
     kBufRastHdr,                         // cg_rast_draw_exposed*: a chunk's CG_PIX_RGBA_F32 frames
+    kBufJpegEnc, kBufJpegEncIo,          // cg_jpeg_enc.hip: a chunk's coefficients and intervals; the host form's frame
     kBufFieldsEnd,
-    kBufBig0 = 20, kBufBigEnd = kBufBig0 + 15,
+    kBufBig0 = 22, kBufBigEnd = kBufBig0 + 15,
     kBufOwner = 40, kBufClipPre, kBufScreen, kBufLow, kBufHigh, kBufClipId, kBufTriId, kBufPos, kBufPick, kBufOwnerEnd
 };
 void *ctx_buf(cg_ctx *c, int which, size_t bytes, hipError_t *e);

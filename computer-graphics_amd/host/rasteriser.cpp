@@ -19,6 +19,7 @@
 //              [--setting S] [--setting-boxes B] [--textures DIR] [--batch] [--pfm FILE]
 //              [--auto-exposure PERMILLE[,TARGET]] [--tonemap linear|reinhard|reinhard-white:W]
 //              [--bloom THRESHOLD,INTENSITY[,LEVELS[,CAP]]]
+//              [--jpeg FILE [--quality 1..100] [--subsampling 444|420]]
 //
 // --batch: Update() runs over the whole key script first, each frame's globals
 // are recorded as a cg_rast_params, and one cg_rast_draw_sequence call renders
@@ -38,6 +39,10 @@
 // --bloom THRESHOLD,INTENSITY[,LEVELS[,CAP]]: the run goes through cg_rast_draw_exposed_bloom -- glare
 // around what exceeds THRESHOLD after the scale, added INTENSITY times before the curve (levels 4 and
 // cap 64 unless given); without --auto-exposure every scale is 1.
+// --jpeg FILE: the frame --out writes, as a baseline JPEG encoded on the device (cg_image_encode_jpeg;
+// quality 75 and 4:2:0 unless --quality / --subsampling say otherwise).  With --batch, every frame of
+// the run, the files one after the other (a motion-JPEG stream): through cg_rast_draw_sequence_jpeg,
+// or with the exposure flags each exposed frame through the encoder.
 #include <cmath>
 #include <cstring>
 #include <fstream>
@@ -48,6 +53,7 @@
 #include "TestModelH.h"
 #include "bloom_arg.h"
 #include "cg_render.h"
+#include "jpeg_arg.h"
 
 using namespace std;
 using glm::mat4;
@@ -209,6 +215,8 @@ int main(int argc, char *argv[])
     float white2 = 1.0f;
     bool bloomed = false;
     cg_hdr_bloom_params bloom{4, 1.0f, 64.0f, 0.25f};          // --bloom: levels and cap unless given
+    JpegArg jpeg;                                              // --jpeg: quality 75, 4:2:0 unless given
+    vector<uint8_t> jpeg_bytes;
     for (int i = 1; i < argc; i += 2) {
         string a = argv[i];
         if (a == "--batch") {
@@ -221,7 +229,18 @@ int main(int argc, char *argv[])
                 cerr << BLOOM_USAGE << endl;
                 return 1;
             }
+            if (ParseJpegArg(a, nullptr, &jpeg)) {
+                cerr << JPEG_USAGE << endl;
+                return 1;
+            }
             break;
+        }
+        if (const int j = ParseJpegArg(a, argv[i + 1], &jpeg)) {
+            if (j < 0) {
+                cerr << JPEG_USAGE << endl;
+                return 1;
+            }
+            continue;
         }
         if (a == "--width") SCREEN_WIDTH = atoi(argv[i + 1]);
         else if (a == "--height") SCREEN_HEIGHT = atoi(argv[i + 1]);
@@ -317,6 +336,20 @@ int main(int argc, char *argv[])
                 rc = cg_rast_draw_sequence(g_ctx, ps.data(), (int)ps.size(), frames.data(), nullptr, nullptr, 0, 0,
                                            info.data(), nullptr);
                 if (rc) die(rc, "cg_rast_draw_sequence");
+                if (!jpeg.path.empty() && batch) {   // the same frames again, delivered compressed
+                    rc = JpegDeliver(
+                        [&](uint8_t *o, size_t cap, size_t *offsets) {
+                            return cg_rast_draw_sequence_jpeg(g_ctx, ps.data(), (int)ps.size(), &jpeg.params, o, cap,
+                                                              offsets, 0, nullptr, nullptr);
+                        },
+                        ps.size(), screen->width, screen->height, &jpeg_bytes);
+                    if (rc) die(rc, "cg_rast_draw_sequence_jpeg");
+                }
+            }
+            if (!jpeg.path.empty() && batch && exposed) {
+                rc = JpegEncodeFrames(g_ctx, frames.data(), ps.size(), screen->width, screen->height, jpeg.params,
+                                      &jpeg_bytes);
+                if (rc) die(rc, "cg_image_encode_jpeg");
             }
             randCalls = info.back().rand_offset;
             g_last = ps.back();                               // the last frame, at its chained index
@@ -332,6 +365,16 @@ int main(int argc, char *argv[])
         }
     }
     SDL_SaveImage(screen, out.c_str());
+    if (!jpeg.path.empty()) {
+        if (jpeg_bytes.empty() && g_drawn) {   // the frame the screenshot holds
+            rc = JpegEncodeFrames(g_ctx, screen->buffer, 1, screen->width, screen->height, jpeg.params, &jpeg_bytes);
+            if (rc) die(rc, "cg_image_encode_jpeg");
+        }
+        if (!JpegSave(jpeg.path, jpeg_bytes)) {
+            cerr << "cannot write " << jpeg.path << endl;
+            return 1;
+        }
+    }
     if (!pfm.empty() && g_drawn) SavePicturePFM(pfm.c_str());
     KillSDL(screen);
     cg_destroy(g_ctx);

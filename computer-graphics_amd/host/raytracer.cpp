@@ -11,6 +11,7 @@
 //   raytracer [--width W] [--height H] [--focal F] [--keys KEYS] [--out FILE] [--batch] [--pfm FILE]
 //             [--auto-exposure PERMILLE[,TARGET]] [--tonemap linear|reinhard|reinhard-white:W]
 //             [--bloom THRESHOLD,INTENSITY[,LEVELS[,CAP]]]
+//             [--jpeg FILE [--quality 1..100] [--subsampling 444|420]]
 //
 // --batch: Update() runs over the whole key script first, each frame's globals
 // are recorded, and one cg_rt_render_sequence call renders every frame; the
@@ -27,6 +28,10 @@
 // --bloom THRESHOLD,INTENSITY[,LEVELS[,CAP]]: the run goes through cg_rt_render_exposed_bloom -- glare
 // around what exceeds THRESHOLD after the scale, added INTENSITY times before the curve (levels 4 and
 // cap 64 unless given); without --auto-exposure every scale is 1.  Without the flag nothing changes.
+// --jpeg FILE: the frame --out writes, as a baseline JPEG encoded on the device (cg_image_encode_jpeg;
+// quality 75 and 4:2:0 unless --quality / --subsampling say otherwise).  With --batch, every frame of
+// the run, the files one after the other (a motion-JPEG stream): through cg_rt_render_sequence_jpeg,
+// or with the exposure flags each exposed frame through the encoder.
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -38,6 +43,7 @@
 #include "TestModelH.h"
 #include "bloom_arg.h"
 #include "cg_render.h"
+#include "jpeg_arg.h"
 
 using namespace std;
 using glm::mat4;
@@ -191,6 +197,8 @@ int main(int argc, char *argv[])
     float white2 = 1.0f;
     bool bloomed = false;
     cg_hdr_bloom_params bloom{4, 1.0f, 64.0f, 0.25f};          // --bloom: levels and cap unless given
+    JpegArg jpeg;                                              // --jpeg: quality 75, 4:2:0 unless given
+    vector<uint8_t> jpeg_bytes;
     for (int i = 1; i < argc; i += 2) {
         string a = argv[i];
         if (a == "--batch") {
@@ -203,7 +211,18 @@ int main(int argc, char *argv[])
                 cerr << BLOOM_USAGE << endl;
                 return 1;
             }
+            if (ParseJpegArg(a, nullptr, &jpeg)) {
+                cerr << JPEG_USAGE << endl;
+                return 1;
+            }
             break;
+        }
+        if (const int j = ParseJpegArg(a, argv[i + 1], &jpeg)) {
+            if (j < 0) {
+                cerr << JPEG_USAGE << endl;
+                return 1;
+            }
+            continue;
         }
         if (a == "--width") SCREEN_WIDTH = atoi(argv[i + 1]);
         else if (a == "--height") SCREEN_HEIGHT = atoi(argv[i + 1]);
@@ -278,6 +297,21 @@ int main(int argc, char *argv[])
                 rc = cg_rt_render_sequence(g_ctx, reinterpret_cast<const cg_light *>(seq.data()), (int)lights.size(),
                                            cams.data(), (int)cams.size(), frames.data(), 0, 0, nullptr);
                 if (rc) die(rc, "cg_rt_render_sequence");
+                if (!jpeg.path.empty() && batch) {   // the same frames again, delivered compressed
+                    rc = JpegDeliver(
+                        [&](uint8_t *o, size_t cap, size_t *offsets) {
+                            return cg_rt_render_sequence_jpeg(g_ctx, reinterpret_cast<const cg_light *>(seq.data()),
+                                                              (int)lights.size(), cams.data(), (int)cams.size(),
+                                                              &jpeg.params, o, cap, offsets, 0, nullptr);
+                        },
+                        cams.size(), screen->width, screen->height, &jpeg_bytes);
+                    if (rc) die(rc, "cg_rt_render_sequence_jpeg");
+                }
+            }
+            if (!jpeg.path.empty() && batch && exposed) {
+                rc = JpegEncodeFrames(g_ctx, frames.data(), cams.size(), screen->width, screen->height, jpeg.params,
+                                      &jpeg_bytes);
+                if (rc) die(rc, "cg_image_encode_jpeg");
             }
             memcpy(screen->buffer, frames.data() + (cams.size() - 1) * px, px * sizeof(uint32_t));
             SDL_Renderframe(screen);
@@ -291,6 +325,16 @@ int main(int argc, char *argv[])
         }
     }
     SDL_SaveImage(screen, out.c_str());
+    if (!jpeg.path.empty()) {
+        if (jpeg_bytes.empty() && drawn > 0) {   // the frame the screenshot holds
+            rc = JpegEncodeFrames(g_ctx, screen->buffer, 1, screen->width, screen->height, jpeg.params, &jpeg_bytes);
+            if (rc) die(rc, "cg_image_encode_jpeg");
+        }
+        if (!JpegSave(jpeg.path, jpeg_bytes)) {
+            cerr << "cannot write " << jpeg.path << endl;
+            return 1;
+        }
+    }
     // Update() changes nothing on the turn it ends the loop: the globals are the last frame's
     if (!pfm.empty() && drawn > 0) SaveRadiancePFM(screen, pfm.c_str());
     KillSDL(screen);

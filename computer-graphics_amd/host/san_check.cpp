@@ -389,8 +389,64 @@ int main(int argc, char **argv)
             cg_hdr_bloom_layout(33, 17, 6, nullptr, nullptr, nullptr, nullptr) != 6)
             fail("bloom refusals", -1);
     }
+    // the JPEG encoder's host-only entries, in buffers of exactly the sizes they are told: sizes that
+    // are all padding, end inside a block and inside an MCU (dummy blocks at 4:2:0) and run over
+    // more than 8 restart intervals, a row stride, every capacity from 0 to the file's length on the
+    // smallest, one byte short on the others; the parser takes every product back
+    int encoded = 0;
+    {
+        const int sizes[][2] = {{1, 1}, {3, 2}, {8, 8}, {16, 16}, {33, 17}, {35, 20}, {24, 88}, {40, 150}};
+        uint32_t seed = 12345u;
+        for (const auto &sz : sizes)
+            for (int sub : {CG_JPEG_444, CG_JPEG_420})
+                for (int q : {1, 50, 100}) {
+                    const int W = sz[0], H = sz[1];
+                    const size_t stride = (size_t)W + 3;
+                    std::vector<uint32_t> px(stride * H);   // exactly H rows: the last row's stride is not read past
+                    for (auto &v : px) v = (seed = seed * 1103515245u + 12345u) >> ((seed >> 28) & 7);
+                    const cg_jpeg_params prm{q, sub};
+                    size_t need = 0, n = 0;
+                    if (cg_image_encode_jpeg_host(px.data(), W, H, stride, &prm, nullptr, 0, &need) != CG_E_CAPACITY || !need)
+                        fail("cg_image_encode_jpeg_host length query", q);
+                    if ((long long)need > cg_image_jpeg_bound(W, H, sub)) fail("cg_image_jpeg_bound", (int)need);
+                    std::vector<uint8_t> file(need);
+                    if (int rc = cg_image_encode_jpeg_host(px.data(), W, H, stride, &prm, file.data(), need, &n))
+                        fail("cg_image_encode_jpeg_host", rc);
+                    int w = 0, h = 0, c = 0;
+                    if (n != need || cg_image_jpeg_check(file.data(), n) || cg_image_jpeg_info(file.data(), n, &w, &h, &c) ||
+                        w != W || h != H || c != 3)
+                        fail("the parser on an encoded file", (int)n);
+                    for (size_t cap = W == 1 ? 0 : need - 1; cap < need; ++cap) {
+                        std::vector<uint8_t> part(cap);
+                        if (cg_image_encode_jpeg_host(px.data(), W, H, stride, &prm, part.data(), cap, &n) != CG_E_CAPACITY ||
+                            n != need || (cap && memcmp(part.data(), file.data(), cap)))
+                            fail("cg_image_encode_jpeg_host capacity", (int)cap);
+                    }
+                    std::vector<uint8_t> hdr(629);
+                    if (cg_image_jpeg_header(W, H, &prm, hdr.data(), 629) != 629 || memcmp(hdr.data(), file.data(), 629) ||
+                        cg_image_jpeg_header(W, H, &prm, hdr.data(), 628) != CG_E_CAPACITY)
+                        fail("cg_image_jpeg_header", W);
+                    ++encoded;
+                }
+        const cg_jpeg_params ok{75, CG_JPEG_420}, bad_q{0, CG_JPEG_420}, bad_s{75, 1};
+        uint32_t one = 0;
+        uint8_t byte = 0;
+        size_t n = 0;
+        if (cg_image_encode_jpeg_host(&one, 0, 1, 0, &ok, &byte, 1, &n) != CG_E_INVALID ||
+            cg_image_encode_jpeg_host(&one, 1, 65536, 0, &ok, &byte, 1, &n) != CG_E_INVALID ||
+            cg_image_encode_jpeg_host(&one, 1, 1, 0, &bad_q, &byte, 1, &n) != CG_E_INVALID ||
+            cg_image_encode_jpeg_host(&one, 1, 1, 0, &bad_s, &byte, 1, &n) != CG_E_INVALID ||
+            cg_image_encode_jpeg_host(nullptr, 1, 1, 0, &ok, &byte, 1, &n) != CG_E_INVALID ||
+            cg_image_encode_jpeg_host(&one, 1, 1, 0, &ok, nullptr, 1, &n) != CG_E_INVALID ||
+            cg_image_encode_jpeg_host(&one, 1, 1, 0, &ok, &byte, 1, nullptr) != CG_E_INVALID ||
+            cg_image_encode_jpeg_host(&one, 2, 1, 1, &ok, &byte, 1, &n) != CG_E_INVALID ||
+            cg_image_jpeg_header(1, 1, nullptr, &byte, 1) != CG_E_INVALID ||
+            cg_image_jpeg_header(1, 1, &ok, nullptr, 629) != CG_E_INVALID || cg_image_jpeg_bound(0, 1, 0) != CG_E_INVALID ||
+            cg_image_jpeg_bound(1, 1, 1) != CG_E_INVALID || cg_image_jpeg_bound(65535, 65535, CG_JPEG_444) <= 0)
+            fail("jpeg encoder refusals", -1);
+    }
     const int malformed = malformed_jpegs();
-    printf("sanitized host code: %d JPEGs, %d malformed JPEGs rejected, %ld clipped triangles, clean\n", checked,
-           malformed, tris);
+    printf("sanitized host code: %d JPEGs, %d malformed JPEGs rejected, %d JPEGs encoded, %ld clipped triangles, clean\n",
+           checked, malformed, encoded, tris);
     return 0;
 }

@@ -1016,6 +1016,103 @@ int cg_image_decode_jpeg(cg_ctx *ctx, const uint8_t *data, size_t n, uint8_t *ou
 int cg_image_decode_jpeg_device(cg_ctx *ctx, const uint8_t *data, size_t n, uint8_t *d_out, size_t cap,
                                 void *stream);
 
+/* ---- JPEG encoding ------------------------------------------------------ */
+/* A baseline JPEG encoder for ARGB8888 frames.  The contract is bit-exact: the file is, byte for
+ * byte, what Pillow over libjpeg-turbo writes with
+ *     Image.fromarray(rgb).save(f, format="JPEG", quality=Q, subsampling=S, restart_marker_rows=1)
+ * and no other option, where rgb[y][x] = (bits 16-23, bits 8-15, bits 0-7) of pixel (x, y); the
+ * alpha byte is ignored.  Q is 1 .. 100, S is CG_JPEG_444 or CG_JPEG_420.  All arithmetic is int32,
+ * `>>` arithmetic, each operation in the order stated; the host function and the kernels share it
+ * (csrc/cg_jpeg_enc.h).
+ *
+ * 1 Colour    Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16
+ *             Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *             Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16
+ * 2 Planes    The MCU is 8 x 8 pixels at 4:4:4 and 16 x 16 at 4:2:0; MX = ceil(W / mcu), MY =
+ *             ceil(H / mcu).  A full-resolution plane is padded by replicating its last column and
+ *             last row.  At 4:2:0 a chroma sample is c[y][x] = (p[2y][2x] + p[2y][2x+1] + p[2y+1][2x]
+ *             + p[2y+1][2x+1] + bias) >> 2, bias 1 for even x and 2 for odd, over the plane padded to
+ *             16 MX columns and an even number of rows; rows of c beyond ceil(H / 2) repeat the last.
+ * 3 Dummies   At 4:2:0 a Y block at or beyond block column ceil(W / 8) or block row ceil(H / 8) is
+ *             not transformed: its AC coefficients are 0 and its DC is the quantised DC of the
+ *             previous block of its MCU, in the order 00, 01, 10, 11 (the first is always real).
+ * 4 FDCT      libjpeg's jfdctint (CONST_BITS 13, PASS1_BITS 2) on sample - 128, rows then columns;
+ *             DESCALE(x, n) = (x + (1 << (n - 1))) >> n; n = 11 for rows, 15 for columns.
+ *             t0 = d0+d7, t7 = d0-d7, t1 = d1+d6, t6 = d1-d6, t2 = d2+d5, t5 = d2-d5, t3 = d3+d4,
+ *             t4 = d3-d4; t10 = t0+t3, t13 = t0-t3, t11 = t1+t2, t12 = t1-t2.
+ *             rows: o0 = (t10+t11) << 2, o4 = (t10-t11) << 2; columns: o0 = DESCALE(t10+t11, 2),
+ *             o4 = DESCALE(t10-t11, 2).  z1 = (t12+t13) * 4433; o2 = DESCALE(z1 + t13 * 6270, n);
+ *             o6 = DESCALE(z1 - t12 * 15137, n).  z1 = t4+t7, z2 = t5+t6, z3 = t4+t6, z4 = t5+t7,
+ *             z5 = (z3+z4) * 9633; t4 *= 2446, t5 *= 16819, t6 *= 25172, t7 *= 12299; z1 *= -7373,
+ *             z2 *= -20995, z3 *= -16069, z4 *= -3196; z3 += z5, z4 += z5;
+ *             o7 = DESCALE(t4+z1+z3, n), o5 = DESCALE(t5+z2+z4, n), o3 = DESCALE(t6+z2+z3, n),
+ *             o1 = DESCALE(t7+z1+z4, n).
+ * 5 Quantise  scale = Q < 50 ? 5000 / Q : 200 - 2 Q; q = clamp((base * scale + 50) / 100, 1, 255)
+ *             over the Annex K.1 tables (luminance for Y, chrominance for Cb and Cr); the coefficient
+ *             is sign(c) * ((|c| + (8 q >> 1)) / (8 q)), integer division (the FDCT carries a factor 8).
+ * 6 Entropy   The four Annex K.3 Huffman tables, Y with tables 0, Cb and Cr with tables 1.  DC: the
+ *             category of the difference to the previous block of the component, then its low bits,
+ *             a negative v sent as v - 1.  AC in zig-zag order: run/size symbols, 0xF0 for each 16
+ *             zeros before a coefficient, 0x00 if the block ends in zeros.  Bits fill bytes from the
+ *             top; a 00 follows every FF byte.  MCUs run left to right, top to bottom, their blocks
+ *             Y (00 01 10 11 at 4:2:0), Cb, Cr.  The restart interval is MX: before every MCU row k
+ *             >= 1 the last byte is padded with 1-bits, FF D0+((k-1) mod 8) is written and the three
+ *             predictors return to 0.  After the last row: pad, FF D9.
+ * 7 Header    629 bytes: SOI; APP0 (JFIF 1.1, no units, 1:1, no thumbnail); DQT 0; DQT 1 (separate
+ *             segments, zig-zag order); SOF0 (precision 8, H, W, components 1 22|11 0, 2 11 1,
+ *             3 11 1); DHT DC0, AC0, DC1, AC1; DRI MX; SOS (1 00, 2 11, 3 11, 00 3F 00). */
+#define CG_JPEG_444 0
+#define CG_JPEG_420 2
+typedef struct { int quality; int subsampling; } cg_jpeg_params;
+/* Host-only (no device, no context).  cg_image_encode_jpeg_host: the file of width x height
+ * pixels, rows row_stride_pixels apart (0: width), into out[0 .. cap) and its length into *n;
+ * CG_E_CAPACITY with *n = the length needed when cap is short (no byte at or past cap is written;
+ * out may be NULL with cap 0).  cg_image_jpeg_header: the bytes before the scan, the same for
+ * every frame of a size and params; returns their count (629) or CG_E_CAPACITY.
+ * cg_image_jpeg_bound: a length no file of the size can exceed -- every block at its longest code
+ * (22 bits of DC, 63 coefficients of 16 + 10 bits) and every byte of the scan stuffed.
+ * cg_image_jpeg_enc_limits: the entropy kernel's workgroup size and the bytes of an interval it
+ * holds in LDS at a time (tests size their cases from these).  CG_E_INVALID for a width or height
+ * outside 1 .. 65535, a quality outside 1 .. 100, another subsampling, NULL pointers. */
+int cg_image_encode_jpeg_host(const uint32_t *argb, int width, int height, size_t row_stride_pixels,
+                              const cg_jpeg_params *params, uint8_t *out, size_t cap, size_t *n);
+int cg_image_jpeg_header(int width, int height, const cg_jpeg_params *params, uint8_t *out, size_t cap);
+long long cg_image_jpeg_bound(int width, int height, int subsampling);
+int cg_image_jpeg_enc_limits(int *threads, int *stage_bytes);
+/* n_frames frames in device memory, enqueued on `stream` (NULL: the context's) without a host
+ * wait.  Frame f is read at d_argb + f * frame_stride pixels (0: width * height; rows are width
+ * apart); its file goes to d_out + f * slot_bytes and its length to d_bytes[f] (8-byte aligned), or
+ * CG_E_CAPACITY there when the file is longer than slot_bytes: then nothing is written to that
+ * slot, and the other frames are unaffected.  Nothing is written past a file's last byte.  The
+ * coefficients and staged intervals of up to 8 frames live in grow-only scratch the context owns,
+ * one set per context: calls on one context must be ordered among themselves, by one stream or by
+ * events; calls on different contexts are independent.  After the first call of a size it does not
+ * allocate.  n_frames == 0 returns CG_OK and touches nothing. */
+int cg_image_encode_jpeg_device(cg_ctx *ctx, const uint32_t *d_argb, int width, int height, int n_frames,
+                                size_t frame_stride, const cg_jpeg_params *params, uint8_t *d_out, size_t slot_bytes,
+                                int64_t *d_bytes, void *stream);
+/* One frame in host memory through the device encoder, arguments as cg_image_encode_jpeg_host;
+ * waits for the file. */
+int cg_image_encode_jpeg(cg_ctx *ctx, const uint32_t *argb, int width, int height, size_t row_stride_pixels,
+                         const cg_jpeg_params *params, uint8_t *out, size_t cap, size_t *n);
+/* Frame sequences delivered into host memory compressed: cg_rt_render_sequence's and
+ * cg_rast_draw_sequence's frames (arguments as there; ARGB only), rendered in chunks of `chunk`
+ * frames (0: 8, at most 64) into the chunk slots of those calls and encoded on the device into
+ * slots of width * height bytes.  A chunk's lengths are read back and exactly its files' bytes are
+ * copied into `out` back to back while the next chunk renders; a file longer than its slot is
+ * encoded again alone into a slot of cg_image_jpeg_bound.  offsets has n_frames + 1 entries:
+ * offsets[f] .. offsets[f + 1] is frame f's file.  If `out` (cap bytes) is short the call returns
+ * CG_E_CAPACITY: the files that fit whole before the first that does not are intact, nothing is
+ * written past cap, and offsets[n_frames] is the capacity a second call needs.  The rasteriser's
+ * rand() index chain and `info` records equal cg_rast_draw_sequence's.  CG_E_INVALID as the calls
+ * they mirror and the encoder (a side above 65535, invalid params, NULL offsets). */
+int cg_rt_render_sequence_jpeg(cg_ctx *ctx, const cg_light *lights, int n_lights, const cg_rt_camera *cams, int n_frames,
+                               const cg_jpeg_params *params, uint8_t *out, size_t cap, size_t *offsets, int chunk,
+                               cg_stats *stats);
+int cg_rast_draw_sequence_jpeg(cg_ctx *ctx, const cg_rast_params *ps, int n_frames, const cg_jpeg_params *params,
+                               uint8_t *out, size_t cap, size_t *offsets, int chunk, cg_rast_seq_frame *info,
+                               cg_stats *stats);
+
 /* ---- measurement ----------------------------------------------------- */
 /* Live device time of the hot kernels: while on, a start / stop HIP event
  * pair rides on each launch's own dispatch (hipExtLaunchKernel) of
