@@ -97,6 +97,14 @@ class JpegParams(C.Structure):         # cg_jpeg_params
 JPEG_444, JPEG_420 = 0, 2                  # Pillow's subsampling numbers
 
 
+class PngParams(C.Structure):          # cg_png_params
+    _fields_ = [("colour", C.c_int), ("filter", C.c_int)]
+
+
+PNG_RGB, PNG_RGBA = 2, 6                   # PNG's colour types
+PNG_FILTER_ADAPTIVE = -1                   # or a fixed PNG filter type 0 .. 4
+
+
 class RTri(C.Structure):       # rasteriser Triangle, 84 B
     _fields_ = [("v0", Vec4), ("v1", Vec4), ("v2", Vec4), ("normal", Vec4), ("color", Vec3),
                 ("texture", C.c_int), ("index", C.c_int)]
@@ -348,6 +356,20 @@ _SIGS = {
                                              C.POINTER(Stats)]),
     "cg_rast_draw_sequence_jpeg": (C.c_int, [P, C.POINTER(RastParams), C.c_int, C.POINTER(JpegParams), P, C.c_size_t,
                                              C.POINTER(C.c_size_t), C.c_int, C.POINTER(RastSeqFrame), C.POINTER(Stats)]),
+    "cg_image_encode_png_host": (C.c_int, [P, C.c_int, C.c_int, C.c_size_t, C.POINTER(PngParams), P, C.c_size_t,
+                                           C.POINTER(C.c_size_t)]),
+    "cg_image_png_bound": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    "cg_image_png_code_lengths": (C.c_int, [P, C.c_int, C.c_int, P]),
+    "cg_image_png_enc_limits": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "cg_image_encode_png_device": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(PngParams), P,
+                                             C.c_size_t, P, P]),
+    "cg_image_encode_png": (C.c_int, [P, P, C.c_int, C.c_int, C.c_size_t, C.POINTER(PngParams), P, C.c_size_t,
+                                      C.POINTER(C.c_size_t)]),
+    "cg_rt_render_sequence_png": (C.c_int, [P, C.POINTER(Light), C.c_int, C.POINTER(RtCamera), C.c_int,
+                                            C.POINTER(PngParams), P, C.c_size_t, C.POINTER(C.c_size_t), C.c_int,
+                                            C.POINTER(Stats)]),
+    "cg_rast_draw_sequence_png": (C.c_int, [P, C.POINTER(RastParams), C.c_int, C.POINTER(PngParams), P, C.c_size_t,
+                                            C.POINTER(C.c_size_t), C.c_int, C.POINTER(RastSeqFrame), C.POINTER(Stats)]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -947,6 +969,52 @@ def image_encode_jpeg_host(argb, quality=75, subsampling=JPEG_420) -> bytes:
     return _jpeg_encode(load().cg_image_encode_jpeg_host, "cg_image_encode_jpeg_host", argb, quality, subsampling)
 
 
+def image_png_bound(width, height, colour=PNG_RGB) -> int:
+    """cg_image_png_bound: a length no PNG file of the size can exceed (host-only)."""
+    n = load().cg_image_png_bound(width, height, colour)
+    if n < 0:
+        raise ValueError(f"cg_image_png_bound({width}, {height}, {colour}) failed ({n})")
+    return n
+
+
+def image_png_enc_limits():
+    """cg_image_png_enc_limits: (lanes of a band workgroup, bytes of a band's bit string it holds in LDS)."""
+    t, b = C.c_int(), C.c_int()
+    load().cg_image_png_enc_limits(C.byref(t), C.byref(b))
+    return t.value, b.value
+
+
+def image_png_code_lengths(freq, limit) -> np.ndarray:
+    """cg_image_png_code_lengths: the encoder's code lengths (uint8) for frequencies under a length limit."""
+    f = np.ascontiguousarray(freq, dtype=np.uint32)
+    out = np.zeros(max(f.size, 1), np.uint8)
+    rc = load().cg_image_png_code_lengths(f.ctypes.data_as(P), f.size, limit, out.ctypes.data_as(P))
+    if rc != CG_OK:
+        raise ValueError(f"cg_image_png_code_lengths failed ({rc})")
+    return out[:f.size]
+
+
+def _png_encode(fn, what, argb, colour, filter):
+    a = _jpeg_frame(argb)
+    h, w = a.shape
+    prm = PngParams(colour, filter)
+    n = C.c_size_t()
+    out = np.empty(max(4096, w * h), np.uint8)
+    rc = fn(a.ctypes.data_as(P), w, h, 0, C.byref(prm), out.ctypes.data_as(P), out.size, C.byref(n))
+    if rc == CG_E_CAPACITY:
+        out = np.empty(n.value, np.uint8)
+        rc = fn(a.ctypes.data_as(P), w, h, 0, C.byref(prm), out.ctypes.data_as(P), out.size, C.byref(n))
+    if rc != CG_OK:
+        raise ValueError(f"{what} failed ({rc})")
+    return out[:n.value].tobytes()
+
+
+def image_encode_png_host(argb, colour=PNG_RGB, filter=PNG_FILTER_ADAPTIVE) -> bytes:
+    """cg_image_encode_png_host: the PNG file of a uint32 (H, W) ARGB8888 frame under the library's own
+    contract (include/cg_render.h); any PNG decoder returns the pixels (host-only, no GPU)."""
+    return _png_encode(load().cg_image_encode_png_host, "cg_image_encode_png_host", argb, colour, filter)
+
+
 DIST_ID_BYTES = 128   # cg_dist_id (an RCCL unique id)
 DIST_SIGNALLED, DIST_CHUNKED = 0, 1   # cg_dist_set_pipeline
 
@@ -1411,11 +1479,11 @@ class Context:
                     "cg_rt_render_sequence")
         return out, st
 
-    def _sequence_jpeg(self, call, what, n, width, height, quality, subsampling, out, cap):
+    def _sequence_jpeg(self, call, what, n, width, height, quality, subsampling, out, cap, prm=None):
         """A compressed delivery call: `call(params, out pointer, cap, offsets)` -> its status.  Without
         `out` the buffer starts at n * W * H / 4 bytes and the call is repeated once at the capacity it
         asks for.  -> (rc, out, offsets uint64[n + 1])."""
-        prm = JpegParams(quality, subsampling)
+        prm = JpegParams(quality, subsampling) if prm is None else prm
         offsets = np.zeros(n + 1, np.uint64)
         op = C.cast(offsets.ctypes.data, C.POINTER(C.c_size_t))
         own = out is None
@@ -1487,6 +1555,49 @@ class Context:
         if full:
             return rc, files, offsets, info, st
         self._check(rc, "cg_rast_draw_sequence_jpeg")
+        return files, info
+
+    def rt_render_sequence_png(self, cams, lights, colour=PNG_RGB, filter=PNG_FILTER_ADAPTIVE, chunk=0, out=None, cap=None,
+                               full=False):
+        """cg_rt_render_sequence_png: rt_render_sequence's frames as PNG files -> list[bytes]; arguments
+        and full=True as rt_render_sequence_jpeg."""
+        if len(lights) != len(cams):
+            raise ValueError("one light list per frame")
+        if not cams:
+            return ([] if not full else (CG_OK, [], np.zeros(1, np.uint64), Stats()))
+        larr, n = sequence_lights(lights)
+        arr = (RtCamera * len(cams))(*cams)
+        st = Stats()
+        call = lambda prm, o, c, offs: self.lib.cg_rt_render_sequence_png(  # noqa: E731
+            self.h, larr, n, arr, len(cams), prm, o, c, offs, chunk, C.byref(st))
+        rc, buf, offsets = self._sequence_jpeg(call, "cg_rt_render_sequence_png", len(cams), cams[0].width,
+                                               cams[0].height, 0, 0, out, cap, PngParams(colour, filter))
+        size = buf.nbytes if isinstance(buf, np.ndarray) else buf.numel() * buf.element_size()
+        files = self._jpeg_files(rc, buf, offsets, size if cap is None else cap)
+        if full:
+            return rc, files, offsets, st
+        self._check(rc, "cg_rt_render_sequence_png")
+        return files
+
+    def rast_draw_sequence_png(self, params_list, colour=PNG_RGB, filter=PNG_FILTER_ADAPTIVE, chunk=0, out=None, cap=None,
+                               full=False):
+        """cg_rast_draw_sequence_png: rast_draw_sequence's frames as PNG files -> (list[bytes], info);
+        arguments and full=True as rast_draw_sequence_jpeg."""
+        n = len(params_list)
+        arr = (RastParams * max(n, 1))(*params_list)
+        info = np.zeros(n + 1, RAST_SEQ_DTYPE)
+        st = Stats()
+        if not n:
+            return ([], info) if not full else (CG_OK, [], np.zeros(1, np.uint64), info, st)
+        call = lambda prm, o, c, offs: self.lib.cg_rast_draw_sequence_png(  # noqa: E731
+            self.h, arr, n, prm, o, c, offs, chunk, C.cast(info.ctypes.data, C.POINTER(RastSeqFrame)), C.byref(st))
+        rc, buf, offsets = self._sequence_jpeg(call, "cg_rast_draw_sequence_png", n, params_list[0].width,
+                                               params_list[0].height, 0, 0, out, cap, PngParams(colour, filter))
+        size = buf.nbytes if isinstance(buf, np.ndarray) else buf.numel() * buf.element_size()
+        files = self._jpeg_files(rc, buf, offsets, size if cap is None else cap)
+        if full:
+            return rc, files, offsets, info, st
+        self._check(rc, "cg_rast_draw_sequence_png")
         return files, info
 
     def rt_assemble_device(self, d_src, pix_format, row0, rows, width, height, nframes, d_frames, frame_stride=0,
@@ -1701,6 +1812,22 @@ class Context:
                                                          C.byref(prm), P(d_out), slot_bytes, P(d_bytes),
                                                          P(stream) if stream else None),
                     "cg_image_encode_jpeg_device")
+
+    def image_encode_png(self, argb, colour=PNG_RGB, filter=PNG_FILTER_ADAPTIVE) -> bytes:
+        """cg_image_encode_png: image_encode_png_host's file, encoded on this context's GPU."""
+        fn = lambda *a: self.lib.cg_image_encode_png(self.h, *a)   # noqa: E731
+        return _png_encode(fn, "cg_image_encode_png", argb, colour, filter)
+
+    def image_encode_png_device(self, d_argb, width, height, n_frames, d_out, slot_bytes, d_bytes, colour=PNG_RGB,
+                                filter=PNG_FILTER_ADAPTIVE, frame_stride=0, stream=None):
+        """cg_image_encode_png_device: n_frames ARGB8888 frames at the device address d_argb (frame_stride
+        pixels apart; 0: width * height) to PNG files at d_out + f * slot_bytes, their lengths (or
+        CG_E_CAPACITY) to the int64 array d_bytes; enqueued on `stream` (None: the context's)."""
+        prm = PngParams(colour, filter)
+        self._check(self.lib.cg_image_encode_png_device(self.h, P(d_argb), width, height, n_frames, frame_stride,
+                                                        C.byref(prm), P(d_out), slot_bytes, P(d_bytes),
+                                                        P(stream) if stream else None),
+                    "cg_image_encode_png_device")
 
     def load_textures_jpeg(self, directory: str) -> dict:
         """Decode the reference's texture files found in `directory` (names as

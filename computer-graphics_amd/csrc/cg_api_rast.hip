@@ -827,14 +827,18 @@ extern "C" int cg_rast_draw_sequence(cg_ctx *c, const cg_rast_params *ps, int n_
 // they equal cg_rast_draw_sequence's.  A frame the stream's capacity could not hold is repaired
 // after the last chunk as there -- drawn alone from its record -- encoded, and put in its place
 // among the files, which are laid out again behind it.
-extern "C" int cg_rast_draw_sequence_jpeg(cg_ctx *c, const cg_rast_params *ps, int n_frames,
-                                          const cg_jpeg_params *params, uint8_t *out, size_t cap, size_t *offsets,
-                                          int chunk, cg_rast_seq_frame *info, cg_stats *stats)
+// JPEG files under jp, or PNG files under pp (`who` names the call in messages).
+static int rast_sequence_files(cg_ctx *c, const cg_rast_params *ps, int n_frames, const cg_jpeg_params *jp,
+                               const cg_png_params *pp, uint8_t *out, size_t cap, size_t *offsets, int chunk,
+                               cg_rast_seq_frame *info, cg_stats *stats, const char *who)
 {
-    if (!c || !offsets || n_frames < 0 || (n_frames && !ps) || (!out && cap) || !params || params->quality < 1 ||
-        params->quality > 100 || (params->subsampling != CG_JPEG_444 && params->subsampling != CG_JPEG_420))
+    if (!c || !offsets || n_frames < 0 || (n_frames && !ps) || (!out && cap)) return CG_E_INVALID;
+    if (pp ? ((pp->colour != CG_PNG_RGB && pp->colour != CG_PNG_RGBA) ||
+              (pp->filter != CG_PNG_FILTER_ADAPTIVE && (pp->filter < 0 || pp->filter > 4)))
+           : (!jp || jp->quality < 1 || jp->quality > 100 || (jp->subsampling != CG_JPEG_444 && jp->subsampling != CG_JPEG_420)))
         return CG_E_INVALID;
-    if (chunk < 0 || chunk > 64) return ctx_invalid(c, "draw_sequence_jpeg: chunk 0 .. 64");
+    const std::string name(who);
+    if (chunk < 0 || chunk > 64) return ctx_invalid(c, (name + ": chunk 0 .. 64").c_str());
     if (c->n_room < 0) {
         c->err = "draw before cg_rast_set_scene";
         return CG_E_NOSCENE;
@@ -842,11 +846,11 @@ extern "C" int cg_rast_draw_sequence_jpeg(cg_ctx *c, const cg_rast_params *ps, i
     offsets[0] = 0;
     if (n_frames == 0) return CG_OK;
     const int W = ps[0].width, H = ps[0].height;
-    if (W <= 2 || H <= 2 || W > 65535 || H > 65535) return ctx_invalid(c, "draw_sequence_jpeg: frame size");
+    if (W <= 2 || H <= 2 || W > 65535 || H > 65535) return ctx_invalid(c, (name + ": frame size").c_str());
     const size_t px = (size_t)W * H;
     for (int f = 0; f < n_frames; ++f)
         if (ps[f].colour_mode < 0 || ps[f].colour_mode > 2 || ps[f].width != W || ps[f].height != H)
-            return ctx_invalid(c, "draw_sequence_jpeg: colour modes 0-2, frames of one size");
+            return ctx_invalid(c, (name + ": colour modes 0-2, frames of one size").c_str());
     auto t0 = std::chrono::steady_clock::now();
     CG_TRY(c, hipSetDevice(c->device), "hipSetDevice");
     const int ch = std::min(chunk ? chunk : 8, n_frames);
@@ -862,7 +866,8 @@ extern "C" int cg_rast_draw_sequence_jpeg(cg_ctx *c, const cg_rast_params *ps, i
             (void)hipStreamSynchronize(c->stream);
         }
     } drain_on_exit{c};
-    JpegDelivery D{c, W, H, n_frames, ch, *params, out, cap, offsets};
+    JpegDelivery D{c, W, H, n_frames, ch, jp ? *jp : cg_jpeg_params{}, out, cap, offsets};
+    if (pp) D.png = true, D.pprm = *pp;
     if (int rc = D.begin()) return rc;
     for (int k = 0; k < 2; ++k) CG_TRY(c, c->rs_argb[k].ensure((size_t)ch * px * sizeof(uint32_t)), "alloc frame slots");
     const size_t rec_bytes = ((size_t)n_frames + 1) * sizeof(cg_rast_seq_frame);
@@ -923,8 +928,10 @@ extern "C" int cg_rast_draw_sequence_jpeg(cg_ctx *c, const cg_rast_params *ps, i
                 p.rand_offset = rec[f].rand_offset;
                 int rc = cg_rast_draw(c, &p, frame.data(), nullptr, nullptr, nullptr);
                 if (rc) return rc;
-                file.resize((size_t)cg_image_jpeg_bound(W, H, params->subsampling));
-                if ((rc = cg_image_encode_jpeg(c, frame.data(), W, H, 0, params, file.data(), file.size(), &len))) return rc;
+                file.resize((size_t)(pp ? cg_image_png_bound(W, H, pp->colour) : cg_image_jpeg_bound(W, H, jp->subsampling)));
+                if ((rc = pp ? cg_image_encode_png(c, frame.data(), W, H, 0, pp, file.data(), file.size(), &len)
+                             : cg_image_encode_jpeg(c, frame.data(), W, H, 0, jp, file.data(), file.size(), &len)))
+                    return rc;
                 src = file.data();
                 rec[f].status = 0;
             } else if (rec[f].status != 0) {
@@ -948,6 +955,21 @@ extern "C" int cg_rast_draw_sequence_jpeg(cg_ctx *c, const cg_rast_params *ps, i
         stats->n_shaded = shaded;
     }
     return rc_out;
+}
+
+extern "C" int cg_rast_draw_sequence_jpeg(cg_ctx *c, const cg_rast_params *ps, int n_frames,
+                                          const cg_jpeg_params *params, uint8_t *out, size_t cap, size_t *offsets,
+                                          int chunk, cg_rast_seq_frame *info, cg_stats *stats)
+{
+    return rast_sequence_files(c, ps, n_frames, params, nullptr, out, cap, offsets, chunk, info, stats, "draw_sequence_jpeg");
+}
+
+extern "C" int cg_rast_draw_sequence_png(cg_ctx *c, const cg_rast_params *ps, int n_frames, const cg_png_params *params,
+                                         uint8_t *out, size_t cap, size_t *offsets, int chunk, cg_rast_seq_frame *info,
+                                         cg_stats *stats)
+{
+    if (!params) return CG_E_INVALID;
+    return rast_sequence_files(c, ps, n_frames, nullptr, params, out, cap, offsets, chunk, info, stats, "draw_sequence_png");
 }
 
 // ---- the float picture (CG_PIX_RGBA_F32) and exposed frames (kernels: the post-pass's *_f32

@@ -523,6 +523,7 @@ static int rt_render_frames_host(cg_ctx *c, const cg_light *lights, int n_lights
 int JpegDelivery::begin()
 {
     slot_bytes = (size_t)W * H;   // a frame's device slot: a file this long is rare and is encoded again alone
+    if (png) slot_bytes = (size_t)cg_image_png_bound(W, H, pprm.colour);   // exact frames: no file is longer
     CG_TRY(c, c->xfer.ensure(hipStreamNonBlocking), "copy stream");
     for (int k = 0; k < 2; ++k) {
         CG_TRY(c, c->jpeg_rdone[k].ensure(), "copy event");
@@ -548,8 +549,10 @@ int JpegDelivery::encode(int j, const uint32_t *d_frames, size_t frame_stride)
     fstride[s] = frame_stride;
     uint8_t *base = (uint8_t *)c->jpeg_out[s].p;
     const size_t lens_b = 256 * (((size_t)ch * 8 + 255) / 256);
-    if (int rc = cg_image_encode_jpeg_device(c, d_frames, W, H, nf, frame_stride, &prm, base + lens_b, slot_bytes,
-                                             (int64_t *)base, c->stream))
+    if (int rc = png ? cg_image_encode_png_device(c, d_frames, W, H, nf, frame_stride, &pprm, base + lens_b, slot_bytes,
+                                                  (int64_t *)base, c->stream)
+                     : cg_image_encode_jpeg_device(c, d_frames, W, H, nf, frame_stride, &prm, base + lens_b, slot_bytes,
+                                                   (int64_t *)base, c->stream))
         return rc;
     CG_TRY(c, hipEventRecord(c->jpeg_rdone[s], c->stream), "encode event");
     return CG_OK;
@@ -567,7 +570,7 @@ int JpegDelivery::deliver(int j)
     for (int f = 0; f < nf; ++f) {
         int64_t len = h_len[f];
         const uint8_t *src = base + lens_b + (size_t)f * slot_bytes;
-        const bool again = len == CG_E_CAPACITY;
+        const bool again = len == CG_E_CAPACITY && !png;
         if (again) {   // longer than W * H bytes: alone, into a slot no file can exceed, behind what the stream holds
             const size_t bound = (size_t)cg_image_jpeg_bound(W, H, prm.subsampling);
             CG_TRY(c, c->jpeg_big.ensure(256 + bound), "alloc file slot");
@@ -603,14 +606,21 @@ static bool jpeg_params_ok(const cg_jpeg_params *p)
     return p && p->quality >= 1 && p->quality <= 100 && (p->subsampling == CG_JPEG_444 || p->subsampling == CG_JPEG_420);
 }
 
-// cg_rt_render_sequence's chunks (rt_render_frames_host above), each encoded on the context's stream
-// behind its render; chunk j's files are copied while chunk j + 1 renders.
-extern "C" int cg_rt_render_sequence_jpeg(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
-                                          int n_frames, const cg_jpeg_params *params, uint8_t *out, size_t cap,
-                                          size_t *offsets, int chunk, cg_stats *stats)
+static bool png_params_ok(const cg_png_params *p)
 {
-    if (!c || !offsets || n_frames < 0 || (n_frames && !cams) || chunk < 0 || (!out && cap) || !jpeg_params_ok(params) ||
-        n_lights < 0 || n_lights > kMaxLights || (n_lights && !lights))
+    return p && (p->colour == CG_PNG_RGB || p->colour == CG_PNG_RGBA) &&
+           (p->filter == CG_PNG_FILTER_ADAPTIVE || (p->filter >= 0 && p->filter <= 4));
+}
+
+// cg_rt_render_sequence's chunks (rt_render_frames_host above), each encoded on the context's stream
+// behind its render; chunk j's files are copied while chunk j + 1 renders.  JPEG files under jp, or
+// PNG files under pp.
+static int rt_sequence_files(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams, int n_frames,
+                             const cg_jpeg_params *jp, const cg_png_params *pp, uint8_t *out, size_t cap, size_t *offsets,
+                             int chunk, cg_stats *stats)
+{
+    if (!c || !offsets || n_frames < 0 || (n_frames && !cams) || chunk < 0 || (!out && cap) ||
+        (pp ? !png_params_ok(pp) : !jpeg_params_ok(jp)) || n_lights < 0 || n_lights > kMaxLights || (n_lights && !lights))
         return CG_E_INVALID;
     offsets[0] = 0;
     if (n_frames == 0) return CG_OK;
@@ -629,7 +639,8 @@ extern "C" int cg_rt_render_sequence_jpeg(cg_ctx *c, const cg_light *lights, int
             (void)hipStreamSynchronize(c->stream);
         }
     } drain_on_exit{c};
-    JpegDelivery D{c, W, H, n_frames, ch, *params, out, cap, offsets};
+    JpegDelivery D{c, W, H, n_frames, ch, jp ? *jp : cg_jpeg_params{}, out, cap, offsets};
+    if (pp) D.png = true, D.pprm = *pp;
     if (int rc = D.begin()) return rc;
     const size_t spx = (size_t)cg_rt_shard_rows(H, nullptr) * W;
     for (int k = 0; k < 2; ++k) CG_TRY(c, c->hslot[k].ensure((size_t)ch * spx * sizeof(uint32_t)), "alloc frame slots");
@@ -660,4 +671,19 @@ extern "C" int cg_rt_render_sequence_jpeg(cg_ctx *c, const cg_light *lights, int
         stats->n_shaded = -1;
     }
     return rc;
+}
+
+extern "C" int cg_rt_render_sequence_jpeg(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
+                                          int n_frames, const cg_jpeg_params *params, uint8_t *out, size_t cap,
+                                          size_t *offsets, int chunk, cg_stats *stats)
+{
+    return rt_sequence_files(c, lights, n_lights, cams, n_frames, params, nullptr, out, cap, offsets, chunk, stats);
+}
+
+extern "C" int cg_rt_render_sequence_png(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
+                                         int n_frames, const cg_png_params *params, uint8_t *out, size_t cap,
+                                         size_t *offsets, int chunk, cg_stats *stats)
+{
+    if (!params) return CG_E_INVALID;
+    return rt_sequence_files(c, lights, n_lights, cams, n_frames, nullptr, params, out, cap, offsets, chunk, stats);
 }

@@ -57,6 +57,8 @@ enum {
     kBufOwner = 40, kBufClipPre, kBufScreen, kBufLow, kBufHigh, kBufClipId, kBufTriId, kBufPos, kBufPick, kBufOwnerEnd
 };
 void *ctx_buf(cg_ctx *c, int which, size_t bytes, hipError_t *e);
+// cg_png_enc.hip's two: 0 a chunk's filtered rows and staged bands, 1 the host form's frame and file
+void *ctx_png_buf(cg_ctx *c, int which, size_t bytes, hipError_t *e);
 int ctx_device(const cg_ctx *c);
 hipStream_t ctx_stream(const cg_ctx *c);
 void ctx_events(cg_ctx *c, hipEvent_t *a, hipEvent_t *b);

@@ -247,7 +247,9 @@ enum KtId {
     // its colour modes 1-2: segments + count + scans, the generator, number + shade
     KT_RAST_BIG_COUNT, KT_RAST_BIG_RAND, KT_RAST_BIG_SHADE,
     // a hits-only pass of the large-scene path: a scope over it, its walk, its gather
-    KT_RT_HITS_PASS, KT_RT_HITS_WALK, KT_RT_HITS_GATHER, KT_COUNT
+    KT_RT_HITS_PASS, KT_RT_HITS_WALK, KT_RT_HITS_GATHER,
+    // the PNG encoder's four kernels (cg_png_enc.hip)
+    KT_PNG_FILTER, KT_PNG_BAND, KT_PNG_SCAN, KT_PNG_GATHER, KT_COUNT
 };
 // HIP events on `st` around the scope's launches while timing is on (id
 // outside [0, KT_COUNT): nothing).

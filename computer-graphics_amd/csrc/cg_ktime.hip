@@ -26,6 +26,7 @@ static const char *const kKtNames[KT_COUNT] = {
     "rast_big_count",           "rast_big_rand",         "rast_big_shade",
     // a hits-only pass (cg_rt_hits_device) on a large scene: the whole pass, its walk, its gather
     "rt_hits_pass",             "rt_hits_walk",          "rt_hits_gather",
+    "png_enc_filter_kernel",    "png_enc_band_kernel",   "png_enc_scan_kernel",     "png_enc_gather_kernel",
 };
 
 namespace {

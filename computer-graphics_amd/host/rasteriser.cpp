@@ -20,6 +20,7 @@
 //              [--auto-exposure PERMILLE[,TARGET]] [--tonemap linear|reinhard|reinhard-white:W]
 //              [--bloom THRESHOLD,INTENSITY[,LEVELS[,CAP]]]
 //              [--jpeg FILE [--quality 1..100] [--subsampling 444|420]]
+//              [--png FILE [--png-colour rgb|rgba] [--png-filter adaptive|0..4]]
 //
 // --batch: Update() runs over the whole key script first, each frame's globals
 // are recorded as a cg_rast_params, and one cg_rast_draw_sequence call renders
@@ -43,6 +44,10 @@
 // quality 75 and 4:2:0 unless --quality / --subsampling say otherwise).  With --batch, every frame of
 // the run, the files one after the other (a motion-JPEG stream): through cg_rast_draw_sequence_jpeg,
 // or with the exposure flags each exposed frame through the encoder.
+// --png FILE: the frame --out writes, as a lossless PNG encoded on the device (cg_image_encode_png; RGB
+// and adaptive filters unless --png-colour / --png-filter say otherwise): it decodes to exactly the
+// pixels of --out.  With --batch, also frame k of the run as FILE with .%04d before its extension:
+// through cg_rast_draw_sequence_png, or with the exposure flags each exposed frame through the encoder.
 #include <cmath>
 #include <cstring>
 #include <fstream>
@@ -54,6 +59,7 @@
 #include "bloom_arg.h"
 #include "cg_render.h"
 #include "jpeg_arg.h"
+#include "png_arg.h"
 
 using namespace std;
 using glm::mat4;
@@ -217,6 +223,7 @@ int main(int argc, char *argv[])
     cg_hdr_bloom_params bloom{4, 1.0f, 64.0f, 0.25f};          // --bloom: levels and cap unless given
     JpegArg jpeg;                                              // --jpeg: quality 75, 4:2:0 unless given
     vector<uint8_t> jpeg_bytes;
+    PngArg png;                                                // --png: RGB, adaptive filters unless given
     for (int i = 1; i < argc; i += 2) {
         string a = argv[i];
         if (a == "--batch") {
@@ -233,11 +240,22 @@ int main(int argc, char *argv[])
                 cerr << JPEG_USAGE << endl;
                 return 1;
             }
+            if (ParsePngArg(a, nullptr, &png)) {
+                cerr << PNG_USAGE << endl;
+                return 1;
+            }
             break;
         }
         if (const int j = ParseJpegArg(a, argv[i + 1], &jpeg)) {
             if (j < 0) {
                 cerr << JPEG_USAGE << endl;
+                return 1;
+            }
+            continue;
+        }
+        if (const int j = ParsePngArg(a, argv[i + 1], &png)) {
+            if (j < 0) {
+                cerr << PNG_USAGE << endl;
                 return 1;
             }
             continue;
@@ -345,11 +363,25 @@ int main(int argc, char *argv[])
                         ps.size(), screen->width, screen->height, &jpeg_bytes);
                     if (rc) die(rc, "cg_rast_draw_sequence_jpeg");
                 }
+                if (!png.path.empty() && batch) {   // the same frames again, delivered exact
+                    rc = PngDeliver(
+                        [&](uint8_t *o, size_t cap, size_t *offsets) {
+                            return cg_rast_draw_sequence_png(g_ctx, ps.data(), (int)ps.size(), &png.params, o, cap, offsets,
+                                                             0, nullptr, nullptr);
+                        },
+                        ps.size(), screen->width, screen->height, png.path);
+                    if (rc) die(rc, "cg_rast_draw_sequence_png");
+                }
             }
             if (!jpeg.path.empty() && batch && exposed) {
                 rc = JpegEncodeFrames(g_ctx, frames.data(), ps.size(), screen->width, screen->height, jpeg.params,
                                       &jpeg_bytes);
                 if (rc) die(rc, "cg_image_encode_jpeg");
+            }
+            if (!png.path.empty() && batch && exposed) {
+                rc = PngEncodeFrames(g_ctx, frames.data(), ps.size(), screen->width, screen->height, png.params,
+                                     [&](size_t f) { return PngFramePath(png.path, f); });
+                if (rc) die(rc, "cg_image_encode_png");
             }
             randCalls = info.back().rand_offset;
             g_last = ps.back();                               // the last frame, at its chained index
@@ -374,6 +406,11 @@ int main(int argc, char *argv[])
             cerr << "cannot write " << jpeg.path << endl;
             return 1;
         }
+    }
+    if (!png.path.empty() && g_drawn) {   // the frame the screenshot holds
+        rc = PngEncodeFrames(g_ctx, screen->buffer, 1, screen->width, screen->height, png.params,
+                             [&](size_t) { return png.path; });
+        if (rc) die(rc, "cg_image_encode_png");
     }
     if (!pfm.empty() && g_drawn) SavePicturePFM(pfm.c_str());
     KillSDL(screen);

@@ -445,8 +445,80 @@ int main(int argc, char **argv)
             cg_image_jpeg_bound(1, 1, 1) != CG_E_INVALID || cg_image_jpeg_bound(65535, 65535, CG_JPEG_444) <= 0)
             fail("jpeg encoder refusals", -1);
     }
+    // the PNG encoder's host-only entries the same way: tiny sizes around a band of 16 rows, both
+    // colours, adaptive and fixed filters, noise (stored bands) and runs (matches), a row stride, the
+    // length query with no buffer, every capacity on the smallest and one byte short on the others;
+    // then the code-length rule at both limits
+    int png_encoded = 0;
+    {
+        const int sizes[][2] = {{1, 1}, {2, 1}, {1, 2}, {5, 15}, {5, 16}, {5, 17}, {7, 33}, {70, 3}};
+        uint32_t seed = 54321u;
+        for (const auto &sz : sizes)
+            for (int colour : {CG_PNG_RGB, CG_PNG_RGBA})
+                for (int filter : {CG_PNG_FILTER_ADAPTIVE, 0, 4})
+                    for (int noisy : {0, 1}) {
+                        const int W = sz[0], H = sz[1];
+                        const size_t stride = (size_t)W + 3;
+                        std::vector<uint32_t> px(stride * H);   // exactly H rows
+                        for (size_t i = 0; i < px.size(); ++i)
+                            px[i] = noisy ? (seed = seed * 1103515245u + 12345u) : 0x01010101u * (uint32_t)(i / 23);
+                        const cg_png_params prm{colour, filter};
+                        size_t need = 0, n = 0;
+                        if (cg_image_encode_png_host(px.data(), W, H, stride, &prm, nullptr, 0, &need) != CG_E_CAPACITY || !need)
+                            fail("cg_image_encode_png_host length query", W);
+                        if ((long long)need > cg_image_png_bound(W, H, colour)) fail("cg_image_png_bound", (int)need);
+                        std::vector<uint8_t> file(need);
+                        if (int rc = cg_image_encode_png_host(px.data(), W, H, stride, &prm, file.data(), need, &n))
+                            fail("cg_image_encode_png_host", rc);
+                        if (n != need || memcmp(file.data(), "\x89PNG\r\n\x1a\n", 8)) fail("the encoded PNG", (int)n);
+                        for (size_t cap = W * H <= 2 ? 0 : need - 1; cap < need; ++cap) {
+                            std::vector<uint8_t> part(cap);
+                            if (cg_image_encode_png_host(px.data(), W, H, stride, &prm, part.data(), cap, &n) != CG_E_CAPACITY ||
+                                n != need || (cap && memcmp(part.data(), file.data(), cap)))
+                                fail("cg_image_encode_png_host capacity", (int)cap);
+                        }
+                        ++png_encoded;
+                    }
+        // Fibonacci frequencies run the limiter; exactly n entries are read and written
+        for (int limit : {15, 7})
+            for (int n : {1, 2, 19, 30, 286}) {
+                std::vector<uint32_t> freq((size_t)n);
+                uint32_t a = 1, b = 1;
+                for (int i = 0; i < n; ++i) {
+                    freq[(size_t)i] = i < 40 ? a : 1u + (uint32_t)i % 3u;
+                    const uint32_t c = a + b;
+                    a = b, b = c;
+                }
+                std::vector<uint8_t> len((size_t)n);
+                const int rc = cg_image_png_code_lengths(freq.data(), n, limit, len.data());
+                if (n > (1 << limit) ? rc != CG_E_INVALID : rc != CG_OK) fail("cg_image_png_code_lengths", n);
+                unsigned long long kraft = 0;
+                for (int i = 0; i < n && !rc; ++i) {
+                    if (!len[(size_t)i] || len[(size_t)i] > limit) fail("a code length", i);
+                    kraft += 1ull << (limit - len[(size_t)i]);
+                }
+                if (!rc && n > 1 && kraft != 1ull << limit) fail("the Kraft sum", n);
+            }
+        const cg_png_params ok{CG_PNG_RGB, CG_PNG_FILTER_ADAPTIVE}, bad_c{4, 0}, bad_f{CG_PNG_RGB, 5};
+        uint32_t one = 0;
+        uint8_t byte = 0;
+        size_t n = 0;
+        if (cg_image_encode_png_host(&one, 0, 1, 0, &ok, &byte, 1, &n) != CG_E_INVALID ||
+            cg_image_encode_png_host(&one, 1, 65536, 0, &ok, &byte, 1, &n) != CG_E_INVALID ||
+            cg_image_encode_png_host(&one, 1, 1, 0, &bad_c, &byte, 1, &n) != CG_E_INVALID ||
+            cg_image_encode_png_host(&one, 1, 1, 0, &bad_f, &byte, 1, &n) != CG_E_INVALID ||
+            cg_image_encode_png_host(nullptr, 1, 1, 0, &ok, &byte, 1, &n) != CG_E_INVALID ||
+            cg_image_encode_png_host(&one, 1, 1, 0, &ok, nullptr, 1, &n) != CG_E_INVALID ||
+            cg_image_encode_png_host(&one, 1, 1, 0, &ok, &byte, 1, nullptr) != CG_E_INVALID ||
+            cg_image_encode_png_host(&one, 2, 1, 1, &ok, &byte, 1, &n) != CG_E_INVALID ||
+            cg_image_png_code_lengths(nullptr, 1, 15, &byte) != CG_E_INVALID ||
+            cg_image_png_code_lengths(&one, 1, 16, &byte) != CG_E_INVALID || cg_image_png_bound(0, 1, CG_PNG_RGB) != CG_E_INVALID ||
+            cg_image_png_bound(1, 1, 3) != CG_E_INVALID || cg_image_png_bound(65535, 65535, CG_PNG_RGBA) <= 0)
+            fail("png encoder refusals", -1);
+    }
     const int malformed = malformed_jpegs();
-    printf("sanitized host code: %d JPEGs, %d malformed JPEGs rejected, %d JPEGs encoded, %ld clipped triangles, clean\n",
-           checked, malformed, encoded, tris);
+    printf("sanitized host code: %d JPEGs, %d malformed JPEGs rejected, %d JPEGs encoded, %d PNGs encoded, "
+           "%ld clipped triangles, clean\n",
+           checked, malformed, encoded, png_encoded, tris);
     return 0;
 }

@@ -1113,6 +1113,107 @@ int cg_rast_draw_sequence_jpeg(cg_ctx *ctx, const cg_rast_params *ps, int n_fram
                                uint8_t *out, size_t cap, size_t *offsets, int chunk, cg_rast_seq_frame *info,
                                cg_stats *stats);
 
+/* ---- PNG encoding ------------------------------------------------------- */
+/* A lossless PNG encoder for ARGB8888 frames: 8-bit samples, no interlace, the chunks IHDR, IDAT
+ * (one per band) and IEND and no other.  Any PNG decoder returns the input pixels.  The bytes are
+ * this library's own -- an LZ77 parse over the whole image, as zlib makes it, is one serial pass
+ * -- and are fixed by the rules below, all integer arithmetic; the host function and the kernels
+ * share them (csrc/cg_png_enc.h) and produce the same file.
+ *
+ * 1 Samples   colour CG_PNG_RGB (colour type 2): a pixel's bytes are bits 16-23, 8-15, 0-7 (R, G,
+ *             B), bits 24-31 are ignored; CG_PNG_RGBA (colour type 6): bits 24-31 follow as A.  bpp
+ *             = 3 or 4.
+ * 2 Filters   Per row, PNG's types 0 None, 1 Sub, 2 Up, 3 Average ((a + b) >> 1), 4 Paeth, with a
+ *             the byte bpp to the left, b the byte above, c the byte above a; bytes outside the
+ *             image are 0.  Paeth: p = a + b - c, pa = |p - a|, pb = |p - b|, pc = |p - c|; a if
+ *             pa <= pb and pa <= pc, else b if pb <= pc, else c.  filter 0 .. 4 uses that type for
+ *             every row; CG_PNG_FILTER_ADAPTIVE gives a row the type whose filtered bytes, read as
+ *             int8, have the smallest sum of absolute values (-128 counts 128), the lowest type on
+ *             a tie.  A filtered row is its type byte and W * bpp bytes.
+ * 3 Bands     Rows 16 k .. 16 k + 15 (fewer in the last) are band k.  A band's filtered rows, back
+ *             to back, are compressed alone and are one IDAT chunk.
+ * 4 Tokens    Within a band, a maximal run of n equal bytes (runs cross rows) with n < 4 is n
+ *             literals.  With n >= 4 it is one literal, then matches of length 258 and distance 1
+ *             while at least 258 bytes of the run remain, then one match of the remainder r if r
+ *             >= 3, else r literals.
+ * 5 Lengths   A code's lengths come from frequencies f and a limit L: the symbols with f > 0
+ *             sorted by (f, symbol); a Huffman merge over two queues -- the sorted leaves and the
+ *             internal nodes in the order made -- that takes the leaf when a leaf and a node weigh
+ *             the same; count[d] = the leaves at depth d, depths above L counted at L; while the
+ *             Kraft sum (count[d] * 2^(L - d) over d) exceeds 2^L: with d the largest depth below
+ *             L that has a leaf, count[d] -= 1, count[d + 1] += 2, count[L] -= 1 (the sum falls by
+ *             one); then the sorted symbols take their lengths in order, count[L] of them L, the
+ *             next count[L - 1] of them L - 1, and so on.  Two or more symbols give a complete
+ *             code; one symbol gets length 1.  Codes are canonical (RFC 1951 3.2.2).
+ * 6 Block     One dynamic block per band.  Literal/length code: f from the band's tokens plus one
+ *             end-of-block, L = 15; HLIT covers the highest used symbol (at least 257).  Distance
+ *             code: HDIST = 2, both lengths 1, so distance 1 is the single bit 0.  The HLIT lengths
+ *             and the two distance lengths are one sequence, coded from the left: a run of r zeros
+ *             sends symbol 18 (min(r, 138)) while r >= 11, then 17 (r) if r >= 3, else r zeros; a
+ *             run of r lengths v > 0 sends v, then 16 (min(rest, 6)) while the rest is >= 3, then
+ *             the rest as v.  Code-length code: f from that sequence, L = 7; HCLEN ends at the last
+ *             length other than 0 in the order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15 (at
+ *             least 4).
+ * 7 Stored    If the dynamic block's bits (3 + 14 + 3 HCLEN + the coded lengths + the tokens + the
+ *             end-of-block) are not fewer than 8 n + 40 ceil(n / 65535) for the band's n bytes, the
+ *             band is stored blocks of 65535 bytes, the last shorter.
+ * 8 Stream    The first chunk's data begins 78 01.  A band that is not the last is followed by an
+ *             empty stored block (000, zero bits to the byte, 00 00 FF FF), so every chunk is whole
+ *             bytes; the last band's last block has BFINAL set, is padded with zero bits and is
+ *             followed by the Adler-32 of all filtered bytes, most significant byte first. */
+#define CG_PNG_RGB 2
+#define CG_PNG_RGBA 6
+#define CG_PNG_FILTER_ADAPTIVE (-1)
+typedef struct { int colour; int filter; } cg_png_params;
+/* Host-only (no device, no context).  cg_image_encode_png_host: as cg_image_encode_jpeg_host --
+ * the file into out[0 .. cap), its length into *n, CG_E_CAPACITY with *n = the length needed when
+ * cap is short (no byte at or past cap is written; out may be NULL with cap 0).
+ * cg_image_png_bound: a length no file of the size can exceed: 8 + 25 + 12 bytes of signature,
+ * IHDR and IEND, 2 + 4 of zlib header and Adler-32, and per band of n bytes 12 of chunk, n + 5
+ * ceil(n / 65535) stored, 5 of empty block after all but the last; a frame whose bands are all
+ * stored is exactly that long.  cg_image_png_code_lengths: rule 5 alone, lengths[0 .. n) from
+ * freq[0 .. n), n <= 286, limit 1 .. 15, at most 2^limit used symbols, frequencies summing below
+ * 2^32.  cg_image_png_enc_limits: the lanes of a band workgroup (the bytes of a band it takes at a
+ * time) and the bytes of a band's bit string it holds in LDS.  CG_E_INVALID for a width or height
+ * outside 1 .. 65535, another colour or filter, NULL pointers. */
+int cg_image_encode_png_host(const uint32_t *argb, int width, int height, size_t row_stride_pixels,
+                             const cg_png_params *params, uint8_t *out, size_t cap, size_t *n);
+long long cg_image_png_bound(int width, int height, int colour);
+int cg_image_png_code_lengths(const uint32_t *freq, int n, int limit, uint8_t *lengths);
+int cg_image_png_enc_limits(int *threads, int *window_bytes);
+/* n_frames frames in device memory, with cg_image_encode_jpeg_device's conventions: enqueued on
+ * `stream` (NULL: the context's) without a host wait; frame f is read at d_argb + f * frame_stride
+ * pixels (0: width * height), its file goes to d_out + f * slot_bytes and its length to d_bytes[f]
+ * (8-byte aligned), or CG_E_CAPACITY there when the file is longer than slot_bytes: then nothing
+ * is written to that slot, and the other frames are unaffected.  Nothing is written past a file's
+ * last byte.  The filtered rows and staged bands of up to 8 frames live in grow-only scratch the
+ * context owns, one set per context: calls on one context must be ordered among themselves; calls
+ * on different contexts are independent.  After the first call of a size it does not allocate.
+ * n_frames == 0 returns CG_OK and touches nothing. */
+int cg_image_encode_png_device(cg_ctx *ctx, const uint32_t *d_argb, int width, int height, int n_frames,
+                               size_t frame_stride, const cg_png_params *params, uint8_t *d_out, size_t slot_bytes,
+                               int64_t *d_bytes, void *stream);
+/* One frame in host memory through the device encoder, arguments as cg_image_encode_png_host;
+ * waits for the file. */
+int cg_image_encode_png(cg_ctx *ctx, const uint32_t *argb, int width, int height, size_t row_stride_pixels,
+                        const cg_png_params *params, uint8_t *out, size_t cap, size_t *n);
+/* Frame sequences delivered into host memory exact: cg_rt_render_sequence_jpeg's and
+ * cg_rast_draw_sequence_jpeg's arguments and behaviour with PNG files -- chunks of `chunk` frames
+ * (0: 8, at most 64) are encoded on the device behind their render into slots of
+ * cg_image_png_bound, so no file is encoded twice, and exactly a chunk's file bytes are copied
+ * into `out` back to back while the next chunk renders.  offsets[f] .. offsets[f + 1] is frame
+ * f's file, which decodes to the frame cg_rt_render_sequence / cg_rast_draw_sequence delivers (all
+ * 32 bits of it with CG_PNG_RGBA).  If `out` (cap bytes) is short the call returns CG_E_CAPACITY:
+ * the files that fit whole before the first that does not are intact, nothing is written past
+ * cap, and offsets[n_frames] is the capacity a second call needs.  The rasteriser's rand() index
+ * chain and `info` records equal cg_rast_draw_sequence's. */
+int cg_rt_render_sequence_png(cg_ctx *ctx, const cg_light *lights, int n_lights, const cg_rt_camera *cams, int n_frames,
+                              const cg_png_params *params, uint8_t *out, size_t cap, size_t *offsets, int chunk,
+                              cg_stats *stats);
+int cg_rast_draw_sequence_png(cg_ctx *ctx, const cg_rast_params *ps, int n_frames, const cg_png_params *params,
+                              uint8_t *out, size_t cap, size_t *offsets, int chunk, cg_rast_seq_frame *info,
+                              cg_stats *stats);
+
 /* ---- measurement ----------------------------------------------------- */
 /* Live device time of the hot kernels: while on, a start / stop HIP event
  * pair rides on each launch's own dispatch (hipExtLaunchKernel) of
@@ -1122,7 +1223,8 @@ int cg_rast_draw_sequence_jpeg(cg_ctx *ctx, const cg_rast_params *ps, int n_fram
  * rast_fill_kernel and rast_post_kernel, on the stream it runs on, plus
  * "rt_big_frame" (a large scene's whole frame: events recorded around it) and, for a large scene's
  * hits-only pass (cg_rt_hits_device), "rt_hits_pass" (the whole pass), "rt_hits_walk" and
- * "rt_hits_gather".  cg_kernel_timing(on)
+ * "rt_hits_gather", and the PNG encoder's png_enc_filter_kernel, png_enc_band_kernel,
+ * png_enc_scan_kernel and png_enc_gather_kernel.  cg_kernel_timing(on)
  * resets the totals (process-wide); cg_kernel_time waits for the recorded
  * launches and returns one kernel's summed launch milliseconds, its busy
  * milliseconds (the union of its launches' spans: launches that overlap on
