@@ -105,6 +105,15 @@ PNG_RGB, PNG_RGBA = 2, 6                   # PNG's colour types
 PNG_FILTER_ADAPTIVE = -1                   # or a fixed PNG filter type 0 .. 4
 
 
+class ExrParams(C.Structure):          # cg_exr_params
+    _fields_ = [("channels", C.c_int), ("type", C.c_int), ("compression", C.c_int), ("alpha_scale", C.c_float)]
+
+
+EXR_RGB, EXR_RGBA = 3, 4                   # the channels of an EXR file
+EXR_HALF, EXR_FLOAT = 1, 2                 # OpenEXR's pixel types
+EXR_NONE, EXR_ZIP = 0, 3                   # OpenEXR's compression numbers
+
+
 class RTri(C.Structure):       # rasteriser Triangle, 84 B
     _fields_ = [("v0", Vec4), ("v1", Vec4), ("v2", Vec4), ("normal", Vec4), ("color", Vec3),
                 ("texture", C.c_int), ("index", C.c_int)]
@@ -369,6 +378,21 @@ _SIGS = {
                                             C.POINTER(PngParams), P, C.c_size_t, C.POINTER(C.c_size_t), C.c_int,
                                             C.POINTER(Stats)]),
     "cg_rast_draw_sequence_png": (C.c_int, [P, C.POINTER(RastParams), C.c_int, C.POINTER(PngParams), P, C.c_size_t,
+                                            C.POINTER(C.c_size_t), C.c_int, C.POINTER(RastSeqFrame), C.POINTER(Stats)]),
+    "cg_image_encode_exr_host": (C.c_int, [P, C.c_int, C.c_int, C.c_size_t, C.POINTER(ExrParams), P, C.c_size_t,
+                                           C.POINTER(C.c_size_t)]),
+    "cg_image_exr_bound": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "cg_image_exr_header": (C.c_int, [C.c_int, C.c_int, C.POINTER(ExrParams), P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "cg_image_exr_half": (C.c_int, [P, C.c_int, P]),
+    "cg_image_exr_enc_limits": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "cg_image_encode_exr_device": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(ExrParams), P,
+                                             C.c_size_t, P, P]),
+    "cg_image_encode_exr": (C.c_int, [P, P, C.c_int, C.c_int, C.c_size_t, C.POINTER(ExrParams), P, C.c_size_t,
+                                      C.POINTER(C.c_size_t)]),
+    "cg_rt_render_sequence_exr": (C.c_int, [P, C.POINTER(Light), C.c_int, C.POINTER(RtCamera), C.c_int,
+                                            C.POINTER(ExrParams), P, C.c_size_t, C.POINTER(C.c_size_t), C.c_int,
+                                            C.POINTER(Stats)]),
+    "cg_rast_draw_sequence_exr": (C.c_int, [P, C.POINTER(RastParams), C.c_int, C.POINTER(ExrParams), P, C.c_size_t,
                                             C.POINTER(C.c_size_t), C.c_int, C.POINTER(RastSeqFrame), C.POINTER(Stats)]),
 }
 EXPORTS = tuple(_SIGS)
@@ -1015,6 +1039,71 @@ def image_encode_png_host(argb, colour=PNG_RGB, filter=PNG_FILTER_ADAPTIVE) -> b
     return _png_encode(load().cg_image_encode_png_host, "cg_image_encode_png_host", argb, colour, filter)
 
 
+def image_exr_bound(width, height, channels=EXR_RGBA, type=EXR_HALF) -> int:
+    """cg_image_exr_bound: a NONE file's exact length, which no ZIP file of the size exceeds (host-only)."""
+    n = load().cg_image_exr_bound(width, height, channels, type)
+    if n < 0:
+        raise ValueError(f"cg_image_exr_bound({width}, {height}, {channels}, {type}) failed ({n})")
+    return n
+
+
+def image_exr_enc_limits():
+    """cg_image_exr_enc_limits: (lanes of a chunk workgroup, bytes of a chunk's bit string it holds in LDS)."""
+    t, b = C.c_int(), C.c_int()
+    load().cg_image_exr_enc_limits(C.byref(t), C.byref(b))
+    return t.value, b.value
+
+
+def image_exr_header(width, height, channels=EXR_RGBA, type=EXR_HALF, compression=EXR_ZIP) -> bytes:
+    """cg_image_exr_header: the header of the EXR file of a picture of that size (host-only)."""
+    prm = ExrParams(channels, type, compression, 1.0)
+    out = np.empty(512, np.uint8)
+    n = C.c_size_t()
+    rc = load().cg_image_exr_header(width, height, C.byref(prm), out.ctypes.data_as(P), out.size, C.byref(n))
+    if rc != CG_OK:
+        raise ValueError(f"cg_image_exr_header failed ({rc})")
+    return out[:n.value].tobytes()
+
+
+def image_exr_half(values) -> np.ndarray:
+    """cg_image_exr_half: the encoder's float32 -> half conversion, as uint16 bits of the input's shape."""
+    v = np.ascontiguousarray(values, dtype=np.float32)
+    out = np.zeros(v.shape, np.uint16)
+    rc = load().cg_image_exr_half(v.ctypes.data_as(P), v.size, out.ctypes.data_as(P))
+    if rc != CG_OK:
+        raise ValueError(f"cg_image_exr_half failed ({rc})")
+    return out
+
+
+def _exr_picture(rgba):
+    a = np.ascontiguousarray(rgba, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError("an EXR picture is a float32 (H, W, 4) array")
+    return a
+
+
+def _exr_encode(fn, what, rgba, channels, type, compression, alpha_scale):
+    a = _exr_picture(rgba)
+    h, w = a.shape[:2]
+    prm = ExrParams(channels, type, compression, alpha_scale)
+    n = C.c_size_t()
+    out = np.empty(max(4096, w * h * 4), np.uint8)
+    rc = fn(a.ctypes.data_as(P), w, h, 0, C.byref(prm), out.ctypes.data_as(P), out.size, C.byref(n))
+    if rc == CG_E_CAPACITY:
+        out = np.empty(n.value, np.uint8)
+        rc = fn(a.ctypes.data_as(P), w, h, 0, C.byref(prm), out.ctypes.data_as(P), out.size, C.byref(n))
+    if rc != CG_OK:
+        raise ValueError(f"{what} failed ({rc})")
+    return out[:n.value].tobytes()
+
+
+def image_encode_exr_host(rgba, channels=EXR_RGBA, type=EXR_HALF, compression=EXR_ZIP, alpha_scale=1.0) -> bytes:
+    """cg_image_encode_exr_host: the OpenEXR file of a float32 (H, W, 4) picture under the library's own
+    contract (include/cg_render.h); any EXR reader returns the samples (host-only, no GPU)."""
+    return _exr_encode(load().cg_image_encode_exr_host, "cg_image_encode_exr_host", rgba, channels, type, compression,
+                       alpha_scale)
+
+
 DIST_ID_BYTES = 128   # cg_dist_id (an RCCL unique id)
 DIST_SIGNALLED, DIST_CHUNKED = 0, 1   # cg_dist_set_pipeline
 
@@ -1579,6 +1668,50 @@ class Context:
         self._check(rc, "cg_rt_render_sequence_png")
         return files
 
+    def rt_render_sequence_exr(self, cams, lights, channels=EXR_RGBA, type=EXR_HALF, compression=EXR_ZIP, alpha_scale=1.0,
+                               chunk=0, out=None, cap=None, full=False):
+        """cg_rt_render_sequence_exr: the CG_PIX_RGBA_F32 pictures of a key script as EXR files -> list[bytes];
+        arguments and full=True as rt_render_sequence_jpeg (chunk at most 8)."""
+        if len(lights) != len(cams):
+            raise ValueError("one light list per frame")
+        if not cams:
+            return ([] if not full else (CG_OK, [], np.zeros(1, np.uint64), Stats()))
+        larr, n = sequence_lights(lights)
+        arr = (RtCamera * len(cams))(*cams)
+        st = Stats()
+        call = lambda prm, o, c, offs: self.lib.cg_rt_render_sequence_exr(  # noqa: E731
+            self.h, larr, n, arr, len(cams), prm, o, c, offs, chunk, C.byref(st))
+        rc, buf, offsets = self._sequence_jpeg(call, "cg_rt_render_sequence_exr", len(cams), cams[0].width, cams[0].height,
+                                               0, 0, out, cap, ExrParams(channels, type, compression, alpha_scale))
+        size = buf.nbytes if isinstance(buf, np.ndarray) else buf.numel() * buf.element_size()
+        files = self._jpeg_files(rc, buf, offsets, size if cap is None else cap)
+        if full:
+            return rc, files, offsets, st
+        self._check(rc, "cg_rt_render_sequence_exr")
+        return files
+
+    def rast_draw_sequence_exr(self, params_list, channels=EXR_RGBA, type=EXR_HALF, compression=EXR_ZIP, alpha_scale=1.0,
+                               chunk=0, out=None, cap=None, full=False):
+        """cg_rast_draw_sequence_exr: the float pictures of a key script as EXR files -> (list[bytes], info);
+        arguments and full=True as rast_draw_sequence_jpeg (chunk at most 8)."""
+        n = len(params_list)
+        arr = (RastParams * max(n, 1))(*params_list)
+        info = np.zeros(n + 1, RAST_SEQ_DTYPE)
+        st = Stats()
+        if not n:
+            return ([], info) if not full else (CG_OK, [], np.zeros(1, np.uint64), info, st)
+        call = lambda prm, o, c, offs: self.lib.cg_rast_draw_sequence_exr(  # noqa: E731
+            self.h, arr, n, prm, o, c, offs, chunk, C.cast(info.ctypes.data, C.POINTER(RastSeqFrame)), C.byref(st))
+        rc, buf, offsets = self._sequence_jpeg(call, "cg_rast_draw_sequence_exr", n, params_list[0].width,
+                                               params_list[0].height, 0, 0, out, cap,
+                                               ExrParams(channels, type, compression, alpha_scale))
+        size = buf.nbytes if isinstance(buf, np.ndarray) else buf.numel() * buf.element_size()
+        files = self._jpeg_files(rc, buf, offsets, size if cap is None else cap)
+        if full:
+            return rc, files, offsets, info, st
+        self._check(rc, "cg_rast_draw_sequence_exr")
+        return files, info
+
     def rast_draw_sequence_png(self, params_list, colour=PNG_RGB, filter=PNG_FILTER_ADAPTIVE, chunk=0, out=None, cap=None,
                                full=False):
         """cg_rast_draw_sequence_png: rast_draw_sequence's frames as PNG files -> (list[bytes], info);
@@ -1828,6 +1961,22 @@ class Context:
                                                         C.byref(prm), P(d_out), slot_bytes, P(d_bytes),
                                                         P(stream) if stream else None),
                     "cg_image_encode_png_device")
+
+    def image_encode_exr(self, rgba, channels=EXR_RGBA, type=EXR_HALF, compression=EXR_ZIP, alpha_scale=1.0) -> bytes:
+        """cg_image_encode_exr: image_encode_exr_host's file, encoded on this context's GPU."""
+        fn = lambda *a: self.lib.cg_image_encode_exr(self.h, *a)   # noqa: E731
+        return _exr_encode(fn, "cg_image_encode_exr", rgba, channels, type, compression, alpha_scale)
+
+    def image_encode_exr_device(self, d_rgba, width, height, n_frames, d_out, slot_bytes, d_bytes, channels=EXR_RGBA,
+                                type=EXR_HALF, compression=EXR_ZIP, alpha_scale=1.0, frame_stride=0, stream=None):
+        """cg_image_encode_exr_device: n_frames CG_PIX_RGBA_F32 pictures at the device address d_rgba
+        (frame_stride pixels apart; 0: width * height) to EXR files at d_out + f * slot_bytes, their
+        lengths (or CG_E_CAPACITY) to the int64 array d_bytes; enqueued on `stream` (None: the context's)."""
+        prm = ExrParams(channels, type, compression, alpha_scale)
+        self._check(self.lib.cg_image_encode_exr_device(self.h, P(d_rgba), width, height, n_frames, frame_stride,
+                                                        C.byref(prm), P(d_out), slot_bytes, P(d_bytes),
+                                                        P(stream) if stream else None),
+                    "cg_image_encode_exr_device")
 
     def load_textures_jpeg(self, directory: str) -> dict:
         """Decode the reference's texture files found in `directory` (names as

@@ -821,24 +821,30 @@ extern "C" int cg_rast_draw_sequence(cg_ctx *c, const cg_rast_params *ps, int n_
     return rc_out;
 }
 
+constexpr int kRastHdrChunkFrames = 8;   // frames of the float scratch (kBufRastHdr) of cg_rast_draw_exposed_device
+
 // cg_rast_draw_sequence's frames delivered compressed: its chunks of the device sequence (ARGB only),
 // each encoded on the context's stream behind its render and copied while the next chunk renders
 // (JpegDelivery, cg_ctx.h).  The records and the rand() index chain are the device sequence's, so
 // they equal cg_rast_draw_sequence's.  A frame the stream's capacity could not hold is repaired
 // after the last chunk as there -- drawn alone from its record -- encoded, and put in its place
 // among the files, which are laid out again behind it.
-// JPEG files under jp, or PNG files under pp (`who` names the call in messages).
+// JPEG files under jp, or PNG files under pp (`who` names the call in messages), or EXR files under
+// ep: then a chunk is at most 8 frames of the float sequence (CG_PIX_RGBA_F32) in the exposed calls'
+// scratch -- one set is enough, since a chunk's encoding stands on the stream before the next
+// chunk's render -- and a repaired frame is drawn as a float picture.
 static int rast_sequence_files(cg_ctx *c, const cg_rast_params *ps, int n_frames, const cg_jpeg_params *jp,
-                               const cg_png_params *pp, uint8_t *out, size_t cap, size_t *offsets, int chunk,
-                               cg_rast_seq_frame *info, cg_stats *stats, const char *who)
+                               const cg_png_params *pp, const cg_exr_params *ep, uint8_t *out, size_t cap, size_t *offsets,
+                               int chunk, cg_rast_seq_frame *info, cg_stats *stats, const char *who)
 {
     if (!c || !offsets || n_frames < 0 || (n_frames && !ps) || (!out && cap)) return CG_E_INVALID;
-    if (pp ? ((pp->colour != CG_PNG_RGB && pp->colour != CG_PNG_RGBA) ||
+    if (ep ? false : pp ? ((pp->colour != CG_PNG_RGB && pp->colour != CG_PNG_RGBA) ||
               (pp->filter != CG_PNG_FILTER_ADAPTIVE && (pp->filter < 0 || pp->filter > 4)))
            : (!jp || jp->quality < 1 || jp->quality > 100 || (jp->subsampling != CG_JPEG_444 && jp->subsampling != CG_JPEG_420)))
         return CG_E_INVALID;
     const std::string name(who);
-    if (chunk < 0 || chunk > 64) return ctx_invalid(c, (name + ": chunk 0 .. 64").c_str());
+    if (chunk < 0 || chunk > (ep ? kRastHdrChunkFrames : 64))
+        return ctx_invalid(c, (name + (ep ? ": chunk 0 .. 8" : ": chunk 0 .. 64")).c_str());
     if (c->n_room < 0) {
         c->err = "draw before cg_rast_set_scene";
         return CG_E_NOSCENE;
@@ -868,8 +874,15 @@ static int rast_sequence_files(cg_ctx *c, const cg_rast_params *ps, int n_frames
     } drain_on_exit{c};
     JpegDelivery D{c, W, H, n_frames, ch, jp ? *jp : cg_jpeg_params{}, out, cap, offsets};
     if (pp) D.png = true, D.pprm = *pp;
+    if (ep) D.exr = true, D.eprm = *ep;
     if (int rc = D.begin()) return rc;
-    for (int k = 0; k < 2; ++k) CG_TRY(c, c->rs_argb[k].ensure((size_t)ch * px * sizeof(uint32_t)), "alloc frame slots");
+    float *rgba = nullptr;
+    if (ep) {
+        hipError_t e;
+        rgba = (float *)ctx_buf(c, kBufRastHdr, kRastHdrChunkFrames * px * 16, &e);
+        if (!rgba) return ctx_fail(c, e, "alloc picture frames");
+    } else
+        for (int k = 0; k < 2; ++k) CG_TRY(c, c->rs_argb[k].ensure((size_t)ch * px * sizeof(uint32_t)), "alloc frame slots");
     const size_t rec_bytes = ((size_t)n_frames + 1) * sizeof(cg_rast_seq_frame);
     CG_TRY(c, c->rs_info.ensure(rec_bytes), "alloc records");
     CG_TRY(c, c->rs_host.ensure(rec_bytes + sizeof(int)), "alloc host records");
@@ -881,10 +894,10 @@ static int rast_sequence_files(cg_ctx *c, const cg_rast_params *ps, int n_frames
         const int s = j & 1, f0 = j * ch, nf = std::min(ch, n_frames - f0);
         int rc = D.slot_wait(j);
         if (rc) return rc;
-        rc = rast_sequence_device(c, ps + f0, nf, (uint32_t *)c->rs_argb[s].p, nullptr, nullptr, px, d_info + f0, c->stream,
-                                  j > 0, host_lanes);
+        rc = rast_sequence_device(c, ps + f0, nf, ep ? (uint32_t *)rgba : (uint32_t *)c->rs_argb[s].p, nullptr, nullptr, px,
+                                  d_info + f0, c->stream, j > 0, host_lanes, ep ? CG_PIX_RGBA_F32 : CG_PIX_ARGB8888);
         if (rc) return rc;
-        if ((rc = D.encode(j, (const uint32_t *)c->rs_argb[s].p, px))) return rc;
+        if ((rc = D.encode(j, ep ? (const void *)rgba : c->rs_argb[s].p, px))) return rc;
         if (j >= 1 && (rc = D.deliver(j - 1))) return rc;
     }
     CG_TRY(c, hipEventRecord(c->ev1, c->stream), "event");
@@ -913,7 +926,7 @@ static int rast_sequence_files(cg_ctx *c, const cg_rast_params *ps, int n_frames
         const bool last_flagged = rec[n_frames - 1].status != 0;
         bool kept = false, stop = false;
         RastLast last;
-        std::vector<uint32_t> frame(px);
+        std::vector<uint32_t> frame(ep ? 4 * px : px);   // a float picture has four words a pixel
         std::vector<uint8_t> file;
         for (int f = 0; f < n_frames; ++f) {
             const uint8_t *src = (size_t)f < have ? first.data() + old[f] : nullptr;
@@ -926,10 +939,14 @@ static int rast_sequence_files(cg_ctx *c, const cg_rast_params *ps, int n_frames
                 }
                 cg_rast_params p = ps[f];
                 p.rand_offset = rec[f].rand_offset;
-                int rc = cg_rast_draw(c, &p, frame.data(), nullptr, nullptr, nullptr);
+                int rc = ep ? cg_rast_draw_picture(c, &p, (float *)frame.data(), nullptr)
+                            : cg_rast_draw(c, &p, frame.data(), nullptr, nullptr, nullptr);
                 if (rc) return rc;
-                file.resize((size_t)(pp ? cg_image_png_bound(W, H, pp->colour) : cg_image_jpeg_bound(W, H, jp->subsampling)));
-                if ((rc = pp ? cg_image_encode_png(c, frame.data(), W, H, 0, pp, file.data(), file.size(), &len)
+                file.resize((size_t)(ep   ? cg_image_exr_bound(W, H, ep->channels, ep->type)
+                                     : pp ? cg_image_png_bound(W, H, pp->colour)
+                                          : cg_image_jpeg_bound(W, H, jp->subsampling)));
+                if ((rc = ep ? cg_image_encode_exr(c, (const float *)frame.data(), W, H, 0, ep, file.data(), file.size(), &len)
+                        : pp ? cg_image_encode_png(c, frame.data(), W, H, 0, pp, file.data(), file.size(), &len)
                              : cg_image_encode_jpeg(c, frame.data(), W, H, 0, jp, file.data(), file.size(), &len)))
                     return rc;
                 src = file.data();
@@ -961,7 +978,8 @@ extern "C" int cg_rast_draw_sequence_jpeg(cg_ctx *c, const cg_rast_params *ps, i
                                           const cg_jpeg_params *params, uint8_t *out, size_t cap, size_t *offsets,
                                           int chunk, cg_rast_seq_frame *info, cg_stats *stats)
 {
-    return rast_sequence_files(c, ps, n_frames, params, nullptr, out, cap, offsets, chunk, info, stats, "draw_sequence_jpeg");
+    return rast_sequence_files(c, ps, n_frames, params, nullptr, nullptr, out, cap, offsets, chunk, info, stats,
+                               "draw_sequence_jpeg");
 }
 
 extern "C" int cg_rast_draw_sequence_png(cg_ctx *c, const cg_rast_params *ps, int n_frames, const cg_png_params *params,
@@ -969,7 +987,18 @@ extern "C" int cg_rast_draw_sequence_png(cg_ctx *c, const cg_rast_params *ps, in
                                          cg_stats *stats)
 {
     if (!params) return CG_E_INVALID;
-    return rast_sequence_files(c, ps, n_frames, nullptr, params, out, cap, offsets, chunk, info, stats, "draw_sequence_png");
+    return rast_sequence_files(c, ps, n_frames, nullptr, params, nullptr, out, cap, offsets, chunk, info, stats,
+                               "draw_sequence_png");
+}
+
+extern "C" int cg_rast_draw_sequence_exr(cg_ctx *c, const cg_rast_params *ps, int n_frames, const cg_exr_params *params,
+                                         uint8_t *out, size_t cap, size_t *offsets, int chunk, cg_rast_seq_frame *info,
+                                         cg_stats *stats)
+{
+    cg_exr_params prm;
+    if (!exr_resolve_params(params, &prm)) return CG_E_INVALID;
+    return rast_sequence_files(c, ps, n_frames, nullptr, nullptr, &prm, out, cap, offsets, chunk, info, stats,
+                               "draw_sequence_exr");
 }
 
 // ---- the float picture (CG_PIX_RGBA_F32) and exposed frames (kernels: the post-pass's *_f32
@@ -1045,8 +1074,6 @@ extern "C" int cg_rast_tonemap_pack_device(cg_ctx *c, const float *d_rgba, size_
            "tonemap pack launch");
     return CG_OK;
 }
-
-constexpr int kRastHdrChunkFrames = 8;   // frames of cg_rast_draw_exposed_device's scratch
 
 // what both forms of cg_rast_draw_exposed check before anything is enqueued (the sequence checks the rest)
 static int rast_exposed_check(cg_ctx *c, const cg_rast_params *ps, int n_frames, const cg_hdr_exposure_params *params,

@@ -524,6 +524,7 @@ int JpegDelivery::begin()
 {
     slot_bytes = (size_t)W * H;   // a frame's device slot: a file this long is rare and is encoded again alone
     if (png) slot_bytes = (size_t)cg_image_png_bound(W, H, pprm.colour);   // exact frames: no file is longer
+    if (exr) slot_bytes = (size_t)cg_image_exr_bound(W, H, eprm.channels, eprm.type);
     CG_TRY(c, c->xfer.ensure(hipStreamNonBlocking), "copy stream");
     for (int k = 0; k < 2; ++k) {
         CG_TRY(c, c->jpeg_rdone[k].ensure(), "copy event");
@@ -542,14 +543,19 @@ int JpegDelivery::slot_wait(int j)
     return CG_OK;
 }
 
-int JpegDelivery::encode(int j, const uint32_t *d_frames, size_t frame_stride)
+int JpegDelivery::encode(int j, const void *d_frames_v, size_t frame_stride)
 {
+    const uint32_t *d_frames = (const uint32_t *)d_frames_v;
     const int s = j & 1, nf = std::min(ch, n_frames - j * ch);
-    frames[s] = d_frames;
+    frames[s] = d_frames_v;
     fstride[s] = frame_stride;
     uint8_t *base = (uint8_t *)c->jpeg_out[s].p;
     const size_t lens_b = 256 * (((size_t)ch * 8 + 255) / 256);
-    if (int rc = png ? cg_image_encode_png_device(c, d_frames, W, H, nf, frame_stride, &pprm, base + lens_b, slot_bytes,
+    if (exr) {
+        if (int rc = cg_image_encode_exr_device(c, (const float *)d_frames_v, W, H, nf, frame_stride, &eprm, base + lens_b, slot_bytes,
+                                                (int64_t *)base, c->stream))
+            return rc;
+    } else if (int rc = png ? cg_image_encode_png_device(c, d_frames, W, H, nf, frame_stride, &pprm, base + lens_b, slot_bytes,
                                                   (int64_t *)base, c->stream)
                      : cg_image_encode_jpeg_device(c, d_frames, W, H, nf, frame_stride, &prm, base + lens_b, slot_bytes,
                                                    (int64_t *)base, c->stream))
@@ -570,12 +576,12 @@ int JpegDelivery::deliver(int j)
     for (int f = 0; f < nf; ++f) {
         int64_t len = h_len[f];
         const uint8_t *src = base + lens_b + (size_t)f * slot_bytes;
-        const bool again = len == CG_E_CAPACITY && !png;
+        const bool again = len == CG_E_CAPACITY && !png && !exr;
         if (again) {   // longer than W * H bytes: alone, into a slot no file can exceed, behind what the stream holds
             const size_t bound = (size_t)cg_image_jpeg_bound(W, H, prm.subsampling);
             CG_TRY(c, c->jpeg_big.ensure(256 + bound), "alloc file slot");
             uint8_t *big = (uint8_t *)c->jpeg_big.p;
-            if (int rc = cg_image_encode_jpeg_device(c, frames[s] + (size_t)f * fstride[s], W, H, 1, 0, &prm, big + 256, bound,
+            if (int rc = cg_image_encode_jpeg_device(c, (const uint32_t *)frames[s] + (size_t)f * fstride[s], W, H, 1, 0, &prm, big + 256, bound,
                                                      (int64_t *)big, c->stream))
                 return rc;
             CG_TRY(c, hipMemcpyAsync(&len, big, 8, hipMemcpyDeviceToHost, c->stream), "d2h length");
@@ -614,13 +620,15 @@ static bool png_params_ok(const cg_png_params *p)
 
 // cg_rt_render_sequence's chunks (rt_render_frames_host above), each encoded on the context's stream
 // behind its render; chunk j's files are copied while chunk j + 1 renders.  JPEG files under jp, or
-// PNG files under pp.
+// PNG files under pp, or EXR files under ep: then a chunk is at most 8 frames, rendered as
+// CG_PIX_RGBA_F32 by the device sequence call into the exposed calls' float scratch -- one set is
+// enough, since a chunk's encoding stands on the stream before the next chunk's render.
 static int rt_sequence_files(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams, int n_frames,
-                             const cg_jpeg_params *jp, const cg_png_params *pp, uint8_t *out, size_t cap, size_t *offsets,
-                             int chunk, cg_stats *stats)
+                             const cg_jpeg_params *jp, const cg_png_params *pp, const cg_exr_params *ep, uint8_t *out,
+                             size_t cap, size_t *offsets, int chunk, cg_stats *stats)
 {
     if (!c || !offsets || n_frames < 0 || (n_frames && !cams) || chunk < 0 || (!out && cap) ||
-        (pp ? !png_params_ok(pp) : !jpeg_params_ok(jp)) || n_lights < 0 || n_lights > kMaxLights || (n_lights && !lights))
+        (ep ? false : pp ? !png_params_ok(pp) : !jpeg_params_ok(jp)) || n_lights < 0 || n_lights > kMaxLights || (n_lights && !lights))
         return CG_E_INVALID;
     offsets[0] = 0;
     if (n_frames == 0) return CG_OK;
@@ -630,7 +638,7 @@ static int rt_sequence_files(cg_ctx *c, const cg_light *lights, int n_lights, co
     if (W <= 0 || H <= 0 || W > 65535 || H > 65535) return CG_E_INVALID;
     for (int f = 1; f < n_frames; ++f)
         if (cams[f].width != W || cams[f].height != H) return CG_E_INVALID;
-    const int ch = std::min(chunk ? std::min(chunk, 64) : 8, n_frames);
+    const int ch = std::min(chunk ? std::min(chunk, ep ? kHdrChunkFrames : 64) : 8, n_frames);
     struct Drain {
         cg_ctx *c;
         ~Drain()
@@ -641,9 +649,13 @@ static int rt_sequence_files(cg_ctx *c, const cg_light *lights, int n_lights, co
     } drain_on_exit{c};
     JpegDelivery D{c, W, H, n_frames, ch, jp ? *jp : cg_jpeg_params{}, out, cap, offsets};
     if (pp) D.png = true, D.pprm = *pp;
+    if (ep) D.exr = true, D.eprm = *ep;
     if (int rc = D.begin()) return rc;
-    const size_t spx = (size_t)cg_rt_shard_rows(H, nullptr) * W;
-    for (int k = 0; k < 2; ++k) CG_TRY(c, c->hslot[k].ensure((size_t)ch * spx * sizeof(uint32_t)), "alloc frame slots");
+    const size_t spx = (size_t)cg_rt_shard_rows(H, nullptr) * W, px = (size_t)W * H;
+    if (ep) CG_TRY(c, c->hdr_rgba.ensure(kHdrChunkFrames * px * 16), "alloc picture frames");
+    else
+        for (int k = 0; k < 2; ++k) CG_TRY(c, c->hslot[k].ensure((size_t)ch * spx * sizeof(uint32_t)), "alloc frame slots");
+    cg_rt_shard whole{0, 1, H, 0, H, 0, 0};   // a band of exactly the frame's rows
     const int nchunks = (n_frames + ch - 1) / ch;
     const int light_stride = std::max(n_lights, 1);
     CG_TRY(c, hipEventRecord(c->ev0, c->stream), "event");
@@ -651,10 +663,18 @@ static int rt_sequence_files(cg_ctx *c, const cg_light *lights, int n_lights, co
         const int s = j & 1, f0 = j * ch, nf = std::min(ch, n_frames - f0);
         int rc = D.slot_wait(j);
         if (rc) return rc;
+        if (ep) {
+            rc = cg_rt_render_sequence_device(c, lights ? lights + (size_t)f0 * n_lights : lights, n_lights, cams + f0, nf,
+                                              &whole, c->hdr_rgba.p, px, CG_PIX_RGBA_F32, c->stream);
+            if (rc) return rc;
+            if ((rc = D.encode(j, c->hdr_rgba.p, px))) return rc;
+            if (j >= 1 && (rc = D.deliver(j - 1))) return rc;
+            continue;
+        }
         rc = rt_render_frames(c, lights ? lights + (size_t)f0 * n_lights : lights, n_lights, cams + f0, nf, nullptr,
                               c->hslot[s].p, spx, CG_PIX_ARGB8888, c->stream, nullptr, nullptr, nullptr, 0, light_stride);
         if (rc) return rc;
-        if ((rc = D.encode(j, (const uint32_t *)c->hslot[s].p, spx))) return rc;
+        if ((rc = D.encode(j, c->hslot[s].p, spx))) return rc;
         if (j >= 1 && (rc = D.deliver(j - 1))) return rc;
     }
     CG_TRY(c, hipEventRecord(c->ev1, c->stream), "event");
@@ -677,7 +697,7 @@ extern "C" int cg_rt_render_sequence_jpeg(cg_ctx *c, const cg_light *lights, int
                                           int n_frames, const cg_jpeg_params *params, uint8_t *out, size_t cap,
                                           size_t *offsets, int chunk, cg_stats *stats)
 {
-    return rt_sequence_files(c, lights, n_lights, cams, n_frames, params, nullptr, out, cap, offsets, chunk, stats);
+    return rt_sequence_files(c, lights, n_lights, cams, n_frames, params, nullptr, nullptr, out, cap, offsets, chunk, stats);
 }
 
 extern "C" int cg_rt_render_sequence_png(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
@@ -685,5 +705,14 @@ extern "C" int cg_rt_render_sequence_png(cg_ctx *c, const cg_light *lights, int 
                                          size_t *offsets, int chunk, cg_stats *stats)
 {
     if (!params) return CG_E_INVALID;
-    return rt_sequence_files(c, lights, n_lights, cams, n_frames, nullptr, params, out, cap, offsets, chunk, stats);
+    return rt_sequence_files(c, lights, n_lights, cams, n_frames, nullptr, params, nullptr, out, cap, offsets, chunk, stats);
+}
+
+extern "C" int cg_rt_render_sequence_exr(cg_ctx *c, const cg_light *lights, int n_lights, const cg_rt_camera *cams,
+                                         int n_frames, const cg_exr_params *params, uint8_t *out, size_t cap,
+                                         size_t *offsets, int chunk, cg_stats *stats)
+{
+    cg_exr_params prm;
+    if (!exr_resolve_params(params, &prm)) return CG_E_INVALID;
+    return rt_sequence_files(c, lights, n_lights, cams, n_frames, nullptr, nullptr, &prm, out, cap, offsets, chunk, stats);
 }

@@ -261,6 +261,9 @@ struct cg_ctx {
     // PNG encode (cg_png_enc.hip): the filtered rows, band lengths, Adler sums, offsets and staged bands
     // of up to 8 frames; the host-memory form's uploaded frame, file slot and length
     DevBuf png_enc, png_enc_io;
+    // EXR encode (cg_exr_enc.hip): the predicted bytes, chunk lengths, offsets and staged streams of up
+    // to 8 frames; the host-memory form's uploaded frame, file slot and length
+    DevBuf exr_enc, exr_enc_io;
     int n_room = -1, n_boxes = 0;
     int scene_tex = 0;                   // bit k: the uploaded room/boxes carry texture k
     // texture modes 1-3 (cg_rast_set_textures): device copies of the maps
@@ -291,7 +294,8 @@ int rt_enqueue(cg_ctx *c, const RtFrame &Fin, void *d_out_v, hipStream_t st, int
 // to back on `xfer` -- called after chunk j + 1 is enqueued, it overlaps that chunk's render.  A
 // frame that did not fit its slot is encoded again alone into a slot of cg_image_jpeg_bound.
 // With `png` set the files are PNGs under `pprm` (cg_*_sequence_png): a frame's slot is
-// cg_image_png_bound, so no file is encoded twice.
+// cg_image_png_bound, so no file is encoded twice.  With `exr` set the chunk is CG_PIX_RGBA_F32
+// pictures and the files are EXRs under `eprm` (cg_*_sequence_exr), in slots of cg_image_exr_bound.
 // offsets[f] .. offsets[f + 1] is frame f's file; once a frame does not fit below `cap` nothing
 // more is copied and the offsets count on, so offsets[n_frames] is the capacity needed.
 struct JpegDelivery {
@@ -302,13 +306,15 @@ struct JpegDelivery {
     size_t cap, *offsets;
     size_t slot_bytes = 0;
     bool full = false;                       // a frame did not fit: nothing more is copied
-    const uint32_t *frames[2] = {};          // the slot sets' rendered chunks, for the frames encoded again
+    const void *frames[2] = {};              // the slot sets' rendered chunks, for the frames encoded again
     size_t fstride[2] = {};
     bool png = false;
     cg_png_params pprm = {};
+    bool exr = false;
+    cg_exr_params eprm = {};
     int begin();
     int slot_wait(int j);                    // before chunk j >= 2 is rendered: chunk j - 2 is copied
-    int encode(int j, const uint32_t *d_frames, size_t frame_stride);
+    int encode(int j, const void *d_frames, size_t frame_stride);   // uint32 pixels; float4 ones with `exr`
     int deliver(int j);
     int finish();                            // waits for the copies; CG_E_CAPACITY if `out` was short
 };

@@ -47,6 +47,16 @@ void *ctx_png_buf(cg_ctx *c, int which, size_t bytes, hipError_t *e)
     *e = b.ensure(bytes);
     return *e == hipSuccess ? b.p : nullptr;
 }
+void *ctx_exr_buf(cg_ctx *c, int which, size_t bytes, hipError_t *e)
+{
+    if (which != 0 && which != 1) {
+        *e = hipErrorInvalidValue;
+        return nullptr;
+    }
+    DevBuf &b = which ? c->exr_enc_io : c->exr_enc;
+    *e = b.ensure(bytes);
+    return *e == hipSuccess ? b.p : nullptr;
+}
 StarState *ctx_star(cg_ctx *c) { return &c->star; }
 int ctx_invalid(cg_ctx *c, const char *what)
 {

@@ -59,6 +59,10 @@ enum {
 void *ctx_buf(cg_ctx *c, int which, size_t bytes, hipError_t *e);
 // cg_png_enc.hip's two: 0 a chunk's filtered rows and staged bands, 1 the host form's frame and file
 void *ctx_png_buf(cg_ctx *c, int which, size_t bytes, hipError_t *e);
+// cg_exr_enc.hip's two: 0 a chunk's predicted bytes and staged streams, 1 the host form's frame and file
+void *ctx_exr_buf(cg_ctx *c, int which, size_t bytes, hipError_t *e);
+// cg_exr_enc.hip: *out = *in, or the defaults for NULL; false if a field is invalid
+bool exr_resolve_params(const cg_exr_params *in, cg_exr_params *out);
 int ctx_device(const cg_ctx *c);
 hipStream_t ctx_stream(const cg_ctx *c);
 void ctx_events(cg_ctx *c, hipEvent_t *a, hipEvent_t *b);

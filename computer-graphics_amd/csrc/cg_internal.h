@@ -249,7 +249,9 @@ enum KtId {
     // a hits-only pass of the large-scene path: a scope over it, its walk, its gather
     KT_RT_HITS_PASS, KT_RT_HITS_WALK, KT_RT_HITS_GATHER,
     // the PNG encoder's four kernels (cg_png_enc.hip)
-    KT_PNG_FILTER, KT_PNG_BAND, KT_PNG_SCAN, KT_PNG_GATHER, KT_COUNT
+    KT_PNG_FILTER, KT_PNG_BAND, KT_PNG_SCAN, KT_PNG_GATHER,
+    // the EXR encoder's four kernels (cg_exr_enc.hip)
+    KT_EXR_PLANE, KT_EXR_CHUNK, KT_EXR_SCAN, KT_EXR_GATHER, KT_COUNT
 };
 // HIP events on `st` around the scope's launches while timing is on (id
 // outside [0, KT_COUNT): nothing).

@@ -27,6 +27,7 @@ static const char *const kKtNames[KT_COUNT] = {
     // a hits-only pass (cg_rt_hits_device) on a large scene: the whole pass, its walk, its gather
     "rt_hits_pass",             "rt_hits_walk",          "rt_hits_gather",
     "png_enc_filter_kernel",    "png_enc_band_kernel",   "png_enc_scan_kernel",     "png_enc_gather_kernel",
+    "exr_enc_plane_kernel",     "exr_enc_chunk_kernel",  "exr_enc_scan_kernel",     "exr_enc_gather_kernel",
 };
 
 namespace {

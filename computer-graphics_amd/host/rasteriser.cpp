@@ -21,6 +21,7 @@
 //              [--bloom THRESHOLD,INTENSITY[,LEVELS[,CAP]]]
 //              [--jpeg FILE [--quality 1..100] [--subsampling 444|420]]
 //              [--png FILE [--png-colour rgb|rgba] [--png-filter adaptive|0..4]]
+//              [--exr FILE [--exr-type half|float] [--exr-compression zip|none] [--exr-colour rgb|rgba]]
 //
 // --batch: Update() runs over the whole key script first, each frame's globals
 // are recorded as a cg_rast_params, and one cg_rast_draw_sequence call renders
@@ -48,6 +49,10 @@
 // and adaptive filters unless --png-colour / --png-filter say otherwise): it decodes to exactly the
 // pixels of --out.  With --batch, also frame k of the run as FILE with .%04d before its extension:
 // through cg_rast_draw_sequence_png, or with the exposure flags each exposed frame through the encoder.
+// --exr FILE: the picture --pfm writes, as an OpenEXR file encoded on the device (cg_image_encode_exr;
+// RGBA halves under ZIP unless --exr-type / --exr-compression / --exr-colour say otherwise).  With
+// --batch, also frame k's picture as FILE with .%04d before its extension, through
+// cg_rast_draw_sequence_exr; the exposure flags do not change them.
 #include <cmath>
 #include <cstring>
 #include <fstream>
@@ -58,6 +63,7 @@
 #include "TestModelH.h"
 #include "bloom_arg.h"
 #include "cg_render.h"
+#include "exr_arg.h"
 #include "jpeg_arg.h"
 #include "png_arg.h"
 
@@ -128,13 +134,19 @@ void Draw(screen *screen)
     }
 }
 
-// --pfm: the picture of the latest frame's parameters, unclamped
+// --pfm, --exr: the picture of the latest frame's parameters, unclamped
+static vector<float> Picture()
+{
+    vector<float> rgba((size_t)g_last.width * g_last.height * 4);
+    int rc = cg_rast_draw_picture(g_ctx, &g_last, rgba.data(), nullptr);
+    if (rc) die(rc, "cg_rast_draw_picture");
+    return rgba;
+}
+
 static void SavePicturePFM(const char *path)
 {
     const int W = g_last.width, H = g_last.height;
-    vector<float> rgba((size_t)W * H * 4);
-    int rc = cg_rast_draw_picture(g_ctx, &g_last, rgba.data(), nullptr);
-    if (rc) die(rc, "cg_rast_draw_picture");
+    const vector<float> rgba = Picture();
     ofstream f(path, ios::binary);
     f << "PF\n" << W << " " << H << "\n-1.0\n";
     vector<float> row((size_t)W * 3);
@@ -224,6 +236,7 @@ int main(int argc, char *argv[])
     JpegArg jpeg;                                              // --jpeg: quality 75, 4:2:0 unless given
     vector<uint8_t> jpeg_bytes;
     PngArg png;                                                // --png: RGB, adaptive filters unless given
+    ExrArg exr;                                                // --exr: RGBA halves under ZIP unless given
     for (int i = 1; i < argc; i += 2) {
         string a = argv[i];
         if (a == "--batch") {
@@ -244,6 +257,10 @@ int main(int argc, char *argv[])
                 cerr << PNG_USAGE << endl;
                 return 1;
             }
+            if (ParseExrArg(a, nullptr, &exr)) {
+                cerr << EXR_USAGE << endl;
+                return 1;
+            }
             break;
         }
         if (const int j = ParseJpegArg(a, argv[i + 1], &jpeg)) {
@@ -256,6 +273,13 @@ int main(int argc, char *argv[])
         if (const int j = ParsePngArg(a, argv[i + 1], &png)) {
             if (j < 0) {
                 cerr << PNG_USAGE << endl;
+                return 1;
+            }
+            continue;
+        }
+        if (const int j = ParseExrArg(a, argv[i + 1], &exr)) {
+            if (j < 0) {
+                cerr << EXR_USAGE << endl;
                 return 1;
             }
             continue;
@@ -383,6 +407,15 @@ int main(int argc, char *argv[])
                                      [&](size_t f) { return PngFramePath(png.path, f); });
                 if (rc) die(rc, "cg_image_encode_png");
             }
+            if (!exr.path.empty() && batch) {   // the frames' float pictures, delivered as files
+                rc = ExrDeliver(
+                    [&](uint8_t *o, size_t cap, size_t *offsets) {
+                        return cg_rast_draw_sequence_exr(g_ctx, ps.data(), (int)ps.size(), &exr.params, o, cap, offsets, 0,
+                                                         nullptr, nullptr);
+                    },
+                    ps.size(), screen->width, screen->height, exr.path);
+                if (rc) die(rc, "cg_rast_draw_sequence_exr");
+            }
             randCalls = info.back().rand_offset;
             g_last = ps.back();                               // the last frame, at its chained index
             g_last.rand_offset = info[ps.size() - 1].rand_offset;
@@ -413,6 +446,10 @@ int main(int argc, char *argv[])
         if (rc) die(rc, "cg_image_encode_png");
     }
     if (!pfm.empty() && g_drawn) SavePicturePFM(pfm.c_str());
+    if (!exr.path.empty() && g_drawn) {
+        rc = ExrEncodePicture(g_ctx, Picture().data(), g_last.width, g_last.height, exr.params, exr.path);
+        if (rc) die(rc, "cg_image_encode_exr");
+    }
     KillSDL(screen);
     cg_destroy(g_ctx);
     return 0;

@@ -13,6 +13,7 @@
 //             [--bloom THRESHOLD,INTENSITY[,LEVELS[,CAP]]]
 //             [--jpeg FILE [--quality 1..100] [--subsampling 444|420]]
 //             [--png FILE [--png-colour rgb|rgba] [--png-filter adaptive|0..4]]
+//             [--exr FILE [--exr-type half|float] [--exr-compression zip|none] [--exr-colour rgb|rgba]]
 //
 // --batch: Update() runs over the whole key script first, each frame's globals
 // are recorded, and one cg_rt_render_sequence call renders every frame; the
@@ -37,6 +38,10 @@
 // and adaptive filters unless --png-colour / --png-filter say otherwise): it decodes to exactly the
 // pixels of --out.  With --batch, also frame k of the run as FILE with .%04d before its extension:
 // through cg_rt_render_sequence_png, or with the exposure flags each exposed frame through the encoder.
+// --exr FILE: the picture --pfm writes, as an OpenEXR file encoded on the device (cg_image_encode_exr;
+// RGBA halves under ZIP unless --exr-type / --exr-compression / --exr-colour say otherwise).  A is the
+// share of the pixel's nine sub-rays that hit, w / 9.  With --batch, also frame k's picture as FILE with
+// .%04d before its extension, through cg_rt_render_sequence_exr; the exposure flags do not change them.
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -48,6 +53,7 @@
 #include "TestModelH.h"
 #include "bloom_arg.h"
 #include "cg_render.h"
+#include "exr_arg.h"
 #include "jpeg_arg.h"
 #include "png_arg.h"
 
@@ -133,16 +139,22 @@ void Draw(screen *screen)
     if (rc) die(rc, "cg_rt_render");
 }
 
-// --pfm: the frame Draw would render from the current globals, unclamped
-static void SaveRadiancePFM(const screen *screen, const char *path)
+// --pfm, --exr: the frame Draw would render from the current globals, unclamped
+static vector<float> Radiance(const screen *screen)
 {
     UploadScene();
     const cg_rt_camera cam = CurrentCamera(screen);
-    const size_t px = (size_t)cam.width * cam.height;
-    vector<float> rgba(px * 4);
+    vector<float> rgba((size_t)cam.width * cam.height * 4);
     int rc = cg_rt_render_radiance(g_ctx, reinterpret_cast<const cg_light *>(lights.data()), (int)lights.size(), &cam,
                                    rgba.data(), nullptr);
     if (rc) die(rc, "cg_rt_render_radiance");
+    return rgba;
+}
+
+static void SaveRadiancePFM(const screen *screen, const char *path)
+{
+    const cg_rt_camera cam = CurrentCamera(screen);
+    const vector<float> rgba = Radiance(screen);
     ofstream f(path, ios::binary);
     f << "PF\n" << cam.width << " " << cam.height << "\n-1.0\n";
     vector<float> row((size_t)cam.width * 3);
@@ -206,6 +218,8 @@ int main(int argc, char *argv[])
     JpegArg jpeg;                                              // --jpeg: quality 75, 4:2:0 unless given
     vector<uint8_t> jpeg_bytes;
     PngArg png;                                                // --png: RGB, adaptive filters unless given
+    ExrArg exr;                                                // --exr: RGBA halves under ZIP unless given
+    exr.params.alpha_scale = 1.0f / 9.0f;                      // w counts the sub-rays of nine that hit
     for (int i = 1; i < argc; i += 2) {
         string a = argv[i];
         if (a == "--batch") {
@@ -226,6 +240,10 @@ int main(int argc, char *argv[])
                 cerr << PNG_USAGE << endl;
                 return 1;
             }
+            if (ParseExrArg(a, nullptr, &exr)) {
+                cerr << EXR_USAGE << endl;
+                return 1;
+            }
             break;
         }
         if (const int j = ParseJpegArg(a, argv[i + 1], &jpeg)) {
@@ -238,6 +256,13 @@ int main(int argc, char *argv[])
         if (const int j = ParsePngArg(a, argv[i + 1], &png)) {
             if (j < 0) {
                 cerr << PNG_USAGE << endl;
+                return 1;
+            }
+            continue;
+        }
+        if (const int j = ParseExrArg(a, argv[i + 1], &exr)) {
+            if (j < 0) {
+                cerr << EXR_USAGE << endl;
                 return 1;
             }
             continue;
@@ -346,6 +371,16 @@ int main(int argc, char *argv[])
                                      [&](size_t f) { return PngFramePath(png.path, f); });
                 if (rc) die(rc, "cg_image_encode_png");
             }
+            if (!exr.path.empty() && batch) {   // the frames' float pictures, delivered as files
+                rc = ExrDeliver(
+                    [&](uint8_t *o, size_t cap, size_t *offsets) {
+                        return cg_rt_render_sequence_exr(g_ctx, reinterpret_cast<const cg_light *>(seq.data()),
+                                                         (int)lights.size(), cams.data(), (int)cams.size(), &exr.params, o,
+                                                         cap, offsets, 0, nullptr);
+                    },
+                    cams.size(), screen->width, screen->height, exr.path);
+                if (rc) die(rc, "cg_rt_render_sequence_exr");
+            }
             memcpy(screen->buffer, frames.data() + (cams.size() - 1) * px, px * sizeof(uint32_t));
             SDL_Renderframe(screen);
         }
@@ -375,6 +410,10 @@ int main(int argc, char *argv[])
     }
     // Update() changes nothing on the turn it ends the loop: the globals are the last frame's
     if (!pfm.empty() && drawn > 0) SaveRadiancePFM(screen, pfm.c_str());
+    if (!exr.path.empty() && drawn > 0) {
+        rc = ExrEncodePicture(g_ctx, Radiance(screen).data(), screen->width, screen->height, exr.params, exr.path);
+        if (rc) die(rc, "cg_image_encode_exr");
+    }
     KillSDL(screen);
     cg_destroy(g_ctx);
     return 0;

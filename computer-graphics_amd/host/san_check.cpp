@@ -516,9 +516,84 @@ int main(int argc, char **argv)
             cg_image_png_bound(1, 1, 3) != CG_E_INVALID || cg_image_png_bound(65535, 65535, CG_PNG_RGBA) <= 0)
             fail("png encoder refusals", -1);
     }
+    // the EXR encoder's host-only entries: odd sizes around a chunk of 16 scanlines, both channel sets,
+    // types and compressions, smooth pictures (deflated chunks), noise (the raw fallback) and float
+    // specials, a row stride, NULL params, the length query with no buffer, every capacity on the
+    // smallest and one byte short on the others; then the half rule alone and the refusals
+    int exr_encoded = 0;
+    {
+        const int sizes[][2] = {{1, 1}, {2, 1}, {1, 2}, {3, 15}, {3, 16}, {5, 17}, {7, 33}, {70, 3}};
+        const uint32_t specials[] = {0x7F800001u, 0x7FC00000u, 0xFF800000u, 0x00000001u, 0x807FFFFFu, 0x33000000u,
+                                     0x33000001u, 0x387FC000u, 0x477FEFFFu, 0x477FF000u, 0xFFFFFFFFu};
+        uint32_t seed = 97531u;
+        int raw_files = 0;
+        for (const auto &sz : sizes)
+            for (int channels : {CG_EXR_RGB, CG_EXR_RGBA})
+                for (int type : {CG_EXR_HALF, CG_EXR_FLOAT})
+                    for (int compression : {CG_EXR_NONE, CG_EXR_ZIP})
+                        for (int content : {0, 1, 2}) {
+                            const int W = sz[0], H = sz[1];
+                            const size_t stride = (size_t)W + 3;
+                            std::vector<float> px(stride * H * 4);   // exactly H rows
+                            for (size_t i = 0; i < px.size(); ++i) {
+                                const uint32_t bits = content == 1   ? (seed = seed * 1103515245u + 12345u)
+                                                      : content == 2 ? specials[i % (sizeof specials / sizeof specials[0])]
+                                                                     : 0x3F000000u + 0x2000u * (uint32_t)(i / 29);
+                                memcpy(&px[i], &bits, 4);
+                            }
+                            const cg_exr_params prm{channels, type, compression, content ? 1.0f : 0.5f};
+                            const bool dflt = channels == CG_EXR_RGBA && type == CG_EXR_HALF && compression == CG_EXR_ZIP && content;
+                            const cg_exr_params *pp = dflt ? nullptr : &prm;   // NULL is RGBA, HALF, ZIP, scale 1
+                            size_t need = 0, n = 0;
+                            if (cg_image_encode_exr_host(px.data(), W, H, stride, pp, nullptr, 0, &need) != CG_E_CAPACITY || !need)
+                                fail("cg_image_encode_exr_host length query", W);
+                            const long long bound = cg_image_exr_bound(W, H, channels, type);
+                            if ((long long)need > bound || (compression == CG_EXR_NONE && (long long)need != bound))
+                                fail("cg_image_exr_bound", (int)need);
+                            if (compression == CG_EXR_ZIP && (long long)need == bound) ++raw_files;   // every chunk fell back
+                            std::vector<uint8_t> file(need);
+                            if (int rc = cg_image_encode_exr_host(px.data(), W, H, stride, pp, file.data(), need, &n))
+                                fail("cg_image_encode_exr_host", rc);
+                            if (n != need || memcmp(file.data(), "\x76\x2f\x31\x01", 4)) fail("the encoded EXR", (int)n);
+                            for (size_t cap = W * H <= 2 ? 0 : need - 1; cap < need; ++cap) {
+                                std::vector<uint8_t> part(cap);
+                                if (cg_image_encode_exr_host(px.data(), W, H, stride, pp, part.data(), cap, &n) != CG_E_CAPACITY ||
+                                    n != need || (cap && memcmp(part.data(), file.data(), cap)))
+                                    fail("cg_image_encode_exr_host capacity", (int)cap);
+                            }
+                            ++exr_encoded;
+                        }
+        if (!raw_files) fail("no EXR file took the raw fallback", 0);
+        std::vector<float> v(sizeof specials / sizeof specials[0]);
+        memcpy(v.data(), specials, sizeof specials);
+        std::vector<uint16_t> hv(v.size());
+        if (cg_image_exr_half(v.data(), (int)v.size(), hv.data()) || hv[0] != 0x7C01 || hv[6] != 0x0001 || hv[9] != 0x7C00)
+            fail("cg_image_exr_half", hv[0]);
+        uint8_t hdr[331];
+        size_t n = 0;
+        if (cg_image_exr_header(7, 33, nullptr, hdr, sizeof hdr, &n) || n != 331) fail("cg_image_exr_header", (int)n);
+        const cg_exr_params ok{CG_EXR_RGB, CG_EXR_HALF, CG_EXR_ZIP, 1.0f}, bad_c{2, 1, 3, 1.0f}, bad_t{3, 3, 3, 1.0f},
+            bad_z{3, 1, 2, 1.0f}, bad_a{4, 1, 3, INFINITY};
+        float one[4] = {0, 0, 0, 0};
+        uint8_t byte = 0;
+        if (cg_image_encode_exr_host(one, 0, 1, 0, &ok, &byte, 1, &n) != CG_E_INVALID ||
+            cg_image_encode_exr_host(one, 1, 65536, 0, &ok, &byte, 1, &n) != CG_E_INVALID ||
+            cg_image_encode_exr_host(one, 1, 1, 0, &bad_c, &byte, 1, &n) != CG_E_INVALID ||
+            cg_image_encode_exr_host(one, 1, 1, 0, &bad_t, &byte, 1, &n) != CG_E_INVALID ||
+            cg_image_encode_exr_host(one, 1, 1, 0, &bad_z, &byte, 1, &n) != CG_E_INVALID ||
+            cg_image_encode_exr_host(one, 1, 1, 0, &bad_a, &byte, 1, &n) != CG_E_INVALID ||
+            cg_image_encode_exr_host(nullptr, 1, 1, 0, &ok, &byte, 1, &n) != CG_E_INVALID ||
+            cg_image_encode_exr_host(one, 1, 1, 0, &ok, nullptr, 1, &n) != CG_E_INVALID ||
+            cg_image_encode_exr_host(one, 1, 1, 0, &ok, &byte, 1, nullptr) != CG_E_INVALID ||
+            cg_image_encode_exr_host(one, 2, 1, 1, &ok, &byte, 1, &n) != CG_E_INVALID ||
+            cg_image_exr_header(1, 1, &ok, hdr, 312, &n) != CG_E_CAPACITY || n != 313 ||
+            cg_image_exr_half(nullptr, 1, hv.data()) != CG_E_INVALID || cg_image_exr_bound(0, 1, CG_EXR_RGB, CG_EXR_HALF) != CG_E_INVALID ||
+            cg_image_exr_bound(1, 1, 5, CG_EXR_HALF) != CG_E_INVALID || cg_image_exr_bound(65535, 65535, CG_EXR_RGBA, CG_EXR_FLOAT) <= 0)
+            fail("exr encoder refusals", -1);
+    }
     const int malformed = malformed_jpegs();
     printf("sanitized host code: %d JPEGs, %d malformed JPEGs rejected, %d JPEGs encoded, %d PNGs encoded, "
-           "%ld clipped triangles, clean\n",
-           checked, malformed, encoded, png_encoded, tris);
+           "%d EXRs encoded, %ld clipped triangles, clean\n",
+           checked, malformed, encoded, png_encoded, exr_encoded, tris);
     return 0;
 }

@@ -1214,6 +1214,112 @@ int cg_rast_draw_sequence_png(cg_ctx *ctx, const cg_rast_params *ps, int n_frame
                               uint8_t *out, size_t cap, size_t *offsets, int chunk, cg_rast_seq_frame *info,
                               cg_stats *stats);
 
+/* ---- EXR encoding ------------------------------------------------------- */
+/* An OpenEXR encoder for CG_PIX_RGBA_F32 pictures: a single-part scanline OpenEXR 2 file that any
+ * EXR reader accepts.  As with the PNG encoder the bytes are this library's own and are fixed by
+ * the rules below, all integer arithmetic except the one float32 product of rule 1; the host
+ * function and the kernels share them (csrc/cg_exr_enc.h) and produce the same file.
+ *
+ * 1 Samples   Source pixel (x, y, z, w) gives R = x, G = y, B = z, and A = w when alpha_scale's
+ *             bits are 0x3F800000, else the single float32 product w * alpha_scale (the raytracer's
+ *             w counts 0 .. 9 samples; its app passes 1.0f / 9.0f).  CG_EXR_FLOAT stores the 32
+ *             bits unchanged.  CG_EXR_HALF rounds to nearest even: with a = the bits without the
+ *             sign, a > 0x7F800000 (NaN) gives 0x7C00 | (mantissa >> 13), bit 0 set when that
+ *             leaves the mantissa 0; a >= 0x47800000 gives inf; a >= 0x38800000 gives (a -
+ *             0x38000000) >> 13, one more when the 13 bits dropped exceed 0x1000 or equal it with
+ *             the result odd (a carry into the exponent is right, up to inf); a < 0x33000000 gives
+ *             0; otherwise (0x800000 | mantissa) >> (126 - exponent) rounded the same way on the
+ *             bits dropped.  The sign is kept throughout.  numpy's astype(float16) gives the same
+ *             bits.  Samples are little endian.
+ * 2 Header    76 2F 31 01, 02 00 00 00, then the attributes channels (chlist), compression
+ *             (compression: one byte 0 or 3), dataWindow (box2i 0, 0, W - 1, H - 1), displayWindow
+ *             (the same), lineOrder (lineOrder: byte 0), pixelAspectRatio (float 1.0),
+ *             screenWindowCenter (v2f 0, 0), screenWindowWidth (float 1.0) in that order, each as
+ *             name\0, type\0, int32 size, value; then one 0 byte.  A chlist entry is name\0, int32
+ *             pixel type (1 half, 2 float), a byte 0, three bytes 0, int32 1, int32 1; the list
+ *             ends with a 0 byte.  Channels are in name order, A B G R or B G R.  331 bytes for
+ *             RGBA, 313 for RGB.  A 2 x 1 RGB half ZIP file's header:
+ *               762f3101 02000000 6368616e6e656c7300 63686c69737400 37000000
+ *               4200 01000000 00000000 01000000 01000000  4700 01000000 00000000 01000000 01000000
+ *               5200 01000000 00000000 01000000 01000000  00
+ *               636f6d7072657373696f6e00 636f6d7072657373696f6e00 01000000 03
+ *               6461746157696e646f7700 626f78326900 10000000 00000000 00000000 01000000 00000000
+ *               646973706c617957696e646f7700 626f78326900 10000000 00000000 00000000 01000000 00000000
+ *               6c696e654f7264657200 6c696e654f7264657200 01000000 00
+ *               706978656c417370656374526174696f00 666c6f617400 04000000 0000803f
+ *               73637265656e57696e646f7743656e74657200 76326600 08000000 00000000 00000000
+ *               73637265656e57696e646f77576964746800 666c6f617400 04000000 0000803f  00
+ * 3 Chunks    CG_EXR_NONE: one scanline a chunk.  CG_EXR_ZIP: scanlines 16 k .. 16 k + 15, fewer
+ *             in the last.  After the header one uint64 per chunk, its offset from the start of
+ *             the file; then the chunks in order, each int32 first y, int32 data length, data.
+ * 4 Pixels    A chunk's n raw bytes are, per scanline, each channel's W samples back to back in
+ *             channel order.  n is even.
+ * 5 ZIP       t = the raw bytes at even positions, then those at odd positions.  d[0] = t[0], d[i]
+ *             = (t[i] - t[i - 1] + 128) mod 256.  The zlib stream of d is what the PNG rules 4 - 8
+ *             give a file of this one band: 78 01, the band's block(s) with BFINAL on the last,
+ *             zero bits to the byte, the Adler-32 of d.  If the stream has fewer than n bytes it
+ *             is the chunk's data; otherwise the data is the n raw bytes (OpenEXR's own fallback:
+ *             its readers take a chunk of exactly n bytes as uncompressed). */
+#define CG_EXR_RGB 3
+#define CG_EXR_RGBA 4
+#define CG_EXR_HALF 1
+#define CG_EXR_FLOAT 2
+#define CG_EXR_NONE 0
+#define CG_EXR_ZIP 3
+typedef struct { int channels; int type; int compression; float alpha_scale; } cg_exr_params;
+/* Host-only (no device, no context).  A NULL params is RGBA, HALF, ZIP, alpha scale 1.
+ * cg_image_encode_exr_host: as cg_image_encode_png_host -- the file of the picture rgba (4 floats
+ * a pixel, rows row_stride_pixels apart, 0: width) into out[0 .. cap), its length into *n,
+ * CG_E_CAPACITY with *n = the length needed when cap is short (no byte at or past cap is written;
+ * out may be NULL with cap 0).  cg_image_exr_bound: header + 8 * chunks + the sum of 8 + n over
+ * the chunks: a NONE file's exact length, and no ZIP file exceeds it.  cg_image_exr_header: the
+ * header's bytes into out[0 .. cap), their count into *n (CG_E_CAPACITY if cap is short).
+ * cg_image_exr_half: rule 1's conversion of n floats.  cg_image_exr_enc_limits: the lanes of a
+ * chunk workgroup (the bytes of d it takes at a time) and the bytes of a chunk's bit string it
+ * holds in LDS.  CG_E_INVALID for a width or height outside 1 .. 65535, unknown enum values, an
+ * alpha_scale that is not finite, NULL pointers. */
+int cg_image_encode_exr_host(const float *rgba, int width, int height, size_t row_stride_pixels,
+                             const cg_exr_params *params, uint8_t *out, size_t cap, size_t *n);
+long long cg_image_exr_bound(int width, int height, int channels, int type);
+int cg_image_exr_header(int width, int height, const cg_exr_params *params, uint8_t *out, size_t cap, size_t *n);
+int cg_image_exr_half(const float *values, int n, uint16_t *halves);
+int cg_image_exr_enc_limits(int *threads, int *window_bytes);
+/* n_frames pictures in device memory, with cg_image_encode_png_device's conventions in every
+ * respect: enqueued on `stream` (NULL: the context's) without a host wait; frame f is read at
+ * d_rgba + 4 * f * frame_stride floats (frame_stride in pixels, 0: width * height; d_rgba 16-byte
+ * aligned), its file goes to d_out + f * slot_bytes and its length to d_bytes[f] (8-byte aligned),
+ * or CG_E_CAPACITY there when the file is longer than slot_bytes: then nothing is written to that
+ * slot, and the other frames are unaffected.  Nothing is written past a file's last byte.  The
+ * predicted bytes and staged streams of up to 8 frames live in grow-only scratch the context owns,
+ * one set per context: calls on one context must be ordered among themselves.  n_frames == 0
+ * returns CG_OK and touches nothing. */
+int cg_image_encode_exr_device(cg_ctx *ctx, const float *d_rgba, int width, int height, int n_frames,
+                               size_t frame_stride, const cg_exr_params *params, uint8_t *d_out, size_t slot_bytes,
+                               int64_t *d_bytes, void *stream);
+/* One picture in host memory through the device encoder, arguments as cg_image_encode_exr_host;
+ * waits for the file. */
+int cg_image_encode_exr(cg_ctx *ctx, const float *rgba, int width, int height, size_t row_stride_pixels,
+                        const cg_exr_params *params, uint8_t *out, size_t cap, size_t *n);
+/* Key scripts of float pictures delivered into host memory as files: cg_rt_render_sequence_png's
+ * and cg_rast_draw_sequence_png's arguments and behaviour with EXR files of the scene-linear
+ * picture before the clamp.  Chunks of `chunk` frames (0: 8, at most 8 -- a float frame is 16
+ * bytes a pixel; the raytracer's call clamps a larger value, the rasteriser's refuses it as it
+ * refuses one above 64 for PNG) are rendered as CG_PIX_RGBA_F32 by cg_rt_render_sequence_device /
+ * cg_rast_draw_sequence_picture_device's route into the scratch the exposed calls own, encoded
+ * behind their render into slots of cg_image_exr_bound, and exactly a chunk's file bytes are
+ * copied into `out` back to back while the next chunk renders.  offsets[f] .. offsets[f + 1] is
+ * frame f's file: with CG_EXR_FLOAT its samples are those floats bit for bit, with CG_EXR_HALF
+ * their halves by rule 1.  If `out` (cap bytes) is short the call returns CG_E_CAPACITY: the
+ * files that fit whole before the first that does not are intact, nothing is written past cap,
+ * and offsets[n_frames] is the capacity a second call needs.  The rasteriser's rand() index chain
+ * and `info` records equal cg_rast_draw_sequence's. */
+int cg_rt_render_sequence_exr(cg_ctx *ctx, const cg_light *lights, int n_lights, const cg_rt_camera *cams, int n_frames,
+                              const cg_exr_params *params, uint8_t *out, size_t cap, size_t *offsets, int chunk,
+                              cg_stats *stats);
+int cg_rast_draw_sequence_exr(cg_ctx *ctx, const cg_rast_params *ps, int n_frames, const cg_exr_params *params,
+                              uint8_t *out, size_t cap, size_t *offsets, int chunk, cg_rast_seq_frame *info,
+                              cg_stats *stats);
+
 /* ---- measurement ----------------------------------------------------- */
 /* Live device time of the hot kernels: while on, a start / stop HIP event
  * pair rides on each launch's own dispatch (hipExtLaunchKernel) of
@@ -1223,8 +1329,9 @@ int cg_rast_draw_sequence_png(cg_ctx *ctx, const cg_rast_params *ps, int n_frame
  * rast_fill_kernel and rast_post_kernel, on the stream it runs on, plus
  * "rt_big_frame" (a large scene's whole frame: events recorded around it) and, for a large scene's
  * hits-only pass (cg_rt_hits_device), "rt_hits_pass" (the whole pass), "rt_hits_walk" and
- * "rt_hits_gather", and the PNG encoder's png_enc_filter_kernel, png_enc_band_kernel,
- * png_enc_scan_kernel and png_enc_gather_kernel.  cg_kernel_timing(on)
+ * "rt_hits_gather", the PNG encoder's png_enc_filter_kernel, png_enc_band_kernel,
+ * png_enc_scan_kernel and png_enc_gather_kernel, and the EXR encoder's exr_enc_plane_kernel,
+ * exr_enc_chunk_kernel, exr_enc_scan_kernel and exr_enc_gather_kernel.  cg_kernel_timing(on)
  * resets the totals (process-wide); cg_kernel_time waits for the recorded
  * launches and returns one kernel's summed launch milliseconds, its busy
  * milliseconds (the union of its launches' spans: launches that overlap on
